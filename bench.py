@@ -3,7 +3,7 @@
 50 Dormand-Prince steps (BASELINE.json configs[1]; "dopri5-50" of BASELINE.md = 301 network
 evaluations per solve), on N MI355X of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one full latent -> latent solve of a batch of 64 synthetic latents per GPU (weak scaling:
@@ -246,6 +246,31 @@ def group_timeout():
     return datetime.timedelta(seconds=float(os.environ.get("USPACE_BENCH_PG_TIMEOUT_S", "600")))
 
 
+DUMP_CAP_BYTES = 64 * 10 ** 6        # --dump-outputs: bytes on disk, all files together
+NPY_HEADER_BYTES = 1024              # bound on the header np.save writes in front of an array of a few dimensions
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32, at most `cap` bytes on disk in all.  An array that does not fit in
+    what is left is replaced by a fixed, seeded sample of its rows (sorted), and the indices of those rows go to <name>_rows.npy
+    (float64).  Returns {file name: shape} of what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    written, left = {}, cap
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        left -= NPY_HEADER_BYTES
+        if a.nbytes > left:
+            left -= NPY_HEADER_BYTES                          # the index file's
+            keep = max(left, 0) // (a[0].nbytes + 8)          # a row + its float64 index
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False)).astype(np.float64)
+            a = a[rows.astype(np.int64)]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows)
+            written[f"{name}_rows.npy"], left = list(rows.shape), left - rows.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[f"{name}.npy"], left = list(a.shape), left - a.nbytes
+    return written
+
+
 def relaunch_argv(gpus, port, argv):
     """The one-rank-per-GPU launch of this script on one node (the form the driver uses for N > 1)."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}",
@@ -275,7 +300,11 @@ def main():
     ap.add_argument("--ode-steps", type=int, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the auxiliary Euler-50 / VAE / roofline measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the whole job's final latents) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = dict(CONFIGS[args.config])
     for k in ("model", "batch", "solver", "ode_steps"):
         if getattr(args, k) is not None:
@@ -392,6 +421,9 @@ def main():
         dt, median_ms = float(tt[0].item()), float(tt[1].item())
         rows_ok = float(tt[2].item()) == 0.0        # MAX over ranks of "my rows of the LAST timed solve's gathered batch differ from my own solve"
         assert rows_ok, "a rank's rows of the gathered batch differ from its own solve"
+        dumped = None
+        if args.dump_outputs and rank == 0:        # the gathered batch of the last timed solve, before any later solve runs
+            dumped = dump_outputs(args.dump_outputs, dict(latents=res.detach().float().cpu().numpy()))
 
         # ---- outside the timed region: rooflines.  One more solve with eager launches and HIP events recorded (by the
         #      library, on the launching stream) around every GEMM and attention launch
@@ -514,6 +546,8 @@ def main():
             "mfma_util_whole_solve": fps * B * nfe * args.steps / dt / 1e12 / MFMA_BF16_PEAK_TFLOPS,
         }
         line.update(extra)
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if recs:
             all_rows = roofline_rows(recs, D)
             line["roofline_all"] = all_rows

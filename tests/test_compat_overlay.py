@@ -1,7 +1,7 @@
 """compat/: the reference's scripts must find this package under the reference's own import names
 (flow_matching.CNF dissect_lfm.py:2, flow_matching_t2i.CNF dissect_lfm_t2i.py:11, tools.utils_uvit.get_nnet
 dissect_lfm.py:67 -> libs.uvit / libs.uvit_t2i tools/utils_uvit.py:27-41) while everything else keeps coming from the
-reference tree.  A miniature reference tree stands in for /root/reference (which does not exist on the GPU box)."""
+reference tree.  Miniature reference trees, written by the tests, stand in for the reference itself."""
 import json
 import os
 import subprocess
@@ -113,28 +113,216 @@ def test_compat_first_on_sys_path_resolves_to_this_package(tmp_path):
     assert out.strip().endswith("ok")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tools"), reason="reference tree not present on this machine")
-def test_against_the_real_reference_tree(tmp_path):
-    """In the build container: the real reference's `tools.utils_uvit` is shadowed and re-exported (its own imports need the
-    leaf-library shims of tests/golden/_refshim.py), `get_nnet` answers from this package."""
+# A PyTorch U-ViT (Bao et al., "All are Worth Words: A ViT Backbone for Diffusion Models", CVPR 2023) with the reference's
+# constructor arguments, parameter names and forward calling convention: the miniature tree's libs/uvit.py and libs/uvit_t2i.py.
+# Written for these tests from the paper's architecture and this repository's fp32 restatement (oracle/uvit_oracle.py), and checked
+# only through the reference's outputs: test_miniature_reference_uvit_reproduces_the_golden_outputs pins it to tests/golden/tiny_*.npz.
+# The parameter names are the reference's because the overlay's twin loads this package's state_dict into it strictly.
+MINI_UVIT = """
+import math
+
+import torch
+import torch.nn as nn
+import torch.utils.checkpoint
+
+T2I = %(t2i)r
+
+
+class Attention(nn.Module):
+    def __init__(self, dim, num_heads):
+        super().__init__()
+        self.num_heads = num_heads
+        self.qkv = nn.Linear(dim, dim * 3, bias=False)
+        self.proj = nn.Linear(dim, dim)
+
+    def forward(self, x):
+        B, L, D = x.shape
+        q, k, v = self.qkv(x).reshape(B, L, 3, self.num_heads, D // self.num_heads).permute(2, 0, 3, 1, 4)
+        a = (q @ k.transpose(-2, -1) * (D // self.num_heads) ** -0.5).softmax(dim=-1)
+        return self.proj((a @ v).transpose(1, 2).reshape(B, L, D))
+
+
+class Mlp(nn.Module):
+    def __init__(self, dim, hidden):
+        super().__init__()
+        self.fc1, self.act, self.fc2 = nn.Linear(dim, hidden), nn.GELU(), nn.Linear(hidden, dim)
+
+    def forward(self, x):
+        return self.fc2(self.act(self.fc1(x)))
+
+
+class Block(nn.Module):
+    def __init__(self, dim, num_heads, mlp_ratio, skip=False, use_checkpoint=False):
+        super().__init__()
+        self.norm1, self.attn = nn.LayerNorm(dim), Attention(dim, num_heads)
+        self.norm2, self.mlp = nn.LayerNorm(dim), Mlp(dim, int(dim * mlp_ratio))
+        self.skip_linear = nn.Linear(2 * dim, dim) if skip else None
+        self.use_checkpoint = use_checkpoint
+
+    def forward(self, x, skip=None):
+        if self.use_checkpoint:     # reentrant: the mode the reference's checkpoint call (no use_reentrant given) runs in
+            return torch.utils.checkpoint.checkpoint(self.run, x, skip, use_reentrant=True)
+        return self.run(x, skip)
+
+    def run(self, x, skip=None):
+        h = x if skip is None else self.skip_linear(torch.cat([x, skip], dim=-1))     # long skip: one linear over [x | skip]
+        h = h + self.attn(self.norm1(h))                                                # pre-LN attention
+        return h + self.mlp(self.norm2(h))                                              # pre-LN MLP
+
+
+def timestep_embedding(t, dim):
+    half = dim // 2
+    f = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32, device=t.device) / half)
+    a = t.float()[:, None] * f[None]
+    return torch.cat([torch.cos(a), torch.sin(a)], dim=-1)
+
+
+class UViT(nn.Module):
+    def __init__(self, img_size=32, patch_size=2, in_chans=4, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0,
+                 qkv_bias=False, mlp_time_embed=False, num_classes=-1, clip_dim=768, num_clip_token=77, use_checkpoint=False,
+                 conv=True, skip=True):
+        super().__init__()
+        assert not qkv_bias and not mlp_time_embed and conv and skip, "the miniature covers the configurations used here"
+        self.patch_size, self.in_chans = patch_size, in_chans
+        self.extras = 1 + (num_clip_token if T2I else int(num_classes > 0))
+        self.pos_embed = nn.Parameter(torch.zeros(1, self.extras + (img_size // patch_size) ** 2, embed_dim))
+        self.patch_embed = nn.Module()
+        self.patch_embed.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
+        if T2I:
+            self.context_embed = nn.Linear(clip_dim, embed_dim)
+        elif num_classes > 0:
+            self.label_emb = nn.Embedding(num_classes, embed_dim)
+        blk = lambda skip: Block(embed_dim, num_heads, mlp_ratio, skip=skip, use_checkpoint=use_checkpoint)
+        self.in_blocks = nn.ModuleList([blk(False) for _ in range(depth // 2)])
+        self.mid_block = blk(False)
+        self.out_blocks = nn.ModuleList([blk(True) for _ in range(depth // 2)])
+        self.norm = nn.LayerNorm(embed_dim)
+        self.decoder_pred = nn.Linear(embed_dim, patch_size ** 2 * in_chans)
+        self.final_layer = nn.Conv2d(in_chans, in_chans, 3, padding=1)
+
+    def forward(self, x, timesteps, y=None, context=None, **kwargs):
+        # the reference's libs/uvit.py reads kwargs["edit_loc"] unconditionally (KeyError without it); its libs/uvit_t2i.py does not
+        if not T2I and kwargs["edit_loc"] is not None:
+            raise NotImplementedError("the miniature has no u-space hooks")
+        B, C, H, W = x.shape
+        p, g = self.patch_size, H // self.patch_size
+        tok = self.patch_embed.proj(x).flatten(2).transpose(1, 2)
+        time_tok = timestep_embedding(timesteps.expand(B), self.pos_embed.shape[-1])[:, None]
+        if T2I:
+            h = torch.cat([time_tok, self.context_embed(context), tok], dim=1)
+        else:
+            h = torch.cat([time_tok, tok], dim=1)
+            if y is not None:
+                h = torch.cat([self.label_emb(y)[:, None], h], dim=1)
+        h = h + self.pos_embed
+        skips = []
+        for b in self.in_blocks:
+            h = b(h)
+            skips.append(h)
+        h = self.mid_block(h)
+        for b in self.out_blocks:
+            h = b(h, skips.pop())
+        h = self.decoder_pred(self.norm(h))[:, self.extras:]
+        img = h.reshape(B, g, g, p, p, C).permute(0, 5, 1, 3, 2, 4).reshape(B, C, H, W)
+        return self.final_layer(img), None
+"""
+
+MINI_UTILS_UVIT = """
+def set_logger(*a, **k):
+    return 'reference set_logger'
+
+
+def get_nnet(name, **kwargs):
+    if name == 'uvit':
+        from libs.uvit import UViT
+        return UViT(**kwargs)
+    elif name == 'uvit_t2i':
+        from libs.uvit_t2i import UViT
+        return UViT(**kwargs)
+    raise NotImplementedError(name)
+
+
+class TrainState:
+    pass
+
+
+def amortize(n_samples, batch_size):
+    k, r = divmod(n_samples, batch_size)
+    return k * [batch_size] + ([r] if r else [])
+
+
+def sample2dir(*a, **k):
+    raise NotImplementedError
+"""
+
+
+def make_miniature_reference(root):
+    """The fake tree of make_fake_reference, but with a working U-ViT (MINI_UVIT) and a `tools.utils_uvit` that holds more than
+    the overlay answers (TrainState, amortize, sample2dir): what a training script finds in the reference tree."""
+    make_fake_reference(root)
+    for rel, text in {"libs/uvit.py": MINI_UVIT % dict(t2i=False), "libs/uvit_t2i.py": MINI_UVIT % dict(t2i=True),
+                      "tools/utils_uvit.py": MINI_UTILS_UVIT}.items():
+        with open(os.path.join(root, rel), "w") as f:
+            f.write(text)
+
+
+def test_miniature_reference_uvit_reproduces_the_golden_outputs(tmp_path, golden_dir):
+    """The miniature tree's U-ViT takes the reference network's state_dicts as they are (strict) and computes the reference's outputs on
+    the golden inputs (tests/golden/tiny_*.npz, produced by the reference itself): a faithful stand-in for the test below."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    make_miniature_reference(str(tmp_path))
+
+    def load(rel, name):
+        spec = importlib.util.spec_from_file_location(name, str(tmp_path / rel))
+        m = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(m)
+        return m
+
+    U, T = load("libs/uvit.py", "mini_uvit"), load("libs/uvit_t2i.py", "mini_uvit_t2i")
+    tiny = dict(img_size=16, patch_size=2, in_chans=4, embed_dim=64, depth=2, num_heads=1, mlp_ratio=4)
+    cases = [("tiny_u.npz", U, dict(num_classes=-1)), ("tiny_u_cond.npz", U, dict(num_classes=10)),
+             ("tiny_t2i.npz", T, dict(clip_dim=64, num_clip_token=77))]
+    for fname, mod, extra in cases:
+        z = np.load(os.path.join(golden_dir, fname))
+        net = mod.UViT(**tiny, **extra)
+        net.load_state_dict({k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd/")}, strict=True)
+        net.eval()
+        x = torch.from_numpy(z["x"])
+        kw = dict(context=torch.from_numpy(z["ctx"])) if "ctx" in z.files else {}
+        if "y" in z.files:
+            kw["y"] = torch.from_numpy(z["y"]).long()
+        runs = [(z["tval"], z["out"])] if "tval" in z.files else [(tv, z[f"out{i}"]) for i, tv in enumerate(z["tvals"])]
+        for tv, want in runs:
+            with torch.no_grad():
+                out, aux = net(x, torch.full((x.shape[0],), float(tv)), edit_loc=None, **kw)
+            assert aux is None
+            np.testing.assert_allclose(out.numpy(), want, rtol=2e-5, atol=2e-5, err_msg=f"{fname} t={float(tv)}")
+
+
+def test_against_a_miniature_reference_tree(tmp_path):
+    """The reference's `tools.utils_uvit` is shadowed and re-exported, `get_nnet` answers from this package, and `training_losses`
+    delegates to the tree's own U-ViT over this package's parameters.  The tree is the miniature of make_miniature_reference, whose
+    U-ViT is pinned to the reference's outputs by the test above."""
+    make_miniature_reference(str(tmp_path))
     code = textwrap.dedent("""
         import sys
         sys.dont_write_bytecode = True
-        sys.path.insert(0, %r)
-        from tests.golden import _refshim
-        _refshim.install()          # leaf-library stand-ins; also appends /root/reference to sys.path
-        for m in [k for k in sys.modules if k.split('.')[0] in ('tools', 'libs')]:
-            del sys.modules[m]
         sys.path[:0] = [%r, %r]
+        sys.path.append(%r)         # the reference tree, behind this package (as run_ref.py orders them)
         import _overlay; _overlay.install()
         import tools.utils_uvit as u
         from flow_matching import CNF
         net = u.get_nnet('uvit', img_size=32, patch_size=2, in_chans=4, embed_dim=64, depth=2, num_heads=1)
         assert type(net).__module__ == 'uspace_amd.libs.uvit', type(net).__module__
         assert CNF.__module__ == 'uspace_amd.flow_matching'
-        assert hasattr(u, 'TrainState') and hasattr(u, 'sample2dir') and u.amortize(5, 2) == [2, 2, 1]
+        assert u.TrainState.__module__ == 'tools._ref_utils_uvit' and u.sample2dir.__module__ == 'tools._ref_utils_uvit'
+        assert u.amortize(5, 2) == [2, 2, 1]
         # ---- train_lfm.py:154-183 / train_lfm_t2i.py:190-204: `score_model.training_losses(...)`, `.mean().backward()`, on CPU.
-        # The loss is the reference's own forward (libs/uvit.py:306-351) over THIS module's parameters (compat/_training.py).
+        # The loss is the tree's own U-ViT forward over THIS module's parameters (compat/_training.py).
         import torch
         torch.manual_seed(3)
         score = CNF(net=net)
@@ -145,7 +333,7 @@ def test_against_the_real_reference_tree(tmp_path):
         loss.mean().backward()
         grads = {n: p.grad for n, p in net.named_parameters()}
         assert all(g is not None for g in grads.values()) and sum(float(g.abs().sum()) for g in grads.values()) > 0
-        # the same numbers as the reference computes by itself: its own UViT with this state_dict, its formula (flow_matching.py:88-100)
+        # the same numbers as the tree computes by itself: its own UViT with this state_dict, the reference's formula (flow_matching.py:88-100)
         import libs._ref_uvit as R
         ref = R.UViT(img_size=32, patch_size=2, in_chans=4, embed_dim=64, depth=2, num_heads=1)
         ref.load_state_dict(net.state_dict(), strict=True)
@@ -191,7 +379,7 @@ def test_against_the_real_reference_tree(tmp_path):
         _training.refresh(net_ck)
         assert calls == [1, 1]
         print('ok')
-    """ % (ROOT, COMPAT, ROOT))
+    """ % (COMPAT, ROOT, str(tmp_path)))
     out = run([sys.executable, "-c", code], str(tmp_path), {"PYTHONDONTWRITEBYTECODE": "1"})
     assert out.strip().endswith("ok")
 

@@ -266,7 +266,23 @@ class _CpuRuntime:
         return "cpu stand-in"
 
 
-def _bench_main_worker(rank, world, port, outdir):
+class _PerSolveKernels(_FakeKernels):
+    """_FakeKernels whose velocity changes from one solve to the next: v(x) = -(1 + s / 8) x during the s-th solve of the process
+    (s = evaluations so far // `nfe`, every solve of interest taking `nfe` evaluations), so that every solve ends somewhere else."""
+
+    def __init__(self, real, nfe):
+        super().__init__(real)
+        self.nfe = nfe
+
+    def uspace_uvit_forward(self, cfg, blob, ws, ws_bytes, io, B, stream):
+        c, o = cfg._obj, io._obj
+        n = B * c.in_chans * c.img_size * c.img_size
+        self._arr(o.out, n)[:] = -(1.0 + (self.forwards // self.nfe) / 8) * self._arr(o.x, n)
+        self.forwards += 1
+        return 0
+
+
+def _bench_main_worker(rank, world, port, outdir, argv=("--steps", "2", "--warmup", "1"), per_solve_nfe=None):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank), LOCAL_RANK=str(rank))
     sys.path.insert(0, ROOT)
     import contextlib
@@ -274,7 +290,7 @@ def _bench_main_worker(rank, world, port, outdir):
 
     import bench
     from uspace_amd import _hip
-    fake = _FakeKernels(_hip.lib())
+    fake = _FakeKernels(_hip.lib()) if per_solve_nfe is None else _PerSolveKernels(_hip.lib(), per_solve_nfe)
     _hip.lib = lambda: fake
     _hip.require_device = lambda t, name="tensor": None
     _hip.stream_ptr = lambda: None
@@ -282,7 +298,7 @@ def _bench_main_worker(rank, world, port, outdir):
     bench.RUNTIME = _CpuRuntime
     bench.MODELS["tiny_u"] = dict(name="uvit", embed_dim=64, depth=2, num_heads=1, num_classes=-1)
     bench.CONFIGS[2] = dict(model="tiny_u", batch=3, solver="dopri5", ode_steps=4, hook=False)
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    sys.argv = ["bench.py", "--gpus", str(world), *argv, "--no-cpu-baseline"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
@@ -327,3 +343,68 @@ def test_bench_main_runs_end_to_end_on_two_gloo_ranks(tmp_path):
     adaptive1 = 2 * line["dopri5_adaptive_nfe"][1] + 2 * line["dopri5_adaptive_norm_group_nfe"][1]
     adaptive0 = 2 * line["dopri5_adaptive_nfe"][0] + 2 * line["dopri5_adaptive_norm_group_nfe"][0]
     assert f1 == 3 * 25 + 2 * 4 + adaptive1 and f0 == 4 * 25 + 2 * 4 + adaptive0
+
+
+def _run_bench_worker(tmp_path, tag, world, argv, per_solve_nfe=None):
+    outdir = tmp_path / tag
+    outdir.mkdir()
+    ctx = mp.get_context("spawn")
+    port = _free_port()
+    procs = [ctx.Process(target=_bench_main_worker, args=(r, world, port, str(outdir), tuple(argv), per_solve_nfe)) for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(240)
+        assert p.exitcode == 0
+    return json.loads(open(outdir / "rank0.txt").read().strip().splitlines()[-1]), int(open(outdir / "forwards0.txt").read())
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_dump_outputs_is_the_last_timed_solve(tmp_path, world):
+    """--dump-outputs DIR: rank 0 writes the whole job's final latents of the last timed solve as DIR/latents.npy in float32.  Every
+    solve of a rank runs a different network (_PerSolveKernels: v = -(1 + s / 8) x in the s-th solve), so the dump names its solve: with
+    2 warm-up and 3 timed solves it must be the end state of solve 4 -- not a warm-up, not an earlier timed solve, and not one of the
+    solves after the timed region (run b keeps the extra measurements on).  Expected values: the oracle's dopri5 on 4 equal steps from
+    z, z from the seeded generator of each rank.  Two runs with the same inputs write the same array; --steps K is the number of timed
+    solves (K per-step timings, K solves' worth of network evaluations)."""
+    from oracle import odeint_oracle as OO
+    import bench
+    nfe = 1 + 6 * 4
+    z = torch.cat([torch.randn(3, 4, 32, 32, generator=torch.Generator().manual_seed(7 + r)) for r in range(world)]).numpy()
+    ends = [OO.solve(lambda t, y, k=1.0 + s / 8: -k * y, z.astype(np.float64), 0.0, 1.0, method="dopri5", n_steps=4) for s in range(7)]
+    dumps = []
+    for run, extra in (("a", ["--no-extra"]), ("b", [])):
+        d = tmp_path / f"dump_{run}"
+        line, forwards = _run_bench_worker(tmp_path, run, world, ["--steps", "3", "--warmup", "2", "--dump-outputs", str(d)] + extra,
+                                           per_solve_nfe=nfe)
+        assert line["steps"] == 3 and len(line["per_step_ms_rank0"]) == 3 and line["nfe"] == nfe
+        if extra:
+            assert forwards == (2 + 3) * nfe                                        # warm-up + timed solves, nothing else (--no-extra)
+        else:
+            assert forwards > (2 + 3 + 1) * nfe                                     # solves after the timed region did run
+        assert sorted(os.listdir(d)) == ["latents.npy"] and line["dumped_outputs"]["files"] == {"latents.npy": [3 * world, 4, 32, 32]}
+        dumps.append(np.load(d / "latents.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (3 * world, 4, 32, 32)
+    np.testing.assert_array_equal(a, b)
+    np.testing.assert_allclose(a, ends[4], rtol=1e-5, atol=1e-6)
+    assert [np.allclose(a, e, rtol=1e-3, atol=0) for e in ends] == [s == 4 for s in range(7)]
+    assert bench.DUMP_CAP_BYTES <= 64 * 10 ** 6
+
+
+def test_bench_dump_outputs_samples_rows_of_an_output_over_the_cap(tmp_path):
+    """An output larger than the cap is written as a fixed, seeded sample of its rows plus their indices; the total stays under the cap."""
+    import bench
+    a = np.arange(100 * 4 * 8, dtype=np.float32).reshape(100, 4, 8)
+    cap = 40 * (a[0].nbytes + 8) + 2 * bench.NPY_HEADER_BYTES
+    w1 = bench.dump_outputs(str(tmp_path / "one"), dict(latents=a), cap=cap)
+    w2 = bench.dump_outputs(str(tmp_path / "two"), dict(latents=a), cap=cap)
+    assert w1 == w2 == {"latents_rows.npy": [40], "latents.npy": [40, 4, 8]}
+    rows = np.load(tmp_path / "one" / "latents_rows.npy")
+    got = np.load(tmp_path / "one" / "latents.npy")
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(got, a[rows.astype(np.int64)])
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "two" / "latents_rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "one" / f) for f in os.listdir(tmp_path / "one")) <= cap
+    small = bench.dump_outputs(str(tmp_path / "small"), dict(latents=a[:10].astype(np.float64)), cap=cap)
+    assert small == {"latents.npy": [10, 4, 8]} and np.load(tmp_path / "small" / "latents.npy").dtype == np.float32
