@@ -153,7 +153,9 @@ USPACE_API int uspace_gemm_plan(int M, int N, int* out);
 /* ... of a launch with this K and role (producer of LayerNorm partial sums or not), i.e. what the dispatcher really launches:
  * few-tile launches use 64x64 tiles (out[0] = 5, out[2] = out[3] = 64; K selects their K loop and with it out[7]: 512 workgroups
  * per round for the four-stage ring, 1024 for the two-stage form); a producer never takes the split form (reported as 256x256) nor
- * 128-wide tiles that would make more than 8 partial-sum slots (reported as 256x256). */
+ * 128-wide tiles that would make more than 8 partial-sum slots (reported as 256x256).  The answer assumes a launch that may take
+ * the K-split tail; a uspace_gemm_slabs_bf16 launch of more than 2 slabs never does (3x3 convolutions: 9): for it, ask with
+ * uspace_gemm_set_sk(0). */
 USPACE_API int uspace_gemm_plan_k(int M, int N, int K, int producer, int* out);
 
 /* Sum of row-shifted GEMMs:  acc[m, n] = sum_t A[m + row_shift[t], 0:K1] . W[n, t*K1:(t+1)*K1]  (+ epilogue

@@ -1541,8 +1541,10 @@ extern "C" int uspace_gemm_plan(int M, int N, int* out) {
     return USPACE_OK;
 }
 
-// ... for a launch with this K and role (producer of LayerNorm partial sums or not): exactly the chain dispatch_tile applies --
-// choose_tile, producer_tile for producers (no split form, no 128-wide tiles beyond 8 slots), refine_small (64x64 tiles, out[0] = 5)
+// ... for a launch with this K and role (producer of LayerNorm partial sums or not): the chain dispatch_tile applies -- choose_tile,
+// producer_tile for producers (no split form, no 128-wide tiles beyond 8 slots), refine_small (64x64 tiles, out[0] = 5), the K-split
+// tail where it wins -- for a launch whose epilogue may take that tail.  dispatch_tile never gives it to n_slab > 2 (the 9-slab
+// convolutions of vae.hip): their form is this answer with the tail switched off (uspace_gemm_set_sk(0)).
 extern "C" int uspace_gemm_plan_k(int M, int N, int K, int producer, int* out) {
     if (M <= 0 || N <= 0 || K <= 0 || !out) return USPACE_ERR_ARG;
     int m1 = 0;

@@ -51,7 +51,12 @@ __global__ __launch_bounds__(128) void vae_conv_in_kernel(const float* __restric
 // vector (16 B loads, a pixel row of C floats is read by C/4 adjacent lanes) and strides over the chunk's
 // pixels.  Per-thread half-vector sums go through LDS and 32 threads add the 16 contributions of their group
 // in a fixed order; gn_finish_kernel adds the chunks, again in a fixed order, so repeated decodes are
-// bit-identical (no atomics).
+// bit-identical (no atomics).  The sums are of x - K, K = the group's first channel at the first interior pixel
+// (one value per (image, group), read by every chunk): var = E[(x-K)^2] - E[x-K]^2 then does not cancel when
+// the group's mean is large against its spread (on raw values it lost all digits at mean/std ~ 3e3 at 256^2).
+__device__ __forceinline__ float gn_pilot(const float* __restrict__ x, int b, int H, int W, int C, int g) {
+    return x[((size_t)b * (H + 2) + 1) * (W + 2) * C + (size_t)C + g * (C >> 5)];
+}
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ partial,
                                                        int H, int W, int C, int c4_log2, int chunks) {
     __shared__ float red[256 * 4];
@@ -64,14 +69,17 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     const int p0 = ck * per, p1 = min(npix, p0 + per);
     float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
     const float* xb = x + (size_t)b * (H + 2) * (W + 2) * C + 4 * q;
+    const int cg = C >> 5;                        // channels per group: a half-vector never straddles two groups
+    const float k0 = gn_pilot(x, b, H, W, C, (4 * q) / cg), k1 = gn_pilot(x, b, H, W, C, (4 * q + 2) / cg);
 #pragma unroll 4
     for (int p = p0 + ps; p < p1; p += PS) {
         const int y = p / W, xx = p - y * W;
         const f32x4 v = *(const f32x4*)(xb + (size_t)((y + 1) * (W + 2) + xx + 1) * C);
-        s0 += v[0] + v[1];
-        q0 += v[0] * v[0] + v[1] * v[1];
-        s1 += v[2] + v[3];
-        q1 += v[2] * v[2] + v[3] * v[3];
+        const float d0 = v[0] - k0, d1 = v[1] - k0, d2 = v[2] - k1, d3 = v[3] - k1;
+        s0 += d0 + d1;
+        q0 += d0 * d0 + d1 * d1;
+        s1 += d2 + d3;
+        q1 += d2 * d2 + d3 * d3;
     }
     red[tid * 4 + 0] = s0;
     red[tid * 4 + 1] = q0;
@@ -94,9 +102,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     }
 }
 
-// (sum, sumsq) partials -> (mean, rstd) per (image, group): one wave per pair, butterfly reduction
+// (sum, sumsq) partials of x - K -> (mean, rstd) per (image, group): one wave per pair, butterfly reduction
 __global__ __launch_bounds__(64) void gn_finish_kernel(const float* __restrict__ partial, float* __restrict__ stats,
-                                                       int chunks, float inv_n, float eps) {
+                                                       int chunks, float inv_n, float eps, const float* __restrict__ x,
+                                                       int H, int W, int C) {
     const int i = blockIdx.x;
     const int b = i >> 5, g = i & 31;
     float s = 0.f, ss = 0.f;
@@ -108,9 +117,9 @@ __global__ __launch_bounds__(64) void gn_finish_kernel(const float* __restrict__
     s = wave_sum(s);
     ss = wave_sum(ss);
     if (threadIdx.x == 0) {
-        const float mean = s * inv_n;
-        const float var = fmaxf(ss * inv_n - mean * mean, 0.f);
-        stats[2 * i] = mean;
+        const float dm = s * inv_n;
+        const float var = fmaxf(ss * inv_n - dm * dm, 0.f);
+        stats[2 * i] = gn_pilot(x, b, H, W, C, g) + dm;
         stats[2 * i + 1] = rsqrtf(var + eps);
     }
 }
@@ -456,7 +465,7 @@ extern "C" int uspace_groupnorm_map_bf16(const float* x, const float* gamma, con
     hipLaunchKernelGGL(gn_stats_kernel, dim3(B * chunks), dim3(256), 0, s, x, partial, H, H, C, c4_log2, chunks);
     US_CHECK_LAUNCH();
     hipLaunchKernelGGL(gn_finish_kernel, dim3(B * 32), dim3(64), 0, s, partial, stats_scratch, chunks,
-                       1.0f / ((float)H * (float)H * (float)(C / 32)), eps);
+                       1.0f / ((float)H * (float)H * (float)(C / 32)), eps, x, H, H, C);
     US_CHECK_LAUNCH();
     const long rows = (long)B * (H + 2) * (H + 2);
     const int rs = 256 >> c4_log2;
