@@ -14,7 +14,8 @@
  *     uspace_uvit_set_ln_fold / _get_ln_fold (atomic; default on); (3) per kernel, the set of devices on which it has
  *     been opted in to more than 64 KiB of dynamic LDS (atomic bit mask; any number of GPUs per process); (4) a
  *     mutex-protected cache of the parameter layout derived from each distinct uspace_uvit_config; (5) the switch of the GEMM's
- *     in-launch K-split tail uspace_gemm_set_sk / _get_sk (atomic; default on); (6) per device, whether it has the 256 CUs that form needs.
+ *     in-launch K-split tail uspace_gemm_set_sk / _get_sk (atomic; default on; read once per call: uspace_uvit_forward reads it once
+ *     for its workspace, its partial-sum slot counts and all of its launches); (6) per device, whether it has the 256 CUs that form needs.
  * bf16 values cross the boundary as raw uint16_t (upper half of an IEEE fp32, RNE).
  */
 #ifndef USPACE_HIP_H

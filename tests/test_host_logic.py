@@ -846,55 +846,37 @@ def test_graph_replay_is_opt_in(monkeypatch):
     assert get_nnet("uvit", **kw).use_graph is True
 
 
-def test_measurement_switches_cannot_reach_a_product_build():
-    """gemm.hip's lab hooks (tile-form override, the four-wave form of tools/lab/gemm4, the chain form) exist only under -DUSPACE_LAB=1,
-    which only the lab build scripts define: csrc/Makefile builds with -DUSPACE_LAB=0 -Werror=undef, naming a hook without the lab flag is a
-    preprocessor error, the switches that produced wrong results on purpose (ablations, same-panel staging) are gone from the source
-    (patches under tools/lab/dropped/), and no build debris (-save-temps output) is tracked next to the sources."""
+def test_lab_hook_cannot_reach_a_product_build():
+    """gemm.hip's lab hook (the tile-form override) exists only under -DUSPACE_LAB=1, which only the lab build script defines: csrc/Makefile
+    builds with -DUSPACE_LAB=0 -Werror=undef, and the hook's code is not in what that build compiles; the switches that produced wrong
+    results on purpose (ablations, same-panel staging) and the retired lab forms (four-wave, chain) are gone from the source (patches under
+    tools/lab/dropped/, or the last commit that held them), and no build debris (-save-temps output) is tracked next to the sources."""
     import shutil
     import subprocess
     csrc = os.path.join(ROOT, "uspace_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "-DUSPACE_LAB=0" in mk and "-Werror=undef" in mk and "USPACE_LAB=1" not in mk and "gemm4" not in mk
     assert "-DUSPACE_LAB=1" in open(os.path.join(ROOT, "tools", "lab", "build_variant.sh")).read()
-    assert "-DUSPACE_LAB=1" in open(os.path.join(ROOT, "tools", "lab", "gemm4", "build.sh")).read()
     src = open(os.path.join(csrc, "gemm.hip")).read()
-    for gone in ("USPACE_ABLATE", "USPACE_SAME_PANELS", "USPACE_DMA_FLAT", "USPACE_KTRACE", "USPACE_FULL_LINES", "K_STAMP"):
+    for gone in ("USPACE_ABLATE", "USPACE_SAME_PANELS", "USPACE_DMA_FLAT", "USPACE_KTRACE", "USPACE_FULL_LINES", "K_STAMP", "USPACE_FORM4", "USPACE_CHAIN"):
         assert gone not in src, gone
-    # every lab-only region is fenced by the VALUE of a hook that is 0 in a product build
+    # every lab-only region is fenced by the VALUE of the lab flag, which is 0 in a product build
     for m in re.finditer(r"^#\s*if\s+(.*)$", src, re.M):
         cond = m.group(1)
         if "USPACE_" in cond and "defined" not in cond:
-            assert re.fullmatch(r"!?USPACE_(LAB|FORM4|CHAIN)\s*", cond), cond
+            assert re.fullmatch(r"!?USPACE_LAB\s*", cond), cond
     hipcc = "/opt/rocm/bin/hipcc"
     if os.path.exists(hipcc):
-        base = [hipcc, "-std=c++17", "--offload-arch=gfx950", "--cuda-host-only", "-E", "-o", os.devnull, os.path.join(csrc, "gemm.hip")]
-        for sw in ("USPACE_FORM4=1", "USPACE_CHAIN=1", "USPACE_CHAIN_BODY=8"):
-            r = subprocess.run(base + ["-DUSPACE_LAB=0", "-D" + sw], capture_output=True, text=True)
-            assert r.returncode != 0 and "lab hooks need -DUSPACE_LAB=1" in r.stderr, (sw, r.stderr[-300:])
-        assert subprocess.run(base + ["-DUSPACE_LAB=1", "-DUSPACE_FORM4=1"], capture_output=True).returncode == 0
+        base = [hipcc, "-std=c++17", "--offload-arch=gfx950", "--cuda-host-only", "-E", "-o", "-", os.path.join(csrc, "gemm.hip")]
+        product = subprocess.run(base + ["-DUSPACE_LAB=0", "-Werror=undef"], capture_output=True, text=True)
+        assert product.returncode == 0, product.stderr[-300:]
+        assert "uspace_lab_gemm_force_tile" not in product.stdout and "g_force_tile" not in product.stdout
+        lab = subprocess.run(base + ["-DUSPACE_LAB=1", "-DUSPACE_SK_MIN_NK=16", "-DUSPACE_SK_MIN_KT=4"], capture_output=True, text=True)
+        assert lab.returncode == 0 and "uspace_lab_gemm_force_tile" in lab.stdout, lab.stderr[-300:]
     if shutil.which("git") and os.path.isdir(os.path.join(ROOT, ".git")):
         tracked = subprocess.run(["git", "-C", ROOT, "ls-files", "uspace_amd"], capture_output=True, text=True).stdout.split()
         junk = [f for f in tracked if f.endswith((".s", ".bc", ".hipi", ".o", ".so")) or "/lib.so." in f or "hipv4-amdgcn" in f]
         assert not junk, junk
-
-
-def test_lab_k_loop_text_comes_from_its_generator(tmp_path):
-    """The assembly K loop of the four-wave GEMM form (tools/lab/gemm4/, measured in round 5 and not landed) is generated text: since
-    round 6 only the generator is tracked (tools/lab/gemm4/build.sh writes kloop4.inc next to the lab build); with its default knobs
-    it must still write the loop the round-5 measurements were made with (shape checked here)."""
-    import subprocess
-    gen = os.path.join(ROOT, "tools", "lab", "gemm4", "gen_kloop4.py")
-    out = str(tmp_path / "kloop4.inc")
-    r = subprocess.run([sys.executable, gen, "--out=" + out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    if shutil.which("git") and os.path.isdir(os.path.join(ROOT, ".git")):
-        assert not subprocess.run(["git", "-C", ROOT, "ls-files", "tools/lab/gemm4/kloop4.inc"], capture_output=True, text=True).stdout.strip()
-    txt = open(out).read()
-    for form in ("KLOOP4_TEXT_00", "KLOOP4_TEXT_01", "KLOOP4_TEXT_10", "KLOOP4_TEXT_11", "KLOOP4_CLOBBERS", "KLOOP4_READ_ROW_7"):
-        assert "#define " + form in txt
-    # every text: 4 tile variants x 128 MFMAs on the main accumulators (+ 4 x 2 x 8 strip MFMAs in the strip forms)
-    assert txt.count("v_mfma_f32_16x16x32_bf16 a[") == 4 * 512
 
 
 def test_gelu_polynomial_in_the_header_keeps_its_stated_accuracy():

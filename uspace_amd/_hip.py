@@ -170,7 +170,7 @@ def lib():
 def library_info():
     """Which library is loaded: path, whether it is the in-tree product build, lab symbols it exports."""
     L = lib()
-    lab = [s for s in ("uspace_lab_gemm_force_tile", "uspace_lab_gemm_set_big_form", "uspace_lab_gemm_trace") if hasattr(L, s)]
+    lab = [s for s in ("uspace_lab_gemm_force_tile", "uspace_lab_gemm_trace") if hasattr(L, s)]
     return {"path": os.path.relpath(LIB_PATH, os.path.dirname(_HERE)), "product_build": os.path.realpath(LIB_PATH) == os.path.realpath(_DEFAULT_LIB),
             "lab_symbols": lab}
 

@@ -145,6 +145,14 @@ int us_output_head_packed(const float* tok, int L, int extras, const float* imag
 // out[n] = sum_k float(bf16(W[n * ld + col0 + k])), k < ncols (rowops.hip; pack-time companion of USPACE_EPI_RANK1)
 int us_rowsum_bf16(const float* W, int ld, int col0, int ncols, float* out, int N, hipStream_t s);
 
+// The GEMM with the switch of its K-split tail (uspace_gemm_set_sk) passed in rather than read (gemm.hip; used by uvit.hip, not
+// exported): a forward reads the switch once, so the slot counts its consumers are told and the forms its producers launch agree.
+int us_gemm_bf16_ext(const uint16_t* A, int lda, const uint16_t* A2, int lda2, int K1, const uint16_t* W, int ldw, int M, int N, int K,
+                     int epi_flags, const float* bias, const float* resid_in, int ld_resid, float* out_f32, int ld_f32, uint16_t* out_bf16,
+                     int ld_bf16, const uspace_gemm_ext* ext, bool sk_on, uspace_stream_t stream);
+int us_gemm_part_slots_k(int M, int N, int K, bool sk_on);
+size_t us_gemm_sk_ws_bytes(int M, int N, int K, bool sk_on);
+
 // Opt a kernel in to more than 64 KiB of dynamic LDS.  The attribute is per DEVICE: `done` (one per kernel, static at the
 // launch site) records the devices already served as a bit mask, so a process that drives several GPUs sets it on each
 // of them, and concurrent host threads at worst set it twice.  Devices >= 64 set it on every launch.

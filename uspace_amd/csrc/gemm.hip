@@ -29,24 +29,12 @@ using namespace usgemm;
 
 // Lab hooks.  What is left of the measurement switches of rounds 1-5 (the ablations, the flat LDS-DMA form, MFMA orders, K-loop stamps, full-line
 // stores, same-panel staging ... are patches under tools/lab/dropped/ now: `gemm_lab_switches_r05.patch`, `gemm_ktrace_fulllines_r04.patch`) exists
-// only under -DUSPACE_LAB=1, which `tools/lab/build_variant.sh` / `tools/lab/gemm4/build.sh` pass and `csrc/Makefile` never does (it builds with
-// -DUSPACE_LAB=0 -Werror=undef): a product build that names one of them stops here.
+// only under -DUSPACE_LAB=1, which `tools/lab/build_variant.sh` passes and `csrc/Makefile` never does (it builds with -DUSPACE_LAB=0
+// -Werror=undef).  The four-wave form (round 5) and the chain form (round 4), measured and not landed (profiles/README.md), were retired
+// after commit 4e4c030.
 //   USPACE_LAB    1: `uspace_lab_gemm_force_tile` overrides the planner's tile form (tools/lab/gemm_ab ... tileA tileB)
-//   USPACE_FORM4  1: 256x256 launches may take the four-wave form of tools/lab/gemm4/ (round 5; lab builds link gemm4.o)
-//   USPACE_CHAIN  1: multi-round store-only launches of 256x256 tiles take the chain form (tools/lab/gemm_chain.h, round 4)
 #ifndef USPACE_LAB
 #define USPACE_LAB 0
-#endif
-#if !USPACE_LAB
-#if defined(USPACE_CHAIN) || defined(USPACE_CHAIN_ABL) || defined(USPACE_CHAIN_DMA8) || defined(USPACE_CHAIN_SPLIT) || defined(USPACE_CHAIN_BODY) || defined(USPACE_FORM4)
-#error "lab hooks need -DUSPACE_LAB=1 (tools/lab/build_variant.sh); the product build takes none"
-#endif
-#endif
-#ifndef USPACE_FORM4
-#define USPACE_FORM4 0
-#endif
-#ifndef USPACE_CHAIN
-#define USPACE_CHAIN 0
 #endif
 // bytes of one K part's accumulators of one shared tile (SK): 1 KiB per wave and 16 x 16 sub-tile, strip sub-tiles included
 constexpr size_t sk_slab_bytes(int BM, int BN, bool xtra) { return (size_t)((BM / 16) * (BN / 16) + (xtra ? BN / 16 : 0)) * 1024; }
@@ -1003,22 +991,38 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
     }
 }
 
-template <int BM, int BN, int WM, int WN, int FLAGS, int NST = 2>
-int launch(const GemmArgs& a, hipStream_t s, int wg_per_round) {
+// ---- host side: the tile forms, the planner that picks one per launch, and the launches.
+enum TileChoice { TILE_BIG = 0, TILE_MID = 1, TILE_SMALL = 2, TILE_SPLIT = 3, TILE_TALL = 4, TILE_TINY = 5, TILE_SK = 6 };
+// 64x64 workgroups per round of the chip: two stages / the four-stage ring (two workgroups per CU)
+constexpr int TINY_SLOTS = 1024, TINY_RING_SLOTS = 512;
+// What each form launches: BM x BN tiles of WM x WN waves, workgroups per round of the chip (the cost model's unit)
+struct TileShape { int BM, BN, WM, WN, per_round; };
+constexpr TileShape SHAPES[] = {
+    {256, 256, 2, 4, 256},          // TILE_BIG
+    {192, 256, 2, 4, 256},          // TILE_MID
+    {128, 128, 2, 2, 512},          // TILE_SMALL (two workgroups per CU)
+    {256, 256, 2, 4, 256},          // TILE_SPLIT: its 256x256 part; the rest of the rows as TILE_SMALL
+    {256, 128, 4, 2, 256},          // TILE_TALL
+    {64, 64, 2, 2, TINY_SLOTS},     // TILE_TINY (ring form: TINY_RING_SLOTS)
+    {256, 256, 2, 4, 256},          // TILE_SK (launch_sk)
+};
+
+template <TileChoice F, int FLAGS, int NST = 2>
+int launch(const GemmArgs& a, hipStream_t s, const Plan& p) {
+    constexpr TileShape t = SHAPES[F];
     GemmArgs g = a;
     if constexpr (NST > 2) {       // ring form over the whole K range: one K range per tile, outputs where the caller wants them
         g.nk_split = g.K / BK;
         g.split_stride = 0;
     }
-    g.tiles_n = us_cdiv(g.N, BN);
-    const Plan p = plan_rows(g.M, BM, g.tiles_n, wg_per_round);
+    g.tiles_n = us_cdiv(g.N, t.BN);
     g.tiles_m = p.tiles_m;
     g.m_main = p.m_main;
     g.n_strip = p.n_strip;
     const int rec = us_rec_begin(US_REC_GEMM, FLAGS, g.M, g.N, g.K, s);
-    const dim3 grid(g.tiles_m * g.tiles_n), block(64 * WM * WN);
-    if (p.n_strip > 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, FLAGS, true, NST>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, FLAGS, false, NST>), grid, block, 0, s, g);
+    const dim3 grid(g.tiles_m * g.tiles_n), block(64 * t.WM * t.WN);
+    if (p.n_strip > 0) hipLaunchKernelGGL((gemm_kernel<t.BM, t.BN, t.WM, t.WN, FLAGS, true, NST>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_kernel<t.BM, t.BN, t.WM, t.WN, FLAGS, false, NST>), grid, block, 0, s, g);
     us_rec_end(rec, s);
     US_CHECK_LAUNCH();
     return USPACE_OK;
@@ -1045,9 +1049,10 @@ constexpr int SK_MIN_NK = 64;           // K tiles of the whole K loop at the le
 constexpr int SK_MIN_KT = 16;           // ... and per part
 #endif
 constexpr double SK_FIXED = 0.10;       // the exchange, in units of a round of 256x256 tiles of such a K loop (14 of 141 us)
-std::atomic<int> g_sk_on{1};            // process-wide switch (include/uspace_hip.h: uspace_gemm_set_sk)
+// Process-wide switch (include/uspace_hip.h: uspace_gemm_set_sk).  Read only by the extern "C" entry points, once per call, and passed
+// down from there: the slot counts a forward hands its consumers and the forms its producers launch come from one reading.
+std::atomic<int> g_sk_on{1};
 inline bool sk_plan(int M, int N, int K, SkPlan* out) {
-    if (!g_sk_on.load(std::memory_order_relaxed)) return false;
     if (M < 256 || N < 256 || (N & 255) || K % BK || K / BK < SK_MIN_NK) return false;     // whole 256-column tiles (wide stores, interior epilogue)
     const int tn = N / 256, tm = M / 256, rem = M - tm * 256, nk = K / BK;
     SkPlan p;
@@ -1111,10 +1116,6 @@ constexpr bool sk_flags(int f) {
     return f == (C_ | B_ | R_ | F_) || f == (B_ | R_ | F_ | H_) || f == (B_ | R_ | F_) || f == (C_ | B_ | R_ | F_ | H_) || f == (C_ | B_ | F_) ||
            f == (K_ | C_ | B_ | F_);
 }
-
-#if USPACE_CHAIN
-#include "../../tools/lab/gemm_chain.h"   // lab only (round 4, measured and not landed: profiles/r04_gemm_chain.md)
-#endif
 
 // ---- small launches: 128x128 tiles that fill a fraction of the CUs, with a long K (fc2 / skip_linear of a small batch:
 // 36 tiles x 32 K tiles for U-ViT-S at 4 x 257 rows).  A lone 128x128 workgroup spends 0.39 us per K tile (its CU's LDS-DMA
@@ -1225,25 +1226,10 @@ inline GemmArgs row_slice(const GemmArgs& a, int m_lo, int m_hi) {
     if (a.part_in) g.part_in = a.part_in + (size_t)m_lo * a.np_in * 2;
     if (a.c_out) g.c_out = a.c_out + m_lo;
     // part_out rows are indexed with the launch's own tiles_n: a split launch would mix two strides, so producers
-    // are never split (choose_tile is asked for a non-split form, see dispatch_tile)
+    // are never split (producer_tile)
     return g;
 }
 
-#if USPACE_FORM4
-// Lab builds only (tools/lab/gemm4/: the four-wave form with the assembly K loop, measured in round 5 and not landed -- profiles/r05_gemm4.md).
-// 256 x 256 launches: 0 = the four-wave form wherever us_gemm4_ok() admits it, 1 = the 8-wave template only, 2 = the four-wave form for
-// EVERY launch it admits, whatever tile form the planner would pick (tests of small shapes)
-std::atomic<int> g_big_form{1};
-#endif
-template <int FLAGS>
-int launch_big(const GemmArgs& a, hipStream_t s) {
-#if USPACE_FORM4
-    if (g_big_form.load(std::memory_order_relaxed) == 0 && us_gemm4_ok(a, FLAGS, false)) return us_gemm4_launch(a, FLAGS, s, false);
-#endif
-    return launch<256, 256, 2, 4, FLAGS>(a, s, 256);
-}
-
-enum TileChoice { TILE_BIG = 0, TILE_MID = 1, TILE_SMALL = 2, TILE_SPLIT = 3, TILE_TALL = 4, TILE_TINY = 5, TILE_SK = 6 };
 struct TileCosts { double c[5]; };      // the cost model's figure for each of the first five forms (1e30: not applicable)
 
 // Four tile configurations, chosen by a round-count cost model (unit: one round of 256x256 tiles):
@@ -1256,10 +1242,10 @@ struct TileCosts { double c[5]; };      // the cost model's figure for each of t
 // are independent, so it is two launches).  Extra-strip plans (plan_rows) cost one more 16-row MFMA tile per workgroup.
 // Examples: U-ViT-L B=64 (M=16448): every shape -> 256x256 in exactly 3 / 1 / 4 / 1 / 1 rounds;
 // U-ViT-S T2I B=64 (M=21376, N=512): 128x128 needs 668 tiles = 1.3 rounds of 512 -> 192x256: 224 tiles, one round.
-TileChoice choose_tile(int M, int N, int* split_rows, TileCosts* costs = nullptr) {
+TileChoice choose_tile(int M, int N, int* split_rows, TileCosts* costs) {
     struct { int M, N; } a{M, N};
     *split_rows = 0;
-    if (costs) for (double& c : costs->c) c = 1e30;
+    for (double& c : costs->c) c = 1e30;
     if (a.N <= 128 || a.M < 192) return TILE_SMALL;   // no half-empty 256-wide tiles
     const int tn = us_cdiv(a.N, 256);
     const long big_tiles = (long)(a.M / 256) * tn;
@@ -1289,7 +1275,7 @@ TileChoice choose_tile(int M, int N, int* split_rows, TileCosts* costs = nullptr
     }
     // the 256x256 form is the measured one on the headline shapes: the others must beat it by a clear margin
     const double best = std::min(std::min(std::min(cost_big * 0.93, cost_mid), std::min(cost_small, cost_split)), cost_tall);
-    if (costs) *costs = TileCosts{{cost_big * 0.93, cost_mid, cost_small, cost_split, cost_tall}};
+    *costs = TileCosts{{cost_big * 0.93, cost_mid, cost_small, cost_split, cost_tall}};
     if (best == cost_big * 0.93) return TILE_BIG;
     if (best == cost_tall) return TILE_TALL;
     if (best == cost_split) {
@@ -1305,13 +1291,12 @@ TileChoice choose_tile(int M, int N, int* split_rows, TileCosts* costs = nullptr
 // tile from 0.44 to 0.18 us and replaces the K-split + finish pair for long K.  U-ViT-S at 4 x 257 rows (rocprofv3 kernel traces,
 // `profiles/r03_gemm_ablation.md` sections 7 and 11): proj 12.4 -> 7.1 us, qkv 9.7 -> 7.0, fc1 10.8 -> 9.8, skip_linear 15.8 -> 8.8,
 // fc2 15.8 -> 12.4.  Producers of LayerNorm partial sums take it only while N / 64 <= 8.
-constexpr int TINY_SLOTS = 1024, TINY_RING_SLOTS = 512;     // workgroups of the 64x64 form per round of the chip: two stages / ring
 // which K loop a 64x64 launch takes: the ring for K loops of 16 tiles or more and for shorter ones of few tiles
 inline bool tiny_ring(int M, int N, int K) {
     return K / BK >= 16 || (K / BK >= RING_NST && (long)us_cdiv(M, 64) * us_cdiv(N, 64) <= 448);
 }
-inline TileChoice refine_small(TileChoice tc, int M, int N, int K, bool producer) {
-    (void)K;   // the choice of the 64x64 form does not depend on K (K picks its K loop: tiny_ring); kept in the signature for callers that pass it
+// (the choice of the 64x64 form does not depend on K: K picks its K loop, tiny_ring)
+inline TileChoice refine_small(TileChoice tc, int M, int N, bool producer) {
     if (tc != TILE_SMALL) return tc;
     if ((long)us_cdiv(M, 128) * us_cdiv(N, 128) > 160) return tc;
     if (producer && us_cdiv(N, 64) > 8) return tc;
@@ -1329,81 +1314,105 @@ inline TileChoice producer_tile(TileChoice tc, int N) {
 
 #if USPACE_LAB
 std::atomic<int> g_force_tile{-1};        // lab builds: >= 0 overrides the planner's tile form (tools/lab/gemm_ab ... force)
+inline int forced_tile() { return g_force_tile.load(std::memory_order_relaxed); }
+#else
+constexpr int forced_tile() { return -1; }
 #endif
 
-// Does the K-split tail beat the form chosen so far?  (Launches of fewer than 32 tiles are the small-launch regime: 64x64 tiles / ring.)
-inline bool sk_wins(int M, int N, int K, TileChoice tc, const TileCosts& cs, SkPlan* p) {
-    if (tc == TILE_TINY || tc == TILE_SK) return false;
-    if (!sk_plan(M, N, K, p) || p->n_dp + p->n_sk < 32) return false;
-#if USPACE_LAB
-    if (const int f = g_force_tile.load(std::memory_order_relaxed); f >= 0) return f == (int)TILE_SK;
-#endif
-    return sk_cost(*p) * 0.93 < cs.c[(int)tc] - 1e-9;
+// One launch's plan: its tile form and everything dispatch_tile launches for it.  dispatch_tile executes it and every planning query
+// (uspace_gemm_plan ... _tile_choice) formats it, so the slot counts and workspace sizes handed out are those of the launches.
+struct GemmPlan {
+    TileChoice form;
+    TileShape shape;      // SHAPES[form]; the 64x64 ring form: TINY_RING_SLOTS per round
+    int nst;              // LDS stages: 2, or RING_NST for the 64x64 ring form
+    Plan rows;            // row plan (TILE_SPLIT: of its 256x256 part)
+    int tiles_n;
+    int split_rows;       // TILE_SPLIT: rows [0, split_rows) take 256x256 tiles, the others 128x128 ...
+    Plan rest;            // ... with this row plan
+    int split_k;          // TILE_SMALL: K parts of the two-kernel K-split form (1: none); taken where the caller gives it workspace
+    SkPlan sk;            // TILE_SK
+};
+
+// shape, row plan and K split of p.form (p.split_rows: the split form's, p.sk: the tail's)
+inline GemmPlan& shape_plan(GemmPlan& p, int M, int N, int K) {
+    p.shape = SHAPES[p.form];
+    p.nst = 2;
+    if (p.form == TILE_TINY && tiny_ring(M, N, K)) {
+        p.nst = RING_NST;
+        p.shape.per_round = TINY_RING_SLOTS;
+    }
+    if (p.form != TILE_SPLIT) p.split_rows = 0;
+    if (p.form == TILE_SK) {
+        p.rows = p.sk.rows;
+        p.tiles_n = p.sk.tiles_n;
+    } else {
+        p.tiles_n = us_cdiv(N, p.shape.BN);
+        p.rows = plan_rows(p.form == TILE_SPLIT ? p.split_rows : M, p.shape.BM, p.tiles_n, p.shape.per_round);
+    }
+    const TileShape& sm = SHAPES[TILE_SMALL];
+    if (p.form == TILE_SPLIT) p.rest = plan_rows(M - p.split_rows, sm.BM, us_cdiv(N, sm.BN), sm.per_round);
+    p.split_k = (p.form == TILE_SMALL && K % BK == 0) ? split_factor(us_cdiv(M, sm.BM) * us_cdiv(N, sm.BN), K) : 1;
+    return p;
 }
-// The tile form of a launch: choose_tile, then producer_tile for producers of LayerNorm partial sums, refine_small, and the K-split
-// tail where the epilogue has it (sk_ok) and it wins.  A pure function of its arguments: uspace_gemm_part_slots_k / _plan_k answer with it.
-inline TileChoice final_tile(int M, int N, int K, bool producer, bool sk_ok, int* m1, SkPlan* skp) {
+
+// The plan of a launch, in stages: choose_tile (the base choice: all that uspace_gemm_plan / _tile_choice / _split_ws_bytes report,
+// base_only), then producer_tile for producers of LayerNorm partial sums, refine_small, the lab override, and the K-split tail where it
+// is allowed (the switch as the caller read it, an epilogue that has the tail) and wins.  A pure function of its arguments.
+inline GemmPlan plan_gemm(int M, int N, int K, bool producer, bool sk_allowed, bool base_only = false) {
+    GemmPlan p{};
     TileCosts cs;
-    TileChoice tc = choose_tile(M, N, m1, &cs);
-    if (producer) tc = producer_tile(tc, N);
-    tc = refine_small(tc, M, N, K, producer);
-    if (sk_ok && sk_wins(M, N, K, tc, cs, skp)) return TILE_SK;
-    return tc;
+    p.form = choose_tile(M, N, &p.split_rows, &cs);
+    if (!base_only) {
+        if (producer) p.form = producer_tile(p.form, N);
+        p.form = refine_small(p.form, M, N, producer);
+        const int force = forced_tile();
+        if (force >= 0 && force != TILE_SPLIT && force != TILE_SK) p.form = (TileChoice)force;
+        // (launches of fewer than 32 tiles are the small-launch regime: 64x64 tiles / ring)
+        if (sk_allowed && p.form != TILE_TINY && sk_plan(M, N, K, &p.sk) && p.sk.n_dp + p.sk.n_sk >= 32 &&
+            (force >= 0 ? force == TILE_SK : sk_cost(p.sk) * 0.93 < cs.c[p.form] - 1e-9))
+            p.form = TILE_SK;
+    }
+    return shape_plan(p, M, N, K);
 }
 
 template <int FLAGS>
-int dispatch_tile(const GemmArgs& a, hipStream_t s) {
-#if USPACE_FORM4
-    if (g_big_form.load(std::memory_order_relaxed) == 2 && us_gemm4_ok(a, FLAGS, true)) return us_gemm4_launch(a, FLAGS, s, true);
-#endif
-    int m1 = 0;
+int dispatch_tile(const GemmArgs& a, hipStream_t s, bool sk_on) {
     constexpr bool PRODUCER = (FLAGS & USPACE_EPI_CEN_OUT) != 0;
-    SkPlan skp;
-    TileChoice tc = final_tile(a.M, a.N, a.K, PRODUCER, sk_flags(FLAGS) && a.n_slab <= 2, &m1, &skp);
-#if USPACE_LAB
-    if (const int f = g_force_tile.load(std::memory_order_relaxed); f >= 0 && f != (int)TILE_SPLIT && f != (int)TILE_SK) tc = (TileChoice)f;
-#endif
-    if constexpr (sk_flags(FLAGS)) {
-        if (tc == TILE_SK) {
-            if (a.sk_ws && a.sk_cnt && sk_ws_need(skp) <= a.sk_ws_bytes && sk_device_ok()) return launch_sk<FLAGS>(a, s, skp);
-            // no workspace: a producer takes the 256x256 form without the tail -- the partial-sum stride its consumers were told
-            // about (uspace_gemm_part_slots_k) --, any other launch the form it would have had
-            tc = PRODUCER ? TILE_BIG : final_tile(a.M, a.N, a.K, false, false, &m1, &skp);
+    // (never the tail for n_slab > 2: the 9-slab convolutions of vae.hip)
+    GemmPlan p = plan_gemm(a.M, a.N, a.K, PRODUCER, sk_on && sk_flags(FLAGS) && a.n_slab <= 2);
+    // The run-time fallbacks.  The tail needs its workspace and a device that holds every shared-tile workgroup at once; without them a
+    // producer takes the 256x256 form -- the partial-sum stride its consumers were told about (uspace_gemm_part_slots_k) --, any other
+    // launch the form it would have had without the tail.
+    if (p.form == TILE_SK) {
+        if constexpr (sk_flags(FLAGS)) {
+            if (a.sk_ws && a.sk_cnt && sk_ws_need(p.sk) <= a.sk_ws_bytes && sk_device_ok()) return launch_sk<FLAGS>(a, s, p.sk);
+        }
+        if (PRODUCER) {
+            p.form = TILE_BIG;
+            shape_plan(p, a.M, a.N, a.K);
+        } else {
+            p = plan_gemm(a.M, a.N, a.K, false, false);
         }
     }
-    if (tc == TILE_SK) return USPACE_ERR_ARG;   // (unreachable: final_tile answers SK only for epilogues that have it)
+    // The K-split form of small launches, where the caller gives it workspace enough
     if constexpr ((FLAGS & (USPACE_EPI_LN_IN | USPACE_EPI_GELU)) == 0) {
-        if (tc == TILE_SMALL && a.split_ws) {
-            const int S = split_factor(us_cdiv(a.M, 128) * us_cdiv(a.N, 128), a.K);
-            if (S > 1 && (size_t)S * a.M * a.N * 4 <= a.split_ws_bytes) {
-                const int rec = us_rec_begin(US_REC_GEMM, FLAGS, a.M, a.N, a.K, s);
-                const int rc = launch_split(a, s, S);
-                if (rc != USPACE_OK) return rc;
-                hipLaunchKernelGGL(splitk_finish_kernel, dim3(a.M), dim3(256), 0, s, a.split_ws, S, (long)a.M * a.N, a, FLAGS, us_cdiv(a.N, 128));
-                us_rec_end(rec, s);
-                US_CHECK_LAUNCH();
-                return USPACE_OK;
-            }
+        if (p.form == TILE_SMALL && p.split_k > 1 && a.split_ws && (size_t)p.split_k * a.M * a.N * 4 <= a.split_ws_bytes) {
+            const int rec = us_rec_begin(US_REC_GEMM, FLAGS, a.M, a.N, a.K, s);
+            US_TRY(launch_split(a, s, p.split_k));
+            hipLaunchKernelGGL(splitk_finish_kernel, dim3(a.M), dim3(256), 0, s, a.split_ws, p.split_k, (long)a.M * a.N, a, FLAGS, us_cdiv(a.N, 128));
+            us_rec_end(rec, s);
+            US_CHECK_LAUNCH();
+            return USPACE_OK;
         }
     }
-#if USPACE_CHAIN
-    if constexpr ((FLAGS & (USPACE_EPI_RESIDUAL | USPACE_EPI_OUT_F32 | USPACE_EPI_CEN_OUT)) == 0) {
-        if (tc == TILE_BIG) {
-            const int tn = us_cdiv(a.N, 256);
-            const Plan p = plan_rows(a.M, 256, tn, 256);
-            if (chain_ok(a, p, tn, FLAGS)) return launch_chain<FLAGS>(a, p, tn, s);
-        }
-    }
-#endif
-    switch (tc) {
-        case TILE_BIG: return launch_big<FLAGS>(a, s);
-        case TILE_MID: return launch<192, 256, 2, 4, FLAGS>(a, s, 256);
-        case TILE_TALL: return launch<256, 128, 4, 2, FLAGS>(a, s, 256);
-        case TILE_SPLIT: {
-            int rc = launch_big<FLAGS>(row_slice(a, 0, m1), s);
-            if (rc != USPACE_OK) return rc;
-            return launch<128, 128, 2, 2, FLAGS>(row_slice(a, m1, a.M), s, 512);
-        }
+    switch (p.form) {
+        case TILE_BIG: return launch<TILE_BIG, FLAGS>(a, s, p.rows);
+        case TILE_MID: return launch<TILE_MID, FLAGS>(a, s, p.rows);
+        case TILE_TALL: return launch<TILE_TALL, FLAGS>(a, s, p.rows);
+        case TILE_SMALL: return launch<TILE_SMALL, FLAGS>(a, s, p.rows);
+        case TILE_SPLIT:
+            US_TRY((launch<TILE_BIG, FLAGS>(row_slice(a, 0, p.split_rows), s, p.rows)));
+            return launch<TILE_SMALL, FLAGS>(row_slice(a, p.split_rows, a.M), s, p.rest);
         case TILE_TINY:
             // a 64 x 64 workgroup is latency-bound with one K tile of prefetch (0.44 us per K tile); with four stages filled up
             // front and refilled behind every barrier, and its fragments fetched a whole tile ahead (KTILE_T), it runs at 0.14-0.19
@@ -1411,33 +1420,53 @@ int dispatch_tile(const GemmArgs& a, hipStream_t s) {
             // (not for short K loops that already put two workgroups on every CU: fc1 of U-ViT-S, 512 tiles x 8 K tiles, 9.8 -> 11.2 us)
             // (the ring form holds 66-74 KiB of LDS: two workgroups per CU, 512 per round -- the row plan must know, or a remainder of
             // a few rows becomes a second round instead of a strip: fc1 of U-ViT-L at 2 x 257 rows, 576 workgroups, 15.9 -> 11.2 us)
-            if (tiny_ring(a.M, a.N, a.K)) return launch<64, 64, 2, 2, FLAGS, RING_NST>(a, s, TINY_RING_SLOTS);
-            return launch<64, 64, 2, 2, FLAGS>(a, s, TINY_SLOTS);
-        default: return launch<128, 128, 2, 2, FLAGS>(a, s, 512);
+            if (p.nst == RING_NST) return launch<TILE_TINY, FLAGS, RING_NST>(a, s, p.rows);
+            return launch<TILE_TINY, FLAGS>(a, s, p.rows);
+        default: return USPACE_ERR_ARG;   // (TILE_SK: only epilogues that have the tail plan it)
     }
 }
 
-int dispatch_flags(const GemmArgs& g, int epi_flags, hipStream_t s) {
+int dispatch_flags(const GemmArgs& g, int epi_flags, hipStream_t s, bool sk_on) {
     constexpr int B_ = USPACE_EPI_BIAS, G_ = USPACE_EPI_GELU, R_ = USPACE_EPI_RESIDUAL,
                   F_ = USPACE_EPI_OUT_F32, H_ = USPACE_EPI_OUT_BF16, C_ = USPACE_EPI_CEN_OUT, L_ = USPACE_EPI_LN_IN, K_ = USPACE_EPI_RANK1;
     switch (epi_flags) {
-        case H_:                return dispatch_tile<H_>(g, s);                 // qkv
-        case B_ | H_:           return dispatch_tile<B_ | H_>(g, s);
-        case B_ | G_ | H_:      return dispatch_tile<B_ | G_ | H_>(g, s);       // fc1 + GELU
-        case B_ | R_ | F_:      return dispatch_tile<B_ | R_ | F_>(g, s);       // proj / fc2 (+= residual)
-        case B_ | R_ | F_ | H_: return dispatch_tile<B_ | R_ | F_ | H_>(g, s);  // ... + bf16 copy (skip stack)
-        case B_ | F_:           return dispatch_tile<B_ | F_>(g, s);            // context_embed
-        case B_ | F_ | H_:      return dispatch_tile<B_ | F_ | H_>(g, s);       // skip_linear
-        case F_:                return dispatch_tile<F_>(g, s);
+        case H_:                return dispatch_tile<H_>(g, s, sk_on);                 // qkv
+        case B_ | H_:           return dispatch_tile<B_ | H_>(g, s, sk_on);
+        case B_ | G_ | H_:      return dispatch_tile<B_ | G_ | H_>(g, s, sk_on);       // fc1 + GELU
+        case B_ | R_ | F_:      return dispatch_tile<B_ | R_ | F_>(g, s, sk_on);       // proj / fc2 (+= residual)
+        case B_ | R_ | F_ | H_: return dispatch_tile<B_ | R_ | F_ | H_>(g, s, sk_on);  // ... + bf16 copy (skip stack)
+        case B_ | F_:           return dispatch_tile<B_ | F_>(g, s, sk_on);            // context_embed
+        case B_ | F_ | H_:      return dispatch_tile<B_ | F_ | H_>(g, s, sk_on);       // skip_linear
+        case F_:                return dispatch_tile<F_>(g, s, sk_on);
         // LayerNorm folded through the GEMMs (consumers LN_IN, producers CEN_OUT)
-        case L_ | B_ | H_:           return dispatch_tile<L_ | B_ | H_>(g, s);            // norm1 -> qkv
-        case L_ | B_ | G_ | H_:      return dispatch_tile<L_ | B_ | G_ | H_>(g, s);       // norm2 -> fc1 + GELU
-        case C_ | B_ | R_ | F_:      return dispatch_tile<C_ | B_ | R_ | F_>(g, s);       // proj / fc2 feeding a norm
-        case C_ | B_ | R_ | F_ | H_: return dispatch_tile<C_ | B_ | R_ | F_ | H_>(g, s);  // ... + raw bf16 copy (skip stack)
-        case C_ | B_ | F_:           return dispatch_tile<C_ | B_ | F_>(g, s);            // skip_linear feeding norm1
-        case K_ | C_ | B_ | F_:      return dispatch_tile<K_ | C_ | B_ | F_>(g, s);       // ... whose skip slab was stored centred
+        case L_ | B_ | H_:           return dispatch_tile<L_ | B_ | H_>(g, s, sk_on);            // norm1 -> qkv
+        case L_ | B_ | G_ | H_:      return dispatch_tile<L_ | B_ | G_ | H_>(g, s, sk_on);       // norm2 -> fc1 + GELU
+        case C_ | B_ | R_ | F_:      return dispatch_tile<C_ | B_ | R_ | F_>(g, s, sk_on);       // proj / fc2 feeding a norm
+        case C_ | B_ | R_ | F_ | H_: return dispatch_tile<C_ | B_ | R_ | F_ | H_>(g, s, sk_on);  // ... + raw bf16 copy (skip stack)
+        case C_ | B_ | F_:           return dispatch_tile<C_ | B_ | F_>(g, s, sk_on);            // skip_linear feeding norm1
+        case K_ | C_ | B_ | F_:      return dispatch_tile<K_ | C_ | B_ | F_>(g, s, sk_on);       // ... whose skip slab was stored centred
         default:                return USPACE_ERR_ARG;
     }
+}
+
+// What uspace_gemm_bf16_ext and uspace_gemm_slabs_bf16 share: the operands (K = n_slab slabs of K1, 32-bit byte offsets) and the outputs
+// of the plain epilogue.  g comes back as one K slab with no LayerNorm folding and no workspaces: every other field is zero.
+int plain_args(GemmArgs& g, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K, int K1, int epi_flags,
+               const float* bias, const float* resid_in, int ld_resid, float* out_f32, int ld_f32, uint16_t* out_bf16, int ld_bf16) {
+    if (!A || !W || M <= 0 || N <= 0 || K1 <= 0 || K1 > K || K % BK || K1 % BK || (N & 3) || (lda & 7) || (ldw & 7)) return USPACE_ERR_ARG;
+    if ((long)M * lda >= (1L << 30) || (long)N * ldw >= (1L << 30)) return USPACE_ERR_ARG;   // 32-bit byte offsets
+    if ((epi_flags & USPACE_EPI_BIAS) && !bias) return USPACE_ERR_ARG;
+    if ((epi_flags & USPACE_EPI_RESIDUAL) && (!resid_in || (ld_resid & 3))) return USPACE_ERR_ARG;
+    if ((epi_flags & USPACE_EPI_OUT_F32) && (!out_f32 || (ld_f32 & 3))) return USPACE_ERR_ARG;
+    if ((epi_flags & USPACE_EPI_OUT_BF16) && (!out_bf16 || (ld_bf16 & 3))) return USPACE_ERR_ARG;
+    if (!(epi_flags & (USPACE_EPI_OUT_F32 | USPACE_EPI_OUT_BF16))) return USPACE_ERR_ARG;
+    g = GemmArgs{};
+    g.A = A; g.W = W; g.bias = bias; g.resid = resid_in; g.out_f32 = out_f32; g.out_bf16 = out_bf16;
+    g.M = M; g.N = N; g.K = K; g.K1 = K1;
+    g.lda = lda; g.lda2 = lda; g.ldw = ldw; g.ld_resid = ld_resid; g.ld_f32 = ld_f32; g.ld_bf16 = ld_bf16;
+    g.m_main = M;
+    g.n_slab = 1;
+    return USPACE_OK;
 }
 
 // 16-byte stores of the bf16 outputs need 16-byte aligned rows
@@ -1448,28 +1477,6 @@ int wide_ok(const GemmArgs& g, int epi_flags) {
 }
 
 }  // namespace
-
-#if USPACE_FORM4
-extern "C" __attribute__((visibility("default"))) int uspace_lab_gemm_set_big_form(int form) {
-    if (form < 0 || form > 2) return USPACE_ERR_ARG;
-    return g_big_form.exchange(form, std::memory_order_relaxed);
-}
-
-extern "C" __attribute__((visibility("default"))) int uspace_lab_gemm_takes_form4(int M, int N, int K, int K1, int epi_flags) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const int form = g_big_form.load(std::memory_order_relaxed);
-    if (form == 1) return 0;
-    int m1 = 0;
-    const TileChoice tc = refine_small((epi_flags & USPACE_EPI_CEN_OUT) ? producer_tile(choose_tile(M, N, &m1), N) : choose_tile(M, N, &m1), M, N, K,
-                                       (epi_flags & USPACE_EPI_CEN_OUT) != 0);
-    if (tc != TILE_BIG && form != 2) return 0;
-    GemmArgs g{};
-    g.M = M; g.N = N; g.K = K; g.K1 = (K1 > 0 && K1 < K) ? K1 : K;
-    g.n_slab = g.K1 < K ? 2 : 1;
-    g.wide = 1;
-    return us_gemm4_ok(g, epi_flags, form == 2) ? 1 : 0;
-}
-#endif
 
 #if USPACE_LAB
 extern "C" __attribute__((visibility("default"))) void uspace_lab_gemm_force_tile(int tc) { g_force_tile.store(tc, std::memory_order_relaxed); }
@@ -1482,129 +1489,76 @@ extern "C" int uspace_gemm_set_sk(int mode) {
 }
 extern "C" int uspace_gemm_get_sk(void) { return g_sk_on.load(std::memory_order_relaxed); }
 
-extern "C" int uspace_gemm_part_slots_k(int M, int N, int K) {
+int us_gemm_part_slots_k(int M, int N, int K, bool sk_on) {
     if (M <= 0 || N <= 0 || K <= 0) return USPACE_ERR_ARG;
-#if USPACE_LAB
-    if (const int f = g_force_tile.load(std::memory_order_relaxed); f >= 0)
-        return us_cdiv(N, f == (int)TILE_TINY ? 64 : (f == (int)TILE_SMALL || f == (int)TILE_TALL) ? 128 : 256);
-#endif
-#if USPACE_FORM4
-    // (forced four-wave form: 256-wide tiles wherever a producer launch of these sizes can take it)
-    if (g_big_form.load(std::memory_order_relaxed) == 2 && uspace_lab_gemm_takes_form4(M, N, K, K, USPACE_EPI_CEN_OUT | USPACE_EPI_BIAS | USPACE_EPI_OUT_F32)) return N / 256;
-#endif
-    int m1 = 0;
-    SkPlan skp;
-    const TileChoice tc = final_tile(M, N, K, true, true, &m1, &skp);
-    return us_cdiv(N, tc == TILE_TINY ? 64 : (tc == TILE_SMALL || tc == TILE_TALL) ? 128 : 256);
+    return plan_gemm(M, N, K, true, sk_on).tiles_n;
 }
+extern "C" int uspace_gemm_part_slots_k(int M, int N, int K) { return us_gemm_part_slots_k(M, N, K, g_sk_on.load(std::memory_order_relaxed) != 0); }
 
 // the largest slot count any producer of [M, N] rows writes (short K loops may take the 64-wide form)
-extern "C" int uspace_gemm_part_slots(int M, int N) { return uspace_gemm_part_slots_k(M, N, 64); }
+extern "C" int uspace_gemm_part_slots(int M, int N) { return uspace_gemm_part_slots_k(M, N, BK); }
 
 extern "C" size_t uspace_gemm_split_ws_bytes(int M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % BK) return 0;
-    int m1 = 0;
-    if (choose_tile(M, N, &m1) != TILE_SMALL) return 0;
-    const int S = split_factor(us_cdiv(M, 128) * us_cdiv(N, 128), K);
-    return S > 1 ? (size_t)S * M * N * 4 : 0;
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const GemmPlan p = plan_gemm(M, N, K, false, false, true);
+    return p.split_k > 1 ? (size_t)p.split_k * M * N * 4 : 0;
 }
 
 extern "C" int uspace_gemm_tile_choice(int M, int N, int* split_rows) {
-    int m1 = 0;
     if (M <= 0 || N <= 0) return USPACE_ERR_ARG;
-    const int c = (int)choose_tile(M, N, &m1);
-    if (split_rows) *split_rows = m1;
-    return c;
+    const GemmPlan p = plan_gemm(M, N, BK, false, false, true);
+    if (split_rows) *split_rows = p.split_rows;
+    return (int)p.form;
 }
 
-// out[8] of uspace_gemm_plan / _plan_k for one tile choice: the shape dispatch_tile launches for it, its row plan and round size
-static void plan_for(TileChoice tc, int M, int N, int K, int m1, int* out) {
-    int BM = 256, BN = 256, per_round = 256;
-    switch (tc) {
-        case TILE_MID: BM = 192; break;
-        case TILE_TALL: BN = 128; break;
-        case TILE_SMALL: BM = BN = 128; per_round = 512; break;
-        case TILE_TINY: BM = BN = 64; per_round = tiny_ring(M, N, K) ? TINY_RING_SLOTS : TINY_SLOTS; break;
-        default: break;
-    }
-    const int rows = tc == TILE_SPLIT ? m1 : M;                 // split: the plan of the 256x256 part
-    const int tn = us_cdiv(N, BN);
-    const Plan p = plan_rows(rows, BM, tn, per_round);
-    out[0] = (int)tc; out[1] = tc == TILE_SPLIT ? m1 : 0; out[2] = BM; out[3] = BN; out[4] = p.tiles_m; out[5] = tn; out[6] = p.n_strip; out[7] = per_round;
+// out[8] of uspace_gemm_plan / _plan_k: form, split rows (TILE_SK: K parts per shared tile), BM, BN, tile rows, tiles_n, strips and
+// workgroups per round (TILE_SK: the whole-tile workgroups in front of the shared ones)
+static void format_plan(const GemmPlan& p, int* out) {
+    const bool sk = p.form == TILE_SK;
+    out[0] = (int)p.form; out[1] = sk ? p.sk.S : p.split_rows; out[2] = p.shape.BM; out[3] = p.shape.BN;
+    out[4] = p.rows.tiles_m; out[5] = p.tiles_n; out[6] = p.rows.n_strip; out[7] = sk ? p.sk.n_dp : p.shape.per_round;
 }
 
 extern "C" int uspace_gemm_plan(int M, int N, int* out) {
     if (M <= 0 || N <= 0 || !out) return USPACE_ERR_ARG;
-    int m1 = 0;
-    const TileChoice tc = choose_tile(M, N, &m1);
-    plan_for(tc, M, N, BK, m1, out);
+    format_plan(plan_gemm(M, N, BK, false, false, true), out);
     return USPACE_OK;
 }
 
-// ... for a launch with this K and role (producer of LayerNorm partial sums or not): the chain dispatch_tile applies -- choose_tile,
-// producer_tile for producers (no split form, no 128-wide tiles beyond 8 slots), refine_small (64x64 tiles, out[0] = 5), the K-split
-// tail where it wins -- for a launch whose epilogue may take that tail.  dispatch_tile never gives it to n_slab > 2 (the 9-slab
-// convolutions of vae.hip): their form is this answer with the tail switched off (uspace_gemm_set_sk(0)).
+// ... for a launch with this K and role (producer of LayerNorm partial sums or not), the K-split tail included for a launch whose
+// epilogue may take it.  dispatch_tile never gives it to n_slab > 2 (the 9-slab convolutions of vae.hip): their form is this answer
+// with the tail switched off (uspace_gemm_set_sk(0)).
 extern "C" int uspace_gemm_plan_k(int M, int N, int K, int producer, int* out) {
     if (M <= 0 || N <= 0 || K <= 0 || !out) return USPACE_ERR_ARG;
-    int m1 = 0;
-    SkPlan skp;
-    const TileChoice tc = final_tile(M, N, K, producer != 0, true, &m1, &skp);
-    if (tc == TILE_SK) {     // out[1] = K parts per shared tile, out[7] = whole-tile workgroups in front of them
-        out[0] = (int)tc; out[1] = skp.S; out[2] = out[3] = 256; out[4] = skp.rows.tiles_m; out[5] = skp.tiles_n; out[6] = skp.rows.n_strip; out[7] = skp.n_dp;
-        return USPACE_OK;
-    }
-    plan_for(tc, M, N, K, m1, out);
+    format_plan(plan_gemm(M, N, K, producer != 0, g_sk_on.load(std::memory_order_relaxed) != 0), out);
     return USPACE_OK;
 }
 
-/* bytes of uspace_gemm_ext.sk_ws a launch with these sizes needs for the K-split tail (0: the launch has none) */
-extern "C" size_t uspace_gemm_sk_ws_bytes(int M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % BK) return 0;
-    int m1 = 0;
-    SkPlan skp;
-    // (asked without a role: the larger of the two answers)
+// (asked without a role: the larger of the two answers)
+size_t us_gemm_sk_ws_bytes(int M, int N, int K, bool sk_on) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
     size_t need = 0;
-    for (int producer = 0; producer < 2; ++producer)
-        if (final_tile(M, N, K, producer != 0, true, &m1, &skp) == TILE_SK) need = std::max(need, sk_ws_need(skp));
+    for (int producer = 0; producer < 2; ++producer) {
+        const GemmPlan p = plan_gemm(M, N, K, producer != 0, sk_on);
+        if (p.form == TILE_SK) need = std::max(need, sk_ws_need(p.sk));
+    }
     return need;
 }
+/* bytes of uspace_gemm_ext.sk_ws a launch with these sizes needs for the K-split tail (0: the launch has none) */
+extern "C" size_t uspace_gemm_sk_ws_bytes(int M, int N, int K) { return us_gemm_sk_ws_bytes(M, N, K, g_sk_on.load(std::memory_order_relaxed) != 0); }
 
-extern "C" int uspace_gemm_bf16_ext(const uint16_t* A, int lda, const uint16_t* A2, int lda2, int K1,
-                                    const uint16_t* W, int ldw, int M, int N, int K, int epi_flags,
-                                    const float* bias, const float* resid_in, int ld_resid,
-                                    float* out_f32, int ld_f32, uint16_t* out_bf16, int ld_bf16,
-                                    const uspace_gemm_ext* ext, uspace_stream_t stream) {
-    if (!A || !W || M <= 0 || N <= 0 || K <= 0) return USPACE_ERR_ARG;
-    if (K % BK || K1 % BK || K1 <= 0 || K1 > K || (N & 3)) return USPACE_ERR_ARG;
-    if (K1 < K && !A2) return USPACE_ERR_ARG;
-    if ((lda & 7) || (ldw & 7) || (K1 < K && lda2 != lda)) return USPACE_ERR_ARG;
-    if ((long)M * lda >= (1L << 30) || (long)N * ldw >= (1L << 30)) return USPACE_ERR_ARG;   // 32-bit byte offsets
-    if ((epi_flags & USPACE_EPI_BIAS) && !bias) return USPACE_ERR_ARG;
-    if ((epi_flags & USPACE_EPI_RESIDUAL) && (!resid_in || (ld_resid & 3))) return USPACE_ERR_ARG;
-    if ((epi_flags & USPACE_EPI_OUT_F32) && (!out_f32 || (ld_f32 & 3))) return USPACE_ERR_ARG;
-    if ((epi_flags & USPACE_EPI_OUT_BF16) && (!out_bf16 || (ld_bf16 & 3))) return USPACE_ERR_ARG;
-    if (!(epi_flags & (USPACE_EPI_OUT_F32 | USPACE_EPI_OUT_BF16))) return USPACE_ERR_ARG;
+int us_gemm_bf16_ext(const uint16_t* A, int lda, const uint16_t* A2, int lda2, int K1, const uint16_t* W, int ldw, int M, int N, int K,
+                     int epi_flags, const float* bias, const float* resid_in, int ld_resid, float* out_f32, int ld_f32, uint16_t* out_bf16,
+                     int ld_bf16, const uspace_gemm_ext* ext, bool sk_on, uspace_stream_t stream) {
     GemmArgs g;
-    g.A = A; g.A2 = (K1 < K) ? A2 : nullptr; g.W = W; g.bias = bias; g.resid = resid_in;
-    g.out_f32 = out_f32; g.out_bf16 = out_bf16;
-    g.M = M; g.N = N; g.K = K; g.K1 = K1;
-    g.lda = lda; g.lda2 = lda2; g.ldw = ldw; g.ld_resid = ld_resid; g.ld_f32 = ld_f32; g.ld_bf16 = ld_bf16;
-    g.tiles_m = g.tiles_n = 0;
-    g.m_main = M; g.n_strip = 0;
-    g.n_slab = (K1 < K) ? 2 : 1;
-    g.k1_log2 = 0;
-    for (int i = 0; i < 9; ++i) g.slab_shift[i] = 0;
-    if (K1 < K) {
-        if (K != 2 * K1 || (K1 & (K1 - 1))) return USPACE_ERR_ARG;   // two equal power-of-two slabs
+    US_TRY(plain_args(g, A, lda, W, ldw, M, N, K, K1, epi_flags, bias, resid_in, ld_resid, out_f32, ld_f32, out_bf16, ld_bf16));
+    g.lda2 = lda2;
+    if (K1 < K) {   // [A | A2]: two equal power-of-two slabs with one row stride
+        if (!A2 || lda2 != lda || K != 2 * K1 || (K1 & (K1 - 1))) return USPACE_ERR_ARG;
+        g.A2 = A2;
+        g.n_slab = 2;
         while ((1 << g.k1_log2) < K1) ++g.k1_log2;
     }
-    g.row_c = nullptr; g.out_cen = nullptr; g.part_out = nullptr; g.part_in = nullptr; g.colsum = nullptr; g.c_out = nullptr;
-    g.row_add = nullptr; g.col_add = nullptr;
-    g.ld_cen = 0; g.np_in = 0; g.inv_d = 0.f; g.eps = 0.f;
-    g.wide = 0;
-    g.nk_split = 0; g.split_stride = 0; g.split_ws = nullptr; g.split_ws_bytes = 0;
-    g.sk_first = 0; g.sk_S = 0; g.sk_ws = nullptr; g.sk_cnt = nullptr; g.sk_ws_bytes = 0;
     if (ext) {
         g.split_ws = (float*)ext->split_ws; g.split_ws_bytes = ext->split_ws_bytes;
         if (g.split_ws && ((uintptr_t)g.split_ws & 15)) return USPACE_ERR_ARG;
@@ -1629,7 +1583,16 @@ extern "C" int uspace_gemm_bf16_ext(const uint16_t* A, int lda, const uint16_t* 
         if (!g.part_in || g.np_in <= 0 || g.np_in > 8 || !g.colsum || g.inv_d <= 0.f || (g.c_out && !g.row_c)) return USPACE_ERR_ARG;
     }
     g.wide = wide_ok(g, epi_flags);
-    return dispatch_flags(g, epi_flags, (hipStream_t)stream);
+    return dispatch_flags(g, epi_flags, (hipStream_t)stream, sk_on);
+}
+
+extern "C" int uspace_gemm_bf16_ext(const uint16_t* A, int lda, const uint16_t* A2, int lda2, int K1,
+                                    const uint16_t* W, int ldw, int M, int N, int K, int epi_flags,
+                                    const float* bias, const float* resid_in, int ld_resid,
+                                    float* out_f32, int ld_f32, uint16_t* out_bf16, int ld_bf16,
+                                    const uspace_gemm_ext* ext, uspace_stream_t stream) {
+    return us_gemm_bf16_ext(A, lda, A2, lda2, K1, W, ldw, M, N, K, epi_flags, bias, resid_in, ld_resid, out_f32, ld_f32, out_bf16, ld_bf16,
+                            ext, g_sk_on.load(std::memory_order_relaxed) != 0, stream);
 }
 
 extern "C" int uspace_gemm_bf16(const uint16_t* A, int lda, const uint16_t* A2, int lda2, int K1,
@@ -1648,31 +1611,13 @@ extern "C" int uspace_gemm_slabs_bf16(const uint16_t* A, int lda, const uint16_t
                                       int n_slab, const int* row_shift, int epi_flags, const float* bias,
                                       const float* resid_in, int ld_resid, float* out_f32, int ld_f32,
                                       uint16_t* out_bf16, int ld_bf16, uspace_stream_t stream) {
-    if (!A || !W || !row_shift || M <= 0 || N <= 0 || K1 <= 0 || n_slab < 1 || n_slab > 9) return USPACE_ERR_ARG;
-    if (K1 % BK || (K1 & (K1 - 1)) || (N & 3) || (lda & 7) || (ldw & 7)) return USPACE_ERR_ARG;
-    if ((long)M * lda >= (1L << 30) || (long)N * ldw >= (1L << 30)) return USPACE_ERR_ARG;
-    if ((epi_flags & USPACE_EPI_BIAS) && !bias) return USPACE_ERR_ARG;
-    if ((epi_flags & USPACE_EPI_RESIDUAL) && (!resid_in || (ld_resid & 3))) return USPACE_ERR_ARG;
-    if ((epi_flags & USPACE_EPI_OUT_F32) && (!out_f32 || (ld_f32 & 3))) return USPACE_ERR_ARG;
-    if ((epi_flags & USPACE_EPI_OUT_BF16) && (!out_bf16 || (ld_bf16 & 3))) return USPACE_ERR_ARG;
-    if (!(epi_flags & (USPACE_EPI_OUT_F32 | USPACE_EPI_OUT_BF16))) return USPACE_ERR_ARG;
-    GemmArgs g;
-    g.A = A; g.A2 = nullptr; g.W = W; g.bias = bias; g.resid = resid_in;
-    g.out_f32 = out_f32; g.out_bf16 = out_bf16;
-    g.M = M; g.N = N; g.K = K1 * n_slab; g.K1 = K1;
-    g.lda = lda; g.lda2 = lda; g.ldw = ldw; g.ld_resid = ld_resid; g.ld_f32 = ld_f32; g.ld_bf16 = ld_bf16;
-    g.tiles_m = g.tiles_n = 0;
-    g.m_main = M; g.n_strip = 0;
-    g.n_slab = n_slab;
-    g.k1_log2 = 0;
-    while ((1 << g.k1_log2) < K1) ++g.k1_log2;
-    for (int i = 0; i < 9; ++i) g.slab_shift[i] = i < n_slab ? row_shift[i] : 0;
-    g.row_c = nullptr; g.out_cen = nullptr; g.part_out = nullptr; g.part_in = nullptr; g.colsum = nullptr; g.c_out = nullptr;
-    g.row_add = nullptr; g.col_add = nullptr;
-    g.ld_cen = 0; g.np_in = 0; g.inv_d = 0.f; g.eps = 0.f;
+    if (!row_shift || n_slab < 1 || n_slab > 9 || K1 <= 0 || (K1 & (K1 - 1))) return USPACE_ERR_ARG;
     if (epi_flags & (USPACE_EPI_CEN_OUT | USPACE_EPI_LN_IN | USPACE_EPI_RANK1)) return USPACE_ERR_ARG;
-    g.nk_split = 0; g.split_stride = 0; g.split_ws = nullptr; g.split_ws_bytes = 0;
-    g.sk_first = 0; g.sk_S = 0; g.sk_ws = nullptr; g.sk_cnt = nullptr; g.sk_ws_bytes = 0;
+    GemmArgs g;
+    US_TRY(plain_args(g, A, lda, W, ldw, M, N, K1 * n_slab, K1, epi_flags, bias, resid_in, ld_resid, out_f32, ld_f32, out_bf16, ld_bf16));
+    g.n_slab = n_slab;
+    while ((1 << g.k1_log2) < K1) ++g.k1_log2;
+    for (int i = 0; i < n_slab; ++i) g.slab_shift[i] = row_shift[i];
     g.wide = wide_ok(g, epi_flags);
-    return dispatch_flags(g, epi_flags, (hipStream_t)stream);
+    return dispatch_flags(g, epi_flags, (hipStream_t)stream, g_sk_on.load(std::memory_order_relaxed) != 0);
 }

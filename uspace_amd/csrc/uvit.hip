@@ -130,7 +130,8 @@ struct Workspace {
 // memset at the start of the forward (include/uspace_hip.h, uspace_gemm_ext.sk_counters)
 inline int sk_launches(const uspace_uvit_config& c) { return 5 * (c.depth + 1) + c.depth / 2 + 2; }
 
-Workspace plan_workspace(const uspace_uvit_config& c, const Model& m, int B) {
+// sk_on: the K-split tail switch (uspace_gemm_set_sk) as the caller read it
+Workspace plan_workspace(const uspace_uvit_config& c, const Model& m, int B, bool sk_on) {
     Workspace w;
     const size_t M = (size_t)B * m.L, D = c.embed_dim;
     size_t off = 0;
@@ -153,9 +154,9 @@ Workspace plan_workspace(const uspace_uvit_config& c, const Model& m, int B) {
                               uspace_gemm_split_ws_bytes((int)M, (int)D, c.mlp_hidden));
     w.splitk = take(w.splitk_bytes);
     // partial-sum slabs of the in-launch K-split tail (qkv; proj, skip_linear, fc2: N = D) and the launches' arrival counters
-    w.sk_bytes = std::max(std::max(uspace_gemm_sk_ws_bytes((int)M, (int)D, (int)D), uspace_gemm_sk_ws_bytes((int)M, (int)D, 2 * (int)D)),
-                          std::max(uspace_gemm_sk_ws_bytes((int)M, (int)D, c.mlp_hidden), uspace_gemm_sk_ws_bytes((int)M, 3 * (int)D, (int)D)));
-    w.sk_bytes = std::max(w.sk_bytes, uspace_gemm_sk_ws_bytes((int)M, c.mlp_hidden, (int)D));
+    auto sk_ws = [&](size_t n, size_t k) { return us_gemm_sk_ws_bytes((int)M, (int)n, (int)k, sk_on); };
+    w.sk_bytes = std::max(std::max(sk_ws(D, D), sk_ws(D, 2 * D)), std::max(sk_ws(D, c.mlp_hidden), sk_ws(3 * D, D)));
+    w.sk_bytes = std::max(w.sk_bytes, sk_ws(c.mlp_hidden, D));
     w.sk = take(w.sk_bytes);
     w.skcnt_bytes = w.sk_bytes ? (size_t)sk_launches(c) * USPACE_GEMM_SK_COUNTERS * 4 : 0;
     w.skcnt = take(w.skcnt_bytes);
@@ -185,7 +186,7 @@ extern "C" size_t uspace_uvit_weight_bytes(const uspace_uvit_config* cfg) {
 extern "C" size_t uspace_uvit_workspace_bytes(const uspace_uvit_config* cfg, int B) {
     if (!valid_cfg(cfg) || B <= 0) return 0;
     const Model m = build_model(*cfg);
-    return plan_workspace(*cfg, m, B).total;
+    return plan_workspace(*cfg, m, B, uspace_gemm_get_sk() != 0).total;
 }
 
 extern "C" int uspace_uvit_pack_weights(const uspace_uvit_config* cfg, const float* const* params, int n_params,
@@ -256,7 +257,9 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
     const uspace_uvit_config& c = *cfg;
     const std::shared_ptr<const Model> mp = model_for(c);
     const Model& m = *mp;
-    const Workspace w = plan_workspace(c, m, B);
+    // the K-split tail switch, read once: the workspace, the slot counts the consumers are told and every launch follow this reading
+    const bool sk_on = uspace_gemm_get_sk() != 0;
+    const Workspace w = plan_workspace(c, m, B, sk_on);
     if (workspace_bytes < w.total) return USPACE_ERR_WORKSPACE;
 
     const int D = c.embed_dim, Hd = c.mlp_hidden, L = m.L, H = c.num_heads;
@@ -297,7 +300,7 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
     };
     uspace_gemm_ext sk_tmp;                           // (the call reads it before it returns)
     auto sk_ptr = [&](const uspace_gemm_ext& e) { sk_tmp = with_sk(e); return (const uspace_gemm_ext*)&sk_tmp; };
-    const bool fold = g_ln_fold.load() != 0 && uspace_gemm_part_slots(B * m.L, c.embed_dim) <= 8;   // consumers read <= 8 partial slots per row
+    const bool fold = g_ln_fold.load() != 0 && us_gemm_part_slots_k(M, D, 64, sk_on) <= 8;   // consumers read <= 8 partial slots per row
     const size_t MD = (size_t)M * D;
 
     constexpr int B_ = USPACE_EPI_BIAS, G_ = USPACE_EPI_GELU, R_ = USPACE_EPI_RESIDUAL, F_ = USPACE_EPI_OUT_F32,
@@ -311,8 +314,8 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
             float* cf = (float*)(ws + w.ctx_f32);
             const long n = (long)B * c.n_extra * c.clip_dim;
             US_TRY(uspace_cast_f32_bf16(io->context, cbf, n, stream));
-            US_TRY(uspace_gemm_bf16(cbf, c.clip_dim, nullptr, 0, c.clip_dim, PH(m.cw), c.clip_dim, B * c.n_extra, D,
-                                    c.clip_dim, B_ | F_, PF(m.cb), nullptr, 0, cf, D, nullptr, 0, stream));
+            US_TRY(us_gemm_bf16_ext(cbf, c.clip_dim, nullptr, 0, c.clip_dim, PH(m.cw), c.clip_dim, B * c.n_extra, D,
+                                    c.clip_dim, B_ | F_, PF(m.cb), nullptr, 0, cf, D, nullptr, 0, nullptr, sk_on, stream));
             extra = cf;
         } else {
             extra = io->context;
@@ -329,8 +332,8 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
         // except the first centring pass; the residual stream x itself is unchanged (fp32).
         constexpr int C_ = USPACE_EPI_CEN_OUT, L_ = USPACE_EPI_LN_IN;
         // partial-sum slots per row of each producer (the 64-wide tile form of short-K launches writes more of them)
-        const int slots_skip = uspace_gemm_part_slots_k(M, D, 2 * D), slots_proj = uspace_gemm_part_slots_k(M, D, D),
-                  slots_fc2 = uspace_gemm_part_slots_k(M, D, Hd);
+        const int slots_skip = us_gemm_part_slots_k(M, D, 2 * D, sk_on), slots_proj = us_gemm_part_slots_k(M, D, D, sk_on),
+                  slots_fc2 = us_gemm_part_slots_k(M, D, Hd, sk_on);
         if (slots_skip <= 0 || slots_proj <= 0 || slots_fc2 <= 0) return USPACE_ERR_ARG;
         auto PFx = [&](int idx) { return (const float*)(wb + m.lay.p[idx].offset); };
         US_TRY(uspace_center_rows(x, xc, cbuf, part, M, D, stream));
@@ -355,8 +358,8 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
                 uspace_gemm_ext pskip = prod;
                 pskip.row_add = cskip + (size_t)si * M;
                 pskip.col_add = PFx(b.skip_cs2);
-                US_TRY(uspace_gemm_bf16_ext(xb, D, skips + (size_t)si * MD, D, D, PH(b.skip_w), 2 * D, M, D, 2 * D, K_ | C_ | B_ | F_, PF(b.skip_b),
-                                            nullptr, 0, x, D, nullptr, 0, sk_ptr(pskip), stream));
+                US_TRY(us_gemm_bf16_ext(xb, D, skips + (size_t)si * MD, D, D, PH(b.skip_w), 2 * D, M, D, 2 * D, K_ | C_ | B_ | F_, PF(b.skip_b),
+                                        nullptr, 0, x, D, nullptr, 0, sk_ptr(pskip), sk_on, stream));
                 np = slots_skip;
                 cen_in = xc;
                 c_in = cbuf;
@@ -364,34 +367,34 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
             uspace_gemm_ext cons{};
             cons.row_c = c_in; cons.c_out = cbuf; cons.part_in = part; cons.np_in = np; cons.norm_dim = D; cons.eps = 1e-5f;
             cons.colsum = PFx(b.qkv_cs);
-            US_TRY(uspace_gemm_bf16_ext(cen_in, D, nullptr, 0, D, PH(b.qkv_f), D, M, 3 * D, D, L_ | B_ | H_, PFx(b.qkv_fb), nullptr, 0,
-                                        nullptr, 0, qkv, 3 * D, &cons, stream));
+            US_TRY(us_gemm_bf16_ext(cen_in, D, nullptr, 0, D, PH(b.qkv_f), D, M, 3 * D, D, L_ | B_ | H_, PFx(b.qkv_fb), nullptr, 0,
+                                    nullptr, 0, qkv, 3 * D, &cons, sk_on, stream));
             const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
             US_TRY(uspace_attention_bf16(qkv, ks, h, B, L, H, stream));
-            US_TRY(uspace_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, C_ | B_ | R_ | F_, PF(b.projb), x, D, x, D,
-                                        nullptr, 0, sk_ptr(prod), stream));
+            US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, C_ | B_ | R_ | F_, PF(b.projb), x, D, x, D,
+                                    nullptr, 0, sk_ptr(prod), sk_on, stream));
             np = slots_proj;
             cons.row_c = cbuf;
             cons.np_in = np;
             cons.colsum = PFx(b.fc1_cs);
             if (is_in) cons.c_out = cskip + (size_t)i * M;      // the row means at norm2 of an in-block stay with its skip
-            US_TRY(uspace_gemm_bf16_ext(xc, D, nullptr, 0, D, PH(b.fc1_f), D, M, Hd, D, L_ | B_ | G_ | H_, PFx(b.fc1_fb), nullptr, 0,
-                                        nullptr, 0, f, Hd, &cons, stream));
+            US_TRY(us_gemm_bf16_ext(xc, D, nullptr, 0, D, PH(b.fc1_f), D, M, Hd, D, L_ | B_ | G_ | H_, PFx(b.fc1_fb), nullptr, 0,
+                                    nullptr, 0, f, Hd, &cons, sk_on, stream));
             if (is_in) {
                 // the next block starts with a norm: centred copy + partials -- written into the skip slot
                 uspace_gemm_ext pin = prod;
                 pin.row_c = cskip + (size_t)i * M;
                 pin.out_cen = skips + (size_t)i * MD;
-                US_TRY(uspace_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, C_ | B_ | R_ | F_, PF(b.fc2b), x, D,
-                                            x, D, nullptr, 0, sk_ptr(pin), stream));
+                US_TRY(us_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, C_ | B_ | R_ | F_, PF(b.fc2b), x, D,
+                                        x, D, nullptr, 0, sk_ptr(pin), sk_on, stream));
                 np = slots_fc2;
                 cen_in = skips + (size_t)i * MD;
                 c_in = cskip + (size_t)i * M;
             } else {
                 // mid / out blocks: the next consumer is skip_linear (raw bf16 xb) or the head (its own norm)
                 uint16_t* copy = is_last ? nullptr : xb;
-                US_TRY(uspace_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, copy ? (B_ | R_ | F_ | H_) : (B_ | R_ | F_),
-                                            PF(b.fc2b), x, D, x, D, copy, D, sk_ptr(plain), stream));
+                US_TRY(us_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, copy ? (B_ | R_ | F_ | H_) : (B_ | R_ | F_),
+                                        PF(b.fc2b), x, D, x, D, copy, D, sk_ptr(plain), sk_on, stream));
             }
             if (i == half) {
                 if (io->mid_tap) {
@@ -409,25 +412,25 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
         if (is_out) {
             // x = skip_linear(cat([x, skip]))  -- two K slabs, skips popped LIFO (libs/uvit.py:159,340)
             const uint16_t* skip = skips + (size_t)(m.nblocks - 1 - i) * MD;
-            US_TRY(uspace_gemm_bf16_ext(xb, D, skip, D, D, PH(b.skip_w), 2 * D, M, D, 2 * D, B_ | F_, PF(b.skip_b),
-                                        nullptr, 0, x, D, nullptr, 0, sk_ptr(plain), stream));
+            US_TRY(us_gemm_bf16_ext(xb, D, skip, D, D, PH(b.skip_w), 2 * D, M, D, 2 * D, B_ | F_, PF(b.skip_b),
+                                    nullptr, 0, x, D, nullptr, 0, sk_ptr(plain), sk_on, stream));
         }
         // x += proj(attn(norm1(x)))
         US_TRY(uspace_layernorm_f32_bf16(x, PF(b.n1w), PF(b.n1b), h, M, D, 1e-5f, stream));
-        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(b.qkv), D, M, 3 * D, D, H_, nullptr, nullptr, 0, nullptr, 0,
-                                qkv, 3 * D, stream));
+        US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.qkv), D, M, 3 * D, D, H_, nullptr, nullptr, 0, nullptr, 0,
+                                qkv, 3 * D, nullptr, sk_on, stream));
         const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
         US_TRY(uspace_attention_bf16(qkv, ks, h, B, L, H, stream));
-        US_TRY(uspace_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, B_ | R_ | F_, PF(b.projb), x, D, x, D,
-                                    nullptr, 0, sk_ptr(plain), stream));
+        US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, B_ | R_ | F_, PF(b.projb), x, D, x, D,
+                                nullptr, 0, sk_ptr(plain), sk_on, stream));
         // x += fc2(gelu(fc1(norm2(x))))
         US_TRY(uspace_layernorm_f32_bf16(x, PF(b.n2w), PF(b.n2b), h, M, D, 1e-5f, stream));
-        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(b.fc1w), D, M, Hd, D, B_ | G_ | H_, PF(b.fc1b), nullptr, 0,
-                                nullptr, 0, f, Hd, stream));
+        US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.fc1w), D, M, Hd, D, B_ | G_ | H_, PF(b.fc1b), nullptr, 0,
+                                nullptr, 0, f, Hd, nullptr, sk_on, stream));
         // bf16 copy of the block output: the skip (in-blocks) or the next skip_linear's first K slab
         uint16_t* copy = is_in ? skips + (size_t)i * MD : (is_last ? nullptr : xb);
-        US_TRY(uspace_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, copy ? (B_ | R_ | F_ | H_) : (B_ | R_ | F_),
-                                    PF(b.fc2b), x, D, x, D, copy, D, sk_ptr(plain), stream));
+        US_TRY(us_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, copy ? (B_ | R_ | F_ | H_) : (B_ | R_ | F_),
+                                PF(b.fc2b), x, D, x, D, copy, D, sk_ptr(plain), sk_on, stream));
         if (i == half) {
             if (io->mid_tap) {
                 if (hipMemcpyAsync(io->mid_tap, x, MD * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
