@@ -341,6 +341,34 @@ USPACE_API int uspace_vae_decode_tap(const uspace_vae_config* cfg, const void* b
                                      const float* z, float scale_factor, int B, int stop_after, float* dump, int* hc_out,
                                      uspace_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * VAE encode (images -> latents): FrozenAutoencoderKL.encode_moments / sample of libs/autoencoder.py:428-442 =
+ * Encoder.forward (:215-300; double_z, 3 input channels, no attention in the down path, Downsample with a conv)
+ * -> quant_conv.  Same uspace_vae_config as the decode; ch must also be a power of two.
+ * ------------------------------------------------------------------------------------- */
+/* parameter tensors in the reference's state_dict order: encoder.* then quant_conv.* */
+USPACE_API int uspace_vae_enc_num_params(const uspace_vae_config* cfg);
+USPACE_API long uspace_vae_enc_param_numel(const uspace_vae_config* cfg, int index);
+USPACE_API size_t uspace_vae_enc_weight_bytes(const uspace_vae_config* cfg);
+USPACE_API size_t uspace_vae_enc_workspace_bytes(const uspace_vae_config* cfg, int B);
+USPACE_API int uspace_vae_enc_pack_weights(const uspace_vae_config* cfg, const float* const* params, int n_params,
+                                           void* blob, size_t blob_bytes, uspace_stream_t stream);
+/* img [B,3,resolution,resolution] fp32 (NCHW) -> moments [B,8,h,h] fp32 (NCHW; mean = channels 0-3, logvar = 4-7).
+ * Every map stays below 2^30 elements: B * (resolution+2)^2 * ch < 2^30, at the SD shape B <= 126 (encode in chunks);
+ * larger B returns USPACE_ERR_ARG. */
+USPACE_API int uspace_vae_encode_moments(const uspace_vae_config* cfg, const void* blob, void* workspace,
+                                         size_t workspace_bytes, const float* img, float* moments, int B,
+                                         uspace_stream_t stream);
+/* Test aid: stop after stage `stop_after` (0 conv_in, then one per res block / downsample of the down path in
+ * execution order, then mid.block_1, mid.attn_1, mid.block_2) and copy that fp32 zero-bordered NHWC map
+ * [B,H+2,H+2,C] to `dump` (device, large enough); hc_out (host int[2]) receives {H, C}. */
+USPACE_API int uspace_vae_encode_tap(const uspace_vae_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                     const float* img, int B, int stop_after, float* dump, int* hc_out,
+                                     uspace_stream_t stream);
+/* z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise): moments [B,8,h,h], noise / z [B,4,h,h], fp32 NCHW */
+USPACE_API int uspace_vae_sample(const float* moments, const float* noise, float scale, float* z, int B, int h,
+                                 uspace_stream_t stream);
+
 /* hipGraph form of the forward.  _create() runs the forward once eagerly on `capture_stream` (must be a
  * real, non-NULL stream), then captures the same launch sequence and instantiates it.  The pointers in
  * `io`, the blob and the workspace are baked in: keep them alive and stable, refresh their CONTENTS

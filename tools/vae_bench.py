@@ -1,6 +1,7 @@
 """Throughput of the SD KL-VAE decode (4x32x32 -> 3x256x256) on the HIP path, with the algorithmic FLOPs of the
-reference's Decoder (libs/autoencoder.py:303-409) counted from the configuration.
-    python tools/vae_bench.py [--batch 8] [--iters 5]"""
+reference's Decoder (libs/autoencoder.py:303-409) counted from the configuration; with --encode, of the encode
+(3x256x256 -> moments 8x32x32, Encoder + quant_conv, libs/autoencoder.py:215-300,428-431) instead.
+    python tools/vae_bench.py [--batch 8] [--iters 5] [--encode]"""
 import argparse
 import json
 import os
@@ -41,13 +42,41 @@ def decoder_flops(dd):
     return f
 
 
+def encoder_flops(dd):
+    """2*MACs of every conv / attention matmul of one image through Encoder + quant_conv (272.7 GFLOP at SD)."""
+    ch, mult, nrb, res = dd["ch"], dd["ch_mult"], dd["num_res_blocks"], dd["resolution"]
+    n = len(mult)
+    h, c = res, ch
+
+    def conv(ci, co, k, hh):
+        return 2 * ci * co * k * k * hh * hh
+
+    def resb(ci, co, hh):
+        return conv(ci, co, 3, hh) + conv(co, co, 3, hh) + (conv(ci, co, 1, hh) if ci != co else 0)
+    f = conv(3, ch, 3, h)
+    for lvl in range(n):
+        co = ch * mult[lvl]
+        for _ in range(nrb):
+            f += resb(c, co, h)
+            c = co
+        if lvl != n - 1:
+            h //= 2
+            f += conv(c, c, 3, h)
+    f += 2 * resb(c, c, h) + 4 * conv(c, c, 1, h) + 2 * 2 * (h * h) ** 2 * c
+    f += conv(c, 2 * dd["z_channels"], 3, h) + conv(2 * dd["z_channels"], 2 * dd["z_channels"], 1, h)
+    return f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--encode", action="store_true", help="measure encode_moments instead of decode")
     a = ap.parse_args()
     from uspace_amd.libs.autoencoder import FrozenAutoencoderKL
     torch.manual_seed(0)
+    if a.encode:
+        return bench_encode(a, FrozenAutoencoderKL)
     vae = FrozenAutoencoderKL(SD, 4).cuda()
     z = (torch.randn(a.batch, 4, 32, 32) * 0.18215).cuda()
     vae.decode(z, chunk=a.batch)
@@ -60,6 +89,22 @@ def main():
     fl = decoder_flops(SD)
     print(json.dumps({"workload": "SD KL-VAE decode 4x32x32 -> 3x256x256", "batch": a.batch, "ms_per_batch": dt * 1e3,
                       "img_per_s": a.batch / dt, "gflop_per_img": fl / 1e9, "tflops": fl * a.batch / dt / 1e12}))
+
+
+def bench_encode(a, FrozenAutoencoderKL):
+    vae = FrozenAutoencoderKL(SD, 4, encoder=True).cuda()
+    x = (torch.rand(a.batch, 3, 256, 256) * 2 - 1).cuda()
+    vae.encode_moments(x, chunk=a.batch)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.iters):
+        vae.encode_moments(x, chunk=a.batch)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / a.iters
+    fl = encoder_flops(SD)
+    print(json.dumps({"workload": "SD KL-VAE encode_moments 3x256x256 -> 8x32x32", "batch": a.batch,
+                      "ms_per_batch": dt * 1e3, "img_per_s": a.batch / dt, "gflop_per_img": fl / 1e9,
+                      "tflops": fl * a.batch / dt / 1e12}))
 
 
 if __name__ == "__main__":

@@ -113,6 +113,14 @@ SIGNATURES = {
     "uspace_vae_pack_weights": (_I, [ctypes.POINTER(VaeConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
     "uspace_vae_decode": (_I, [ctypes.POINTER(VaeConfig), _P, _P, _SZ, _P, _F, _P, _I, _P]),
     "uspace_vae_decode_tap": (_I, [ctypes.POINTER(VaeConfig), _P, _P, _SZ, _P, _F, _I, _I, _P, ctypes.POINTER(_I), _P]),
+    "uspace_vae_enc_num_params": (_I, [ctypes.POINTER(VaeConfig)]),
+    "uspace_vae_enc_param_numel": (_L, [ctypes.POINTER(VaeConfig), _I]),
+    "uspace_vae_enc_weight_bytes": (_SZ, [ctypes.POINTER(VaeConfig)]),
+    "uspace_vae_enc_workspace_bytes": (_SZ, [ctypes.POINTER(VaeConfig), _I]),
+    "uspace_vae_enc_pack_weights": (_I, [ctypes.POINTER(VaeConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
+    "uspace_vae_encode_moments": (_I, [ctypes.POINTER(VaeConfig), _P, _P, _SZ, _P, _P, _I, _P]),
+    "uspace_vae_encode_tap": (_I, [ctypes.POINTER(VaeConfig), _P, _P, _SZ, _P, _I, _I, _P, ctypes.POINTER(_I), _P]),
+    "uspace_vae_sample": (_I, [_P, _P, _F, _P, _I, _I, _P]),
     "uspace_clip_num_params": (_I, [ctypes.POINTER(ClipConfig)]),
     "uspace_clip_param_numel": (_L, [ctypes.POINTER(ClipConfig), _I]),
     "uspace_clip_weight_bytes": (_SZ, [ctypes.POINTER(ClipConfig)]),

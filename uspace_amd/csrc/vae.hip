@@ -7,6 +7,9 @@
 // carry the residual stream; GroupNorm(+SiLU) turns them into the bf16 operand maps (border re-zeroed).
 // Nearest-2x upsampling writes the next resolution's bf16 operand directly.  The single-head mid-block
 // attention (1024 tokens x 512 channels) runs as two GEMMs per image around a row softmax.
+//
+// The encoder (images [B,3,R,R] -> moments [B,8,h,w], libs/autoencoder.py:215-300,428-431) runs on the same helpers
+// (VaeRun); its stride-2 downsample convolves four bf16 phase maps of the input with the same slab GEMM.
 #include <algorithm>
 #include <vector>
 
@@ -295,6 +298,160 @@ __global__ __launch_bounds__(256) void vae_conv_out_kernel(const bf16_t* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------ encoder kernels
+// Encoder conv_in (3 -> C0, 3x3, pad 1, libs/autoencoder.py:224-228) on NCHW fp32 images -> fp32 zero-bordered NHWC
+// map (interior only).  K = 27 is too narrow for an MFMA tile and the kernel is store-bound (R^2 * C0 * 4 bytes per
+// image): C0/4 adjacent lanes share a pixel, each holding its 4 channels' 27 weights in registers for the whole launch
+// and writing one 16 B vector.  w: fp32 checkpoint layout [C0][3][3][3].  64-bit pixel offsets.
+__global__ __launch_bounds__(256) void vae_enc_conv_in_kernel(const float* __restrict__ img, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, float* __restrict__ out,
+                                                              int B, int R, int C0) {
+    const int C4 = C0 >> 2;
+    const int q = threadIdx.x % C4;
+    const long slot = ((long)blockIdx.x * 256 + threadIdx.x) / C4, slots = (long)gridDim.x * 256 / C4;
+    float wr[4][27];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int e = 0; e < 27; ++e) wr[j][e] = w[(4 * q + j) * 27 + e];
+    const f32x4 bs = *(const f32x4*)(bias + 4 * q);
+    const long plane = (long)R * R, npix = (long)B * plane;
+    for (long pix = slot; pix < npix; pix += slots) {
+        const long b = pix / plane;
+        const int rr = (int)(pix - b * plane), y = rr / R, x = rr - (rr / R) * R;
+        float nb[27];   // (c, dy, dx) order, 0 outside the image
+#pragma unroll
+        for (int e = 0; e < 27; ++e) {
+            const int c = e / 9, dy = (e % 9) / 3 - 1, dx = e % 3 - 1;
+            const int yy = y + dy, xx = x + dx;
+            nb[e] = (yy >= 0 && yy < R && xx >= 0 && xx < R) ? img[((b * 3 + c) * R + yy) * R + xx] : 0.f;
+        }
+        f32x4 s = bs;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 27; ++e) s[j] += wr[j][e] * nb[e];
+        *(f32x4*)(out + ((b * (R + 2) + y + 1) * (R + 2) + x + 1) * C0 + 4 * q) = s;
+    }
+}
+
+// Downsample operand (libs/autoencoder.py:53-70: pad (0,1,0,1), 3x3 stride 2): fp32 map [B,H+2,H+2,C] interior -> four
+// bf16 phase maps E[py,px][a,b] = x[2a+py, 2b+px] in the zero-bordered layout of the output resolution Ho = H/2,
+// phase p = 2*py+px at rows p*prow.  The conv's bottom / right pad x[H] = 0 is the phase maps' border row / column Ho+1,
+// written as zero from the index here (never read from the fp32 map, whose border holds conv garbage).
+__global__ __launch_bounds__(256) void downsample_phases_kernel(const float* __restrict__ x, bf16_t* __restrict__ y,
+                                                                int B, int H, int C, long prow) {
+    const int C4 = C >> 2, Ho = H >> 1, P = Ho + 2;
+    const long rows = (long)B * P * P;
+    const long total = 4 * rows * C4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long ra = i / C4;
+        const int c = (int)(i % C4) * 4;
+        const int ph = (int)(ra / rows);
+        const long row = ra - ph * rows;
+        const int xx = (int)(row % P), yy = (int)((row / P) % P);
+        const long b = row / ((long)P * P);
+        uint2 o = make_uint2(0u, 0u);
+        if (xx >= 1 && xx <= Ho && yy >= 1 && yy <= Ho) {
+            const int sy = 2 * (yy - 1) + (ph >> 1), sx = 2 * (xx - 1) + (ph & 1);
+            const f32x4 v = *(const f32x4*)(x + ((b * (H + 2) + sy + 1) * (H + 2) + sx + 1) * C + c);
+            o.x = pack_bf2(v[0], v[1]);
+            o.y = pack_bf2(v[2], v[3]);
+        }
+        *(uint2*)(y + (ph * prow + row) * C + c) = o;
+    }
+}
+
+// Encoder conv_out (C -> 8, 3x3, libs/autoencoder.py:269-273) fused with quant_conv (8 -> 8, 1x1, :419,430) -> NCHW fp32
+// moments.  LPP = C/8 adjacent lanes share a group of 4 consecutive pixels of one row, each lane owning 8 channels; eight
+// outputs of 9x8 weights each do not fit in registers, so a lane streams its weights (fp32 [8][9][C], L1 / L2 resident)
+// once per tap and output and uses them for the 4 pixels.  The 32 sums are reduced across the LPP lanes, and lane 0 adds
+// the bias and applies quant_conv.  x: bf16 zero-bordered map; wq: fp32 [8][8]; out [B,8,H,W].
+__global__ __launch_bounds__(256) void vae_enc_conv_out_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, const float* __restrict__ wq,
+                                                               const float* __restrict__ bq, float* __restrict__ out,
+                                                               int B, int H, int W, int C) {
+    const int LPP = C >> 3;
+    const int l = threadIdx.x % LPP;
+    const int WG = (W + 3) >> 2;   // pixel groups per row
+    const long slot = ((long)blockIdx.x * 256 + threadIdx.x) / LPP, slots = (long)gridDim.x * 256 / LPP;
+    const long ngroups = (long)B * H * WG;
+    for (long gi = slot; gi < ngroups; gi += slots) {
+        const int xg = (int)(gi % WG), yy = (int)((gi / WG) % H);
+        const long b = gi / ((long)WG * H);
+        const int x0 = xg * 4;
+        const bf16_t* xc = x + ((b * (H + 2) + yy + 1) * (W + 2) + x0 + 1) * C + l * 8;
+        float acc[4][8];
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int o = 0; o < 8; ++o) acc[p][o] = 0.f;
+#pragma unroll 1
+        for (int t = 0; t < 9; ++t) {
+            const int dy = t / 3 - 1, dx = t % 3 - 1;
+            float a[4][8];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                uint4 q = make_uint4(0u, 0u, 0u, 0u);
+                if (x0 + p < W) q = *(const uint4*)(xc + ((long)dy * (W + 2) + dx + p) * C);
+                const uint32_t u[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    a[p][2 * e] = __uint_as_float(u[e] << 16);
+                    a[p][2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u);
+                }
+            }
+#pragma unroll
+            for (int o = 0; o < 8; ++o) {
+                const float* wr = w + (size_t)(o * 9 + t) * C + l * 8;
+                const f32x4 w0 = *(const f32x4*)wr, w1 = *(const f32x4*)(wr + 4);
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    acc[p][o] += a[p][0] * w0[0] + a[p][1] * w0[1] + a[p][2] * w0[2] + a[p][3] * w0[3] +
+                                 a[p][4] * w1[0] + a[p][5] * w1[1] + a[p][6] * w1[2] + a[p][7] * w1[3];
+            }
+        }
+        for (int off = LPP >> 1; off > 0; off >>= 1)
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int o = 0; o < 8; ++o) acc[p][o] += __shfl_xor(acc[p][o], off, 64);
+        if (l == 0) {
+            const long plane = (long)H * W;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                if (x0 + p >= W) continue;
+                float h[8];
+#pragma unroll
+                for (int o = 0; o < 8; ++o) h[o] = acc[p][o] + bias[o];
+                float* op = out + b * 8 * plane + (long)yy * W + x0 + p;
+#pragma unroll
+                for (int o2 = 0; o2 < 8; ++o2) {
+                    float m = bq[o2];
+#pragma unroll
+                    for (int o = 0; o < 8; ++o) m += wq[o2 * 8 + o] * h[o];
+                    op[o2 * plane] = m;
+                }
+            }
+        }
+    }
+}
+
+// FrozenAutoencoderKL.sample (libs/autoencoder.py:433-439): z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps),
+// moments [B,8,h,w] = (mean, logvar) along channels, eps / z [B,4,h,w].  Rounded step by step as the reference's
+// elementwise ops are (no contraction into FMAs).
+__global__ __launch_bounds__(256) void vae_sample_kernel(const float* __restrict__ m, const float* __restrict__ eps,
+                                                         float scale, float* __restrict__ z, int B, int hw) {
+    const long half = 4L * hw, total = (long)B * half;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long b = i / half, r = i - b * half;
+        const float mean = m[b * 2 * half + r];
+        const float lv = fminf(fmaxf(m[b * 2 * half + half + r], -30.0f), 20.0f);
+        const float sd = expf(__fmul_rn(0.5f, lv));
+        z[i] = __fmul_rn(scale, __fadd_rn(mean, __fmul_rn(sd, eps[i])));
+    }
+}
+
 // weight repacks (fp32 checkpoint layout -> kernel layout)
 __global__ void repack_conv3_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int Co, int Ci) {
     const long n = (long)Co * Ci * 9;   // src [Co][Ci][3][3] -> dst [Co][9][Ci]
@@ -335,16 +492,14 @@ struct ResIdx {
     int cin, cout;
 };
 
-struct VaeModel {
+struct AttnIdx {   // single-head AttnBlock (libs/autoencoder.py:139-195): norm, q, k, v, proj_out
+    int nw, nb, q_w, q_b, k_w, k_b, v_w, v_b, po_w, po_b;
+};
+
+// parameter list of one packed blob, in the reference's state_dict order
+struct ParamTable {
     std::vector<PDesc> p;
     size_t blob_bytes = 0;
-    int conv_in_w, conv_in_b;
-    ResIdx mid1, mid2;
-    int an_w, an_b, q_w, q_b, k_w, k_b, v_w, v_b, po_w, po_b;
-    std::vector<std::vector<ResIdx>> up;   // [level][block]
-    std::vector<int> us_w, us_b;           // upsample conv per level (-1 at level 0)
-    int no_w, no_b, co_w, co_b, pq_w, pq_b;
-    int n_levels, c_top, z_res, res;
     int add(long numel, PKind k, int co = 0, int ci = 0) {
         PDesc d{numel, k, co, ci, blob_bytes, 0};
         d.bytes = (size_t)numel * ((k == P_CONV3_BF16 || k == P_CONV1_BF16) ? 2 : 4);
@@ -362,6 +517,25 @@ struct VaeModel {
         if (cin != cout) { r.sw = add((long)cout * cin, P_CONV1_BF16, cout, cin); r.sb = add(cout, P_F32); }
         return r;
     }
+    AttnIdx add_attn(int c) {
+        AttnIdx a;
+        a.nw = add(c, P_F32); a.nb = add(c, P_F32);
+        a.q_w = add((long)c * c, P_CONV1_BF16, c, c); a.q_b = add(c, P_F32);
+        a.k_w = add((long)c * c, P_CONV1_BF16, c, c); a.k_b = add(c, P_F32);
+        a.v_w = add((long)c * c, P_CONV1_BF16, c, c); a.v_b = add(c, P_F32);
+        a.po_w = add((long)c * c, P_CONV1_BF16, c, c); a.po_b = add(c, P_F32);
+        return a;
+    }
+};
+
+struct VaeModel : ParamTable {
+    int conv_in_w, conv_in_b;
+    ResIdx mid1, mid2;
+    AttnIdx attn;
+    std::vector<std::vector<ResIdx>> up;   // [level][block]
+    std::vector<int> us_w, us_b;           // upsample conv per level (-1 at level 0)
+    int no_w, no_b, co_w, co_b, pq_w, pq_b;
+    int n_levels, c_top, z_res, res;
 };
 
 bool valid_vae(const uspace_vae_config* c) {
@@ -384,11 +558,7 @@ VaeModel build_vae(const uspace_vae_config& c) {
     m.c_top = block_in;
     m.conv_in_w = m.add((long)block_in * 4 * 9, P_F32); m.conv_in_b = m.add(block_in, P_F32);
     m.mid1 = m.add_res(block_in, block_in);
-    m.an_w = m.add(block_in, P_F32); m.an_b = m.add(block_in, P_F32);
-    m.q_w = m.add((long)block_in * block_in, P_CONV1_BF16, block_in, block_in); m.q_b = m.add(block_in, P_F32);
-    m.k_w = m.add((long)block_in * block_in, P_CONV1_BF16, block_in, block_in); m.k_b = m.add(block_in, P_F32);
-    m.v_w = m.add((long)block_in * block_in, P_CONV1_BF16, block_in, block_in); m.v_b = m.add(block_in, P_F32);
-    m.po_w = m.add((long)block_in * block_in, P_CONV1_BF16, block_in, block_in); m.po_b = m.add(block_in, P_F32);
+    m.attn = m.add_attn(block_in);
     m.mid2 = m.add_res(block_in, block_in);
     // channel flow follows construction order (levels reversed); state_dict lists up.0 .. up.{n-1}
     std::vector<int> in_at(c.n_levels);
@@ -412,10 +582,63 @@ VaeModel build_vae(const uspace_vae_config& c) {
     return m;
 }
 
+// Encoder (libs/autoencoder.py:215-300) with double_z, 3 input channels and no attention in the down path, then quant_conv
+struct EncModel : ParamTable {
+    int conv_in_w, conv_in_b;
+    std::vector<std::vector<ResIdx>> down;   // [level][block]
+    std::vector<int> ds_w, ds_b;             // downsample conv per level (-1 at the last level)
+    ResIdx mid1, mid2;
+    AttnIdx attn;
+    int no_w, no_b, co_w, co_b, qc_w, qc_b;
+    int n_levels, c_top, z_res, res;
+};
+
+bool valid_enc(const uspace_vae_config* c) {
+    return valid_vae(c) && c->ch <= 512 && (c->ch & (c->ch - 1)) == 0;   // conv_in's C0 = ch feeds a GroupNorm
+}
+
+// parameter order = the reference's state_dict order (encoder.*, then quant_conv.*)
+EncModel build_enc(const uspace_vae_config& c) {
+    EncModel m;
+    m.n_levels = c.n_levels;
+    m.res = c.resolution;
+    m.z_res = c.resolution >> (c.n_levels - 1);
+    m.conv_in_w = m.add((long)c.ch * 3 * 9, P_F32); m.conv_in_b = m.add(c.ch, P_F32);
+    m.down.resize(c.n_levels);
+    m.ds_w.assign(c.n_levels, -1);
+    m.ds_b.assign(c.n_levels, -1);
+    int bi = c.ch;
+    for (int lvl = 0; lvl < c.n_levels; ++lvl) {
+        const int bo = c.ch * c.ch_mult[lvl];
+        for (int j = 0; j < c.num_res_blocks; ++j) { m.down[lvl].push_back(m.add_res(bi, bo)); bi = bo; }
+        if (lvl != c.n_levels - 1) { m.ds_w[lvl] = m.add((long)bi * bi * 9, P_CONV3_BF16, bi, bi); m.ds_b[lvl] = m.add(bi, P_F32); }
+    }
+    m.c_top = bi;
+    m.mid1 = m.add_res(bi, bi);
+    m.attn = m.add_attn(bi);
+    m.mid2 = m.add_res(bi, bi);
+    m.no_w = m.add(bi, P_F32); m.no_b = m.add(bi, P_F32);
+    m.co_w = m.add((long)8 * bi * 9, P_CONV3_F32T, 8, bi); m.co_b = m.add(8, P_F32);
+    m.qc_w = m.add(64, P_F32); m.qc_b = m.add(8, P_F32);
+    return m;
+}
+
 struct VaeWs {
     size_t fa, fb, hb, xb, stats, tok, q, k, v, vt, s, pr, o, po, total;
     long guard_rows;
 };
+
+inline size_t map_rows(int B, int res) { return (size_t)B * (res + 2) * (res + 2) + 2 * (size_t)(res + 3); }
+
+// everything after the four maps: GroupNorm statistics and the mid-block attention's buffers
+template <class Take>
+void plan_stats_attn(VaeWs& w, Take take, int B, int z_res, int c_top) {
+    w.stats = take((size_t)B * (1 + USPACE_GN_MAX_CHUNKS) * 64 * 4);
+    const size_t T = (size_t)B * z_res * z_res, Cc = c_top, HW = (size_t)z_res * z_res;
+    w.tok = take(T * Cc * 2); w.q = take(T * Cc * 2); w.k = take(T * Cc * 2); w.v = take(T * Cc * 2);
+    w.vt = take(T * Cc * 2); w.s = take(HW * HW * 4); w.pr = take(HW * HW * 2); w.o = take(T * Cc * 2);
+    w.po = take(T * Cc * 4);
+}
 
 VaeWs plan_vae_ws(const uspace_vae_config& c, const VaeModel& m, int B) {
     VaeWs w;
@@ -424,14 +647,14 @@ VaeWs plan_vae_ws(const uspace_vae_config& c, const VaeModel& m, int B) {
     int res = m.z_res;
     int chan = m.c_top;
     for (int lvl = c.n_levels - 1; lvl >= 0; --lvl) {
-        const size_t rows = (size_t)B * (res + 2) * (res + 2) + 2 * (size_t)(res + 3);
+        const size_t rows = map_rows(B, res);
         const int cmax = chan > c.ch * c.ch_mult[lvl] ? chan : c.ch * c.ch_mult[lvl];
         max_f = std::max(max_f, rows * cmax * 4);
         max_h = std::max(max_h, rows * cmax * 2);
         chan = c.ch * c.ch_mult[lvl];
         if (lvl != 0) {
             res *= 2;
-            const size_t rows2 = (size_t)B * (res + 2) * (res + 2) + 2 * (size_t)(res + 3);
+            const size_t rows2 = map_rows(B, res);
             max_h = std::max(max_h, rows2 * chan * 2);
             max_f = std::max(max_f, rows2 * chan * 4);
         }
@@ -439,15 +662,185 @@ VaeWs plan_vae_ws(const uspace_vae_config& c, const VaeModel& m, int B) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
     w.fa = take(max_f); w.fb = take(max_f); w.hb = take(max_h); w.xb = take(max_h);
-    w.stats = take((size_t)B * (1 + USPACE_GN_MAX_CHUNKS) * 64 * 4);
-    const size_t T = (size_t)B * m.z_res * m.z_res, Cc = m.c_top, HW = (size_t)m.z_res * m.z_res;
-    w.tok = take(T * Cc * 2); w.q = take(T * Cc * 2); w.k = take(T * Cc * 2); w.v = take(T * Cc * 2);
-    w.vt = take(T * Cc * 2); w.s = take(HW * HW * 4); w.pr = take(HW * HW * 2); w.o = take(T * Cc * 2);
-    w.po = take(T * Cc * 4);
+    plan_stats_attn(w, take, B, m.z_res, m.c_top);
     w.total = off;
     return w;
 }
 
+// one downsample phase map (guard rows included): the phase stride of the stride-2 convolution, in rows
+inline long phase_rows(int B, int Ho) { return (long)map_rows(B, Ho); }
+
+VaeWs plan_enc_ws(const uspace_vae_config& c, const EncModel& m, int B) {
+    VaeWs w;
+    size_t max_f = 0, max_h = 0;
+    int res = c.resolution, chan = c.ch;
+    for (int lvl = 0; lvl < c.n_levels; ++lvl) {
+        const int bo = c.ch * c.ch_mult[lvl];
+        const size_t cmax = chan > bo ? chan : bo;
+        max_f = std::max(max_f, map_rows(B, res) * cmax * 4);
+        max_h = std::max(max_h, map_rows(B, res) * cmax * 2);
+        chan = bo;
+        if (lvl != c.n_levels - 1) {
+            res /= 2;
+            max_h = std::max(max_h, 4 * (size_t)phase_rows(B, res) * chan * 2);   // the four phase maps
+            max_f = std::max(max_f, map_rows(B, res) * chan * 4);
+        }
+    }
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
+    w.fa = take(max_f); w.fb = take(max_f); w.hb = take(max_h); w.xb = take(max_h);
+    plan_stats_attn(w, take, B, m.z_res, m.c_top);
+    w.total = off;
+    return w;
+}
+
+// fp32 checkpoint tensors -> packed blob (the layouts of PKind)
+int pack_params(const ParamTable& m, const float* const* params, int n_params, void* blob, size_t blob_bytes,
+                uspace_stream_t stream) {
+    if (n_params != (int)m.p.size()) return USPACE_ERR_ARG;
+    if (blob_bytes < m.blob_bytes) return USPACE_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < n_params; ++i) {
+        const PDesc& d = m.p[i];
+        if (!params[i]) return USPACE_ERR_ARG;
+        char* dst = (char*)blob + d.offset;
+        switch (d.kind) {
+            case P_F32:
+                if (hipMemcpyAsync(dst, params[i], d.bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return USPACE_ERR_LAUNCH;
+                break;
+            case P_CONV1_BF16:
+                US_TRY(uspace_cast_f32_bf16(params[i], (uint16_t*)dst, d.numel, stream));
+                break;
+            case P_CONV3_BF16:
+                hipLaunchKernelGGL(repack_conv3_bf16_kernel, dim3(grid_for(d.numel)), dim3(256), 0, s, params[i], (bf16_t*)dst, d.co, d.ci);
+                US_CHECK_LAUNCH();
+                break;
+            case P_CONV3_F32T:
+                hipLaunchKernelGGL(repack_conv3_f32_kernel, dim3(grid_for(d.numel)), dim3(256), 0, s, params[i], (float*)dst, d.co, d.ci);
+                US_CHECK_LAUNCH();
+                break;
+        }
+    }
+    return USPACE_OK;
+}
+
+// What the decode and the encode share: the workspace maps, GroupNorm(+SiLU), the 9-slab 3x3 convolution, the ResnetBlock
+// and the mid-block attention.  Two fp32 maps alternate as the residual stream (cur / tmp); hb / xb hold bf16 operands.
+struct VaeRun {
+    int B;
+    hipStream_t s;
+    uspace_stream_t stream;
+    const char* wb;
+    char* ws;
+    const ParamTable* m;
+    const VaeWs* w;
+    float* stats;
+    size_t cur_off, tmp_off;
+
+    VaeRun(const ParamTable& m_, const VaeWs& w_, const void* blob, void* workspace, int B_, uspace_stream_t st)
+        : B(B_), s((hipStream_t)st), stream(st), wb((const char*)blob), ws((char*)workspace), m(&m_), w(&w_),
+          stats((float*)((char*)workspace + w_.stats)), cur_off(w_.fa), tmp_off(w_.fb) {}
+
+    const float* PF(int i) const { return (const float*)(wb + m->p[i].offset); }
+    const uint16_t* PH(int i) const { return (const uint16_t*)(wb + m->p[i].offset); }
+    long rows_of(int h) const { return (long)B * (h + 2) * (h + 2); }
+    static long guard(int h) { return (long)(h + 3); }
+    // map pointers (row 0 sits `guard` rows into the buffer)
+    float* fmap(size_t off, int h, int C) const { return (float*)(ws + off) + guard(h) * C; }
+    uint16_t* hmap(size_t off, int h, int C) const { return (uint16_t*)(ws + off) + guard(h) * C; }
+
+    int group_norm(const float* x, int h, int C, int gw, int gb, bool silu, uint16_t* y) const {
+        return uspace_groupnorm_map_bf16(x, PF(gw), PF(gb), y, stats, B, h, C, silu ? 1 : 0, 1e-6f, stream);
+    }
+    int conv3(const uint16_t* a, int h, int Cin, int Cout, int wi, int bi, const float* resid, float* o) const {
+        constexpr int B_ = USPACE_EPI_BIAS, R_ = USPACE_EPI_RESIDUAL, F_ = USPACE_EPI_OUT_F32;
+        const int P = h + 2;
+        int shifts[9];
+        for (int t = 0; t < 9; ++t) shifts[t] = (t / 3 - 1) * P + (t % 3 - 1);
+        return uspace_gemm_slabs_bf16(a, Cin, PH(wi), 9 * Cin, (int)rows_of(h), Cout, Cin, 9, shifts,
+                                      resid ? (B_ | R_ | F_) : (B_ | F_), PF(bi), resid, Cout, o, Cout, nullptr, 0, stream);
+    }
+    // ResnetBlock (libs/autoencoder.py:73-134, temb None) on the current map, in place or into tmp (then swapped)
+    int resblock(const ResIdx& r, int h) {
+        constexpr int B_ = USPACE_EPI_BIAS, F_ = USPACE_EPI_OUT_F32;
+        float* x = fmap(cur_off, h, r.cin);
+        uint16_t* hb = hmap(w->hb, h, r.cin > r.cout ? r.cin : r.cout);
+        US_TRY(group_norm(x, h, r.cin, r.n1w, r.n1b, true, hb));
+        float* t1 = fmap(tmp_off, h, r.cout);
+        US_TRY(conv3(hb, h, r.cin, r.cout, r.c1w, r.c1b, nullptr, t1));
+        US_TRY(group_norm(t1, h, r.cout, r.n2w, r.n2b, true, hb));
+        if (r.cin != r.cout) {
+            // nin_shortcut (1x1) on x, written over t1 (already consumed by norm2), then conv2 accumulates onto it
+            uint16_t* xb = hmap(w->xb, h, r.cin);
+            US_TRY(uspace_cast_f32_bf16(x, xb, rows_of(h) * r.cin, stream));
+            US_TRY(uspace_gemm_bf16(xb, r.cin, nullptr, 0, r.cin, PH(r.sw), r.cin, (int)rows_of(h), r.cout, r.cin, B_ | F_,
+                                    PF(r.sb), nullptr, 0, t1, r.cout, nullptr, 0, stream));
+            US_TRY(conv3(hb, h, r.cout, r.cout, r.c2w, r.c2b, t1, t1));
+            std::swap(cur_off, tmp_off);
+        } else {
+            US_TRY(conv3(hb, h, r.cout, r.cout, r.c2w, r.c2b, x, x));   // x += conv2(...)
+        }
+        return USPACE_OK;
+    }
+    // AttnBlock over H*H tokens of Cc channels, in place on the current map
+    int mid_attn(const AttnIdx& a, int H, int Cc) {
+        constexpr int B_ = USPACE_EPI_BIAS, F_ = USPACE_EPI_OUT_F32, H_ = USPACE_EPI_OUT_BF16;
+        const int HW = H * H;
+        const long T = (long)B * HW;
+        float* x = fmap(cur_off, H, Cc);
+        uint16_t* hb = hmap(w->hb, H, Cc);
+        US_TRY(group_norm(x, H, Cc, a.nw, a.nb, false, hb));
+        uint16_t* tok = (uint16_t*)(ws + w->tok);
+        hipLaunchKernelGGL(gather_interior_kernel, dim3(grid_for(T * (Cc / 8))), dim3(256), 0, s, hb, tok, B, H, H, Cc);
+        US_CHECK_LAUNCH();
+        uint16_t *q = (uint16_t*)(ws + w->q), *k = (uint16_t*)(ws + w->k), *v = (uint16_t*)(ws + w->v);
+        uint16_t *vt = (uint16_t*)(ws + w->vt), *pr = (uint16_t*)(ws + w->pr), *o = (uint16_t*)(ws + w->o);
+        float* sc = (float*)(ws + w->s);
+        float* po = (float*)(ws + w->po);
+        US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(a.q_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(a.q_b), nullptr, 0, nullptr, 0, q, Cc, stream));
+        US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(a.k_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(a.k_b), nullptr, 0, nullptr, 0, k, Cc, stream));
+        US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(a.v_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(a.v_b), nullptr, 0, nullptr, 0, v, Cc, stream));
+        hipLaunchKernelGGL(transpose_kernel, dim3(us_cdiv(Cc, 32), us_cdiv(HW, 32), B), dim3(256), 0, s, v, vt, HW, Cc);
+        US_CHECK_LAUNCH();
+        const float scale = 1.0f / sqrtf((float)Cc);
+        for (int b = 0; b < B; ++b) {
+            // w_ = softmax(q k^T * c^-0.5) over keys; h_ = w_ v   (libs/autoencoder.py:179-191)
+            US_TRY(uspace_gemm_bf16(q + (size_t)b * HW * Cc, Cc, nullptr, 0, Cc, k + (size_t)b * HW * Cc, Cc, HW, HW, Cc, F_,
+                                    nullptr, nullptr, 0, sc, HW, nullptr, 0, stream));
+            hipLaunchKernelGGL(softmax_rows_kernel, dim3(us_cdiv(HW, 4)), dim3(256), 0, s, sc, pr, (long)HW, HW, scale);
+            US_CHECK_LAUNCH();
+            US_TRY(uspace_gemm_bf16(pr, HW, nullptr, 0, HW, vt + (size_t)b * HW * Cc, HW, HW, Cc, HW, H_, nullptr, nullptr, 0,
+                                    nullptr, 0, o + (size_t)b * HW * Cc, Cc, stream));
+        }
+        US_TRY(uspace_gemm_bf16(o, Cc, nullptr, 0, Cc, PH(a.po_w), Cc, (int)T, Cc, Cc, B_ | F_, PF(a.po_b), nullptr, 0, po, Cc, nullptr, 0, stream));
+        hipLaunchKernelGGL(scatter_add_kernel, dim3(grid_for(T * (Cc / 4))), dim3(256), 0, s, x, po, B, H, H, Cc);
+        US_CHECK_LAUNCH();
+        return USPACE_OK;
+    }
+    // Downsample (pad (0,1,0,1), 3x3 stride 2) of the current H map into tmp at H/2, then swapped.  Tap (dy, dx) reads
+    // phase (dy%2, dx%2) shifted by (dy/2, dx/2) pixels of the output layout, so it is the 9-slab GEMM with K1 = C over the
+    // phase maps.  The shifts reach 3 phase maps (~3 * B * (H/2+2)^2 rows) past A: gemm.hip's a_base() adds a slab's
+    // shift to the base pointer in 64 bits and builds that slab's buffer descriptor from the shifted base, so the 32-bit
+    // per-lane offsets stay within one map (M * lda < 2^30, checked there).
+    int downsample(int wi, int bi, int H, int C) {
+        constexpr int B_ = USPACE_EPI_BIAS, F_ = USPACE_EPI_OUT_F32;
+        const int Ho = H / 2, P = Ho + 2;
+        const long prow = phase_rows(B, Ho);
+        uint16_t* ph = hmap(w->hb, Ho, C);   // phase 0, row 0
+        hipLaunchKernelGGL(downsample_phases_kernel, dim3(grid_for(4 * rows_of(Ho) * (C / 4))), dim3(256), 0, s,
+                           fmap(cur_off, H, C), (bf16_t*)ph, B, H, C, prow);
+        US_CHECK_LAUNCH();
+        int shifts[9];
+        for (int t = 0; t < 9; ++t) {
+            const int dy = t / 3, dx = t % 3;
+            shifts[t] = (int)(((dy & 1) * 2 + (dx & 1)) * prow) + (dy >> 1) * P + (dx >> 1);
+        }
+        US_TRY(uspace_gemm_slabs_bf16(ph, C, PH(wi), 9 * C, (int)rows_of(Ho), C, C, 9, shifts, B_ | F_, PF(bi), nullptr, C,
+                                      fmap(tmp_off, Ho, C), C, nullptr, 0, stream));
+        std::swap(cur_off, tmp_off);
+        return USPACE_OK;
+    }
+};
 
 }  // namespace
 
@@ -500,32 +893,7 @@ extern "C" size_t uspace_vae_workspace_bytes(const uspace_vae_config* cfg, int B
 extern "C" int uspace_vae_pack_weights(const uspace_vae_config* cfg, const float* const* params, int n_params,
                                        void* blob, size_t blob_bytes, uspace_stream_t stream) {
     if (!valid_vae(cfg) || !params || !blob) return USPACE_ERR_ARG;
-    const VaeModel m = build_vae(*cfg);
-    if (n_params != (int)m.p.size()) return USPACE_ERR_ARG;
-    if (blob_bytes < m.blob_bytes) return USPACE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < n_params; ++i) {
-        const PDesc& d = m.p[i];
-        if (!params[i]) return USPACE_ERR_ARG;
-        char* dst = (char*)blob + d.offset;
-        switch (d.kind) {
-            case P_F32:
-                if (hipMemcpyAsync(dst, params[i], d.bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return USPACE_ERR_LAUNCH;
-                break;
-            case P_CONV1_BF16:
-                US_TRY(uspace_cast_f32_bf16(params[i], (uint16_t*)dst, d.numel, stream));
-                break;
-            case P_CONV3_BF16:
-                hipLaunchKernelGGL(repack_conv3_bf16_kernel, dim3(grid_for(d.numel)), dim3(256), 0, s, params[i], (bf16_t*)dst, d.co, d.ci);
-                US_CHECK_LAUNCH();
-                break;
-            case P_CONV3_F32T:
-                hipLaunchKernelGGL(repack_conv3_f32_kernel, dim3(grid_for(d.numel)), dim3(256), 0, s, params[i], (float*)dst, d.co, d.ci);
-                US_CHECK_LAUNCH();
-                break;
-        }
-    }
-    return USPACE_OK;
+    return pack_params(build_vae(*cfg), params, n_params, blob, blob_bytes, stream);
 }
 
 static int vae_decode_impl(const uspace_vae_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
@@ -536,63 +904,21 @@ static int vae_decode_impl(const uspace_vae_config* cfg, const void* blob, void*
     const VaeModel m = build_vae(c);
     const VaeWs w = plan_vae_ws(c, m, B);
     if (workspace_bytes < w.total) return USPACE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const char* wb = (const char*)blob;
-    char* ws = (char*)workspace;
-    auto PF = [&](int i) { return (const float*)(wb + m.p[i].offset); };
-    auto PH = [&](int i) { return (const uint16_t*)(wb + m.p[i].offset); };
-    constexpr int B_ = USPACE_EPI_BIAS, R_ = USPACE_EPI_RESIDUAL, F_ = USPACE_EPI_OUT_F32, H_ = USPACE_EPI_OUT_BF16;
-    float* stats = (float*)(ws + w.stats);
+    VaeRun r(m, w, blob, workspace, B, stream);
+    hipStream_t s = r.s;
 
     int stage = 0, cur_c = m.c_top;
     int H = m.z_res;   // current resolution (square)
-    auto rows_of = [&](int h) { return (long)B * (h + 2) * (h + 2); };
-    auto guard = [&](int h) { return (long)(h + 3); };
-    // map pointers (row 0 sits `guard` rows into the buffer); A = current fp32 map, Bf = scratch fp32 map
-    auto fmap = [&](size_t off, int h, int C) { return (float*)(ws + off) + guard(h) * C; };
-    auto hmap = [&](size_t off, int h, int C) { return (uint16_t*)(ws + off) + guard(h) * C; };
-    size_t cur_off = w.fa, tmp_off = w.fb;
-
-    auto group_norm = [&](const float* x, int h, int C, int gw, int gb, bool silu, uint16_t* y) -> int {
-        return uspace_groupnorm_map_bf16(x, PF(gw), PF(gb), y, stats, B, h, C, silu ? 1 : 0, 1e-6f, stream);
-    };
-    auto conv3 = [&](const uint16_t* a, int h, int Cin, int Cout, int wi, int bi, const float* resid, float* o) -> int {
-        const int P = h + 2;
-        int shifts[9];
-        for (int t = 0; t < 9; ++t) shifts[t] = (t / 3 - 1) * P + (t % 3 - 1);
-        return uspace_gemm_slabs_bf16(a, Cin, PH(wi), 9 * Cin, (int)rows_of(h), Cout, Cin, 9, shifts,
-                                      resid ? (B_ | R_ | F_) : (B_ | F_), PF(bi), resid, Cout, o, Cout, nullptr, 0, stream);
-    };
-    auto resblock = [&](const ResIdx& r, int h) -> int {
-        float* x = fmap(cur_off, h, r.cin);
-        uint16_t* hb = hmap(w.hb, h, r.cin > r.cout ? r.cin : r.cout);
-        US_TRY(group_norm(x, h, r.cin, r.n1w, r.n1b, true, hb));
-        float* t1 = fmap(tmp_off, h, r.cout);
-        US_TRY(conv3(hb, h, r.cin, r.cout, r.c1w, r.c1b, nullptr, t1));
-        US_TRY(group_norm(t1, h, r.cout, r.n2w, r.n2b, true, hb));
-        if (r.cin != r.cout) {
-            // nin_shortcut (1x1) on x, written over t1 (already consumed by norm2), then conv2 accumulates onto it
-            uint16_t* xb = hmap(w.xb, h, r.cin);
-            US_TRY(uspace_cast_f32_bf16(x, xb, rows_of(h) * r.cin, stream));
-            US_TRY(uspace_gemm_bf16(xb, r.cin, nullptr, 0, r.cin, PH(r.sw), r.cin, (int)rows_of(h), r.cout, r.cin, B_ | F_,
-                                    PF(r.sb), nullptr, 0, t1, r.cout, nullptr, 0, stream));
-            US_TRY(conv3(hb, h, r.cout, r.cout, r.c2w, r.c2b, t1, t1));
-            std::swap(cur_off, tmp_off);
-        } else {
-            US_TRY(conv3(hb, h, r.cout, r.cout, r.c2w, r.c2b, x, x));   // x += conv2(...)
-        }
-        return USPACE_OK;
-    };
 
     // ---- z/scale -> post_quant_conv -> conv_in
-    hipLaunchKernelGGL(vae_conv_in_kernel, dim3(B * H * H), dim3(128), 0, s, z, 1.0f / scale_factor, PF(m.pq_w), PF(m.pq_b),
-                       PF(m.conv_in_w), PF(m.conv_in_b), fmap(cur_off, H, m.c_top), H, H, m.c_top);
+    hipLaunchKernelGGL(vae_conv_in_kernel, dim3(B * H * H), dim3(128), 0, s, z, 1.0f / scale_factor, r.PF(m.pq_w), r.PF(m.pq_b),
+                       r.PF(m.conv_in_w), r.PF(m.conv_in_b), r.fmap(r.cur_off, H, m.c_top), H, H, m.c_top);
     US_CHECK_LAUNCH();
 #define VAE_STAGE_DONE(CH)                                                                              \
     do {                                                                                                 \
         cur_c = (CH);                                                                                    \
         if (stage++ == stop_after && dump) {                                                             \
-            if (hipMemcpyAsync(dump, fmap(cur_off, H, cur_c), (size_t)rows_of(H) * cur_c * 4,             \
+            if (hipMemcpyAsync(dump, r.fmap(r.cur_off, H, cur_c), (size_t)r.rows_of(H) * cur_c * 4,       \
                                hipMemcpyDeviceToDevice, s) != hipSuccess) return USPACE_ERR_LAUNCH;       \
             dump_hc[0] = H; dump_hc[1] = cur_c;                                                          \
             return USPACE_OK;                                                                            \
@@ -600,73 +926,42 @@ static int vae_decode_impl(const uspace_vae_config* cfg, const void* blob, void*
     } while (0)
     VAE_STAGE_DONE(m.c_top);
     // ---- mid: ResnetBlock, AttnBlock, ResnetBlock
-    US_TRY(resblock(m.mid1, H));
+    US_TRY(r.resblock(m.mid1, H));
     VAE_STAGE_DONE(m.c_top);
-    {
-        const int Cc = m.c_top, HW = H * H;
-        const long T = (long)B * HW;
-        float* x = fmap(cur_off, H, Cc);
-        uint16_t* hb = hmap(w.hb, H, Cc);
-        US_TRY(group_norm(x, H, Cc, m.an_w, m.an_b, false, hb));
-        uint16_t* tok = (uint16_t*)(ws + w.tok);
-        hipLaunchKernelGGL(gather_interior_kernel, dim3(grid_for(T * (Cc / 8))), dim3(256), 0, s, hb, tok, B, H, H, Cc);
-        US_CHECK_LAUNCH();
-        uint16_t *q = (uint16_t*)(ws + w.q), *k = (uint16_t*)(ws + w.k), *v = (uint16_t*)(ws + w.v);
-        uint16_t *vt = (uint16_t*)(ws + w.vt), *pr = (uint16_t*)(ws + w.pr), *o = (uint16_t*)(ws + w.o);
-        float* sc = (float*)(ws + w.s);
-        float* po = (float*)(ws + w.po);
-        US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(m.q_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(m.q_b), nullptr, 0, nullptr, 0, q, Cc, stream));
-        US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(m.k_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(m.k_b), nullptr, 0, nullptr, 0, k, Cc, stream));
-        US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(m.v_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(m.v_b), nullptr, 0, nullptr, 0, v, Cc, stream));
-        hipLaunchKernelGGL(transpose_kernel, dim3(us_cdiv(Cc, 32), us_cdiv(HW, 32), B), dim3(256), 0, s, v, vt, HW, Cc);
-        US_CHECK_LAUNCH();
-        const float scale = 1.0f / sqrtf((float)Cc);
-        for (int b = 0; b < B; ++b) {
-            // w_ = softmax(q k^T * c^-0.5) over keys; h_ = w_ v   (libs/autoencoder.py:179-191)
-            US_TRY(uspace_gemm_bf16(q + (size_t)b * HW * Cc, Cc, nullptr, 0, Cc, k + (size_t)b * HW * Cc, Cc, HW, HW, Cc, F_,
-                                    nullptr, nullptr, 0, sc, HW, nullptr, 0, stream));
-            hipLaunchKernelGGL(softmax_rows_kernel, dim3(us_cdiv(HW, 4)), dim3(256), 0, s, sc, pr, (long)HW, HW, scale);
-            US_CHECK_LAUNCH();
-            US_TRY(uspace_gemm_bf16(pr, HW, nullptr, 0, HW, vt + (size_t)b * HW * Cc, HW, HW, Cc, HW, H_, nullptr, nullptr, 0,
-                                    nullptr, 0, o + (size_t)b * HW * Cc, Cc, stream));
-        }
-        US_TRY(uspace_gemm_bf16(o, Cc, nullptr, 0, Cc, PH(m.po_w), Cc, (int)T, Cc, Cc, B_ | F_, PF(m.po_b), nullptr, 0, po, Cc, nullptr, 0, stream));
-        hipLaunchKernelGGL(scatter_add_kernel, dim3(grid_for(T * (Cc / 4))), dim3(256), 0, s, x, po, B, H, H, Cc);
-        US_CHECK_LAUNCH();
-    }
+    US_TRY(r.mid_attn(m.attn, H, m.c_top));
     VAE_STAGE_DONE(m.c_top);
-    US_TRY(resblock(m.mid2, H));
+    US_TRY(r.resblock(m.mid2, H));
     VAE_STAGE_DONE(m.c_top);
     // ---- up path, highest level first
     for (int lvl = c.n_levels - 1; lvl >= 0; --lvl) {
-        for (const ResIdx& r : m.up[lvl]) {
-            US_TRY(resblock(r, H));
-            VAE_STAGE_DONE(r.cout);
+        for (const ResIdx& rb : m.up[lvl]) {
+            US_TRY(r.resblock(rb, H));
+            VAE_STAGE_DONE(rb.cout);
         }
         if (lvl != 0) {
             const int Cc = c.ch * c.ch_mult[lvl];
-            float* x = fmap(cur_off, H, Cc);
-            uint16_t* hb = hmap(w.hb, 2 * H, Cc);
-            hipLaunchKernelGGL(upsample_kernel, dim3(grid_for(rows_of(2 * H) * (Cc / 4))), dim3(256), 0, s, x, hb, B, H, H, Cc);
+            float* x = r.fmap(r.cur_off, H, Cc);
+            uint16_t* hb = r.hmap(w.hb, 2 * H, Cc);
+            hipLaunchKernelGGL(upsample_kernel, dim3(grid_for(r.rows_of(2 * H) * (Cc / 4))), dim3(256), 0, s, x, hb, B, H, H, Cc);
             US_CHECK_LAUNCH();
             H *= 2;
-            float* y = fmap(tmp_off, H, Cc);
-            US_TRY(conv3(hb, H, Cc, Cc, m.us_w[lvl], m.us_b[lvl], nullptr, y));
-            std::swap(cur_off, tmp_off);
+            float* y = r.fmap(r.tmp_off, H, Cc);
+            US_TRY(r.conv3(hb, H, Cc, Cc, m.us_w[lvl], m.us_b[lvl], nullptr, y));
+            std::swap(r.cur_off, r.tmp_off);
             VAE_STAGE_DONE(Cc);
         }
     }
     // ---- norm_out + SiLU + conv_out -> NCHW image
     {
         const int Cc = c.ch * c.ch_mult[0];
-        float* x = fmap(cur_off, H, Cc);
-        uint16_t* hb = hmap(w.hb, H, Cc);
-        US_TRY(group_norm(x, H, Cc, m.no_w, m.no_b, true, hb));
+        float* x = r.fmap(r.cur_off, H, Cc);
+        uint16_t* hb = r.hmap(w.hb, H, Cc);
+        US_TRY(r.group_norm(x, H, Cc, m.no_w, m.no_b, true, hb));
         const long npix = (long)B * H * H;
         // 2 waves/SIMD at ~240 VGPRs: 512 workgroups fill the chip once and amortise the per-thread weight load
         const dim3 grid((unsigned)std::min<long>((npix * (Cc / 8) + 255) / 256, 512));
 #define US_CONV_OUT(LPP)                                                                                              \
-    hipLaunchKernelGGL(vae_conv_out_kernel<LPP>, grid, dim3(256), 0, s, (const bf16_t*)hb, PF(m.co_w), PF(m.co_b), out, B, H, H)
+    hipLaunchKernelGGL(vae_conv_out_kernel<LPP>, grid, dim3(256), 0, s, (const bf16_t*)hb, r.PF(m.co_w), r.PF(m.co_b), out, B, H, H)
         switch (Cc) {
             case 64:  US_CONV_OUT(8); break;
             case 128: US_CONV_OUT(16); break;
@@ -697,4 +992,126 @@ extern "C" int uspace_vae_decode_tap(const uspace_vae_config* cfg, const void* b
     (void)dummy_out;
     return vae_decode_impl(cfg, blob, workspace, workspace_bytes, z, scale_factor, dump /*unused unless the tap is past the end*/,
                            B, stream, stop_after, dump, hc_out);
+}
+
+// ------------------------------------------------------------------------------------------ encoder
+extern "C" int uspace_vae_enc_num_params(const uspace_vae_config* cfg) {
+    if (!valid_enc(cfg)) return USPACE_ERR_ARG;
+    return (int)build_enc(*cfg).p.size();
+}
+
+extern "C" long uspace_vae_enc_param_numel(const uspace_vae_config* cfg, int index) {
+    if (!valid_enc(cfg)) return USPACE_ERR_ARG;
+    const EncModel m = build_enc(*cfg);
+    if (index < 0 || index >= (int)m.p.size()) return USPACE_ERR_ARG;
+    return m.p[index].numel;
+}
+
+extern "C" size_t uspace_vae_enc_weight_bytes(const uspace_vae_config* cfg) {
+    return valid_enc(cfg) ? build_enc(*cfg).blob_bytes : 0;
+}
+
+extern "C" size_t uspace_vae_enc_workspace_bytes(const uspace_vae_config* cfg, int B) {
+    if (!valid_enc(cfg) || B <= 0) return 0;
+    const EncModel m = build_enc(*cfg);
+    return plan_enc_ws(*cfg, m, B).total;
+}
+
+extern "C" int uspace_vae_enc_pack_weights(const uspace_vae_config* cfg, const float* const* params, int n_params,
+                                           void* blob, size_t blob_bytes, uspace_stream_t stream) {
+    if (!valid_enc(cfg) || !params || !blob) return USPACE_ERR_ARG;
+    return pack_params(build_enc(*cfg), params, n_params, blob, blob_bytes, stream);
+}
+
+static int vae_encode_impl(const uspace_vae_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                           const float* img, float* moments, int B, uspace_stream_t stream, int stop_after, float* dump,
+                           int* dump_hc) {
+    if (!valid_enc(cfg) || !blob || !workspace || !img || B <= 0 || (!moments && !dump)) return USPACE_ERR_ARG;
+    const uspace_vae_config& c = *cfg;
+    const EncModel m = build_enc(c);
+    // 32-bit element offsets (GEMM operands, GroupNorm rows): every map of the chunk stays below 2^30 elements
+    {
+        int res = c.resolution, chan = c.ch;
+        for (int lvl = 0; lvl < c.n_levels; ++lvl) {
+            const int bo = c.ch * c.ch_mult[lvl];
+            if ((long)B * (res + 2) * (res + 2) * std::max(chan, bo) >= (1L << 30)) return USPACE_ERR_ARG;
+            chan = bo;
+            if (lvl != c.n_levels - 1) res /= 2;
+        }
+    }
+    const VaeWs w = plan_enc_ws(c, m, B);
+    if (workspace_bytes < w.total) return USPACE_ERR_WORKSPACE;
+    VaeRun r(m, w, blob, workspace, B, stream);
+    hipStream_t s = r.s;
+
+    int stage = 0, cur_c = c.ch;
+    int H = c.resolution;
+
+    // ---- conv_in on the NCHW images
+    {
+        const long items = (long)B * H * H * (c.ch / 4);
+        hipLaunchKernelGGL(vae_enc_conv_in_kernel, dim3(grid_for(items, 2048)), dim3(256), 0, s, img, r.PF(m.conv_in_w),
+                           r.PF(m.conv_in_b), r.fmap(r.cur_off, H, c.ch), B, H, c.ch);
+        US_CHECK_LAUNCH();
+    }
+    VAE_STAGE_DONE(c.ch);
+    // ---- down path
+    for (int lvl = 0; lvl < c.n_levels; ++lvl) {
+        for (const ResIdx& rb : m.down[lvl]) {
+            US_TRY(r.resblock(rb, H));
+            VAE_STAGE_DONE(rb.cout);
+        }
+        if (lvl != c.n_levels - 1) {
+            US_TRY(r.downsample(m.ds_w[lvl], m.ds_b[lvl], H, cur_c));
+            H /= 2;
+            VAE_STAGE_DONE(cur_c);
+        }
+    }
+    // ---- mid: ResnetBlock, AttnBlock, ResnetBlock
+    US_TRY(r.resblock(m.mid1, H));
+    VAE_STAGE_DONE(m.c_top);
+    US_TRY(r.mid_attn(m.attn, H, m.c_top));
+    VAE_STAGE_DONE(m.c_top);
+    US_TRY(r.resblock(m.mid2, H));
+    VAE_STAGE_DONE(m.c_top);
+    if (!moments) return USPACE_ERR_ARG;   // a tap past the last stage
+    // ---- norm_out + SiLU + conv_out + quant_conv -> NCHW moments
+    {
+        const int Cc = m.c_top;
+        uint16_t* hb = r.hmap(w.hb, H, Cc);
+        US_TRY(r.group_norm(r.fmap(r.cur_off, H, Cc), H, Cc, m.no_w, m.no_b, true, hb));
+        const long items = (long)B * H * ((H + 3) / 4) * (Cc / 8);
+        hipLaunchKernelGGL(vae_enc_conv_out_kernel, dim3(grid_for(items, 1024)), dim3(256), 0, s, (const bf16_t*)hb,
+                           r.PF(m.co_w), r.PF(m.co_b), r.PF(m.qc_w), r.PF(m.qc_b), moments, B, H, H, Cc);
+        US_CHECK_LAUNCH();
+    }
+    return USPACE_OK;
+}
+#undef VAE_STAGE_DONE
+
+extern "C" int uspace_vae_encode_moments(const uspace_vae_config* cfg, const void* blob, void* workspace,
+                                         size_t workspace_bytes, const float* img, float* moments, int B,
+                                         uspace_stream_t stream) {
+    if (!moments) return USPACE_ERR_ARG;
+    return vae_encode_impl(cfg, blob, workspace, workspace_bytes, img, moments, B, stream, -1, nullptr, nullptr);
+}
+
+// Test aid: run the encode up to (and including) stage `stop_after` -- 0 conv_in, then one per res block / downsample of
+// the down path in execution order, then mid.block_1, mid.attn_1, mid.block_2 -- and copy that stage's fp32
+// zero-bordered NHWC map ([B, H+2, H+2, C]) to `dump`; hc_out (host) receives {H, C}.
+extern "C" int uspace_vae_encode_tap(const uspace_vae_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                     const float* img, int B, int stop_after, float* dump, int* hc_out,
+                                     uspace_stream_t stream) {
+    if (!dump || !hc_out || stop_after < 0) return USPACE_ERR_ARG;
+    hc_out[0] = hc_out[1] = 0;
+    return vae_encode_impl(cfg, blob, workspace, workspace_bytes, img, nullptr, B, stream, stop_after, dump, hc_out);
+}
+
+extern "C" int uspace_vae_sample(const float* moments, const float* noise, float scale, float* z, int B, int h,
+                                 uspace_stream_t stream) {
+    if (!moments || !noise || !z || B <= 0 || h <= 0) return USPACE_ERR_ARG;
+    hipLaunchKernelGGL(vae_sample_kernel, dim3(grid_for((long)B * 4 * h * h)), dim3(256), 0, (hipStream_t)stream, moments,
+                       noise, scale, z, B, h * h);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
 }
