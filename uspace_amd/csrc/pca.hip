@@ -5,7 +5,7 @@
 // (v_mfma_f64_16x16x4_f64): products of fp32 data are exact in fp64 and the accumulation does not square the data's
 // rounding error into the small eigenvalues, which an fp32 (or split-bf16) Gram matrix would.  Only the N x N symmetric
 // eigen-decomposition is left to a library (uspace_amd/tools/utils_pca.py).
-//   uspace_center_cols_f32 : xc = x - column mean                                   (HBM-bound)
+//   uspace_center_cols_f32 : xc = x - column mean (fp64 mean, one rounding)         (HBM-bound)
 //   uspace_gram_f64        : G = xc . xc^T, fp64 [N, N]                              (2 N^2 F flop)
 //   uspace_project_rows_f64: out[n, F] = Ut[n, N] . xc[N, F]  (sigma_i v_i), fp32     (2 n N F flop)
 //   uspace_normalize_rows_signed : unit rows, largest-magnitude entry positive (sklearn's svd_flip convention)
@@ -24,11 +24,14 @@ __global__ __launch_bounds__(256) void center_cols_kernel(const float* __restric
         const f32x4 v = *(const f32x4*)(x + (size_t)r * F + c);
         s0 += v[0]; s1 += v[1]; s2 += v[2]; s3 += v[3];
     }
+    // the mean stays in fp64: x - fp32(mean) would add half an ulp of the mean (1e3 and more for offset columns) to
+    // every centred value; this way xc is x - mean rounded once
     const double inv = 1.0 / N;
-    const f32x4 m = {(float)(s0 * inv), (float)(s1 * inv), (float)(s2 * inv), (float)(s3 * inv)};
+    s0 *= inv; s1 *= inv; s2 *= inv; s3 *= inv;
     for (int r = 0; r < N; ++r) {
         const f32x4 v = *(const f32x4*)(x + (size_t)r * F + c);
-        *(f32x4*)(xc + (size_t)r * F + c) = v - m;
+        const f32x4 d = {(float)(v[0] - s0), (float)(v[1] - s1), (float)(v[2] - s2), (float)(v[3] - s3)};
+        *(f32x4*)(xc + (size_t)r * F + c) = d;
     }
 }
 
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(256) void project_rows_kernel(const double* __restr
 __global__ __launch_bounds__(1024) void normalize_rows_kernel(float* __restrict__ v, long F) {
     __shared__ double s_sum[16];
     __shared__ float s_max[16], s_val[16];
+    __shared__ long s_idx[16];
     float* row = v + (size_t)blockIdx.x * F;
     double sum = 0.0;
     float best = -1.f, bval = 0.f;
@@ -163,13 +167,14 @@ __global__ __launch_bounds__(1024) void normalize_rows_kernel(float* __restrict_
         if (ob > best || (ob == best && oi < bidx)) { best = ob; bval = ov; bidx = oi; }
     }
     const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_sum[wave] = sum; s_max[wave] = best; s_val[wave] = bval; }
+    if ((threadIdx.x & 63) == 0) { s_sum[wave] = sum; s_max[wave] = best; s_val[wave] = bval; s_idx[wave] = bidx; }
     __syncthreads();
     double tot = 0.0;
     float mb = -1.f, mv = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {      // waves cover increasing index ranges only per stride: ties across
-        tot += s_sum[w];                                    // waves are resolved towards the lower wave, a fixed order
-        if (s_max[w] > mb) { mb = s_max[w]; mv = s_val[w]; }
+    long mi = F;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {      // thread t owns indices t, t + 1024, ...: a lower wave does not
+        tot += s_sum[w];                                    // hold the lower index, so ties across waves compare the indices
+        if (s_max[w] > mb || (s_max[w] == mb && s_idx[w] < mi)) { mb = s_max[w]; mv = s_val[w]; mi = s_idx[w]; }
     }
     const float scale = (float)((mv < 0.f ? -1.0 : 1.0) / sqrt(tot > 1e-60 ? tot : 1e-60));
     for (long i = threadIdx.x; i < F; i += blockDim.x) row[i] *= scale;
