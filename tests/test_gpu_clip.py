@@ -43,10 +43,10 @@ def test_tiny_text_transformer_matches_hf_golden(golden_dir):
         assert rel_l2(h, z[f"hidden/{k}"]) < (1e-6 if k == 0 else 6e-3), k
     assert torch.equal(m(ids), out)                               # deterministic
     # shorter prompts (L < 77) and one row at a time give the same rows (causal: a prefix does not see its suffix)
-    short = m(ids[:, :33].contiguous())
-    assert rel_l2(short.cpu().numpy(), out[:, :33].cpu().numpy()) < 2e-3
-    one = m(ids[1:2].contiguous())
-    assert rel_l2(one.cpu().numpy(), out[1:2].cpu().numpy()) < 2e-3
+    # (bit-equal: every GEMM form walks K in the same order and splits none, the row kernels work per row and masked keys get P = 0
+    # exactly -- tests/test_gpu_clip_parity.py checks this at the CLIP-L shape)
+    assert torch.equal(m(ids[:, :33].contiguous()), out[:, :33])
+    assert torch.equal(m(ids[1:2].contiguous()), out[1:2])
     with pytest.raises(IndexError):
         m(torch.full((1, 5), 1000, device="cuda"))
     with pytest.raises(ValueError):
@@ -66,7 +66,7 @@ def test_causal_attention_matches_oracle(hip, B, L, H):
     assert rc == 0
     got = out.float().cpu().numpy()
     assert rel_l2(got, ref) < 8e-3
-    assert np.abs(got[:, 0] - q32[:, 0, 2 * D:]).max() < 2e-2      # the first token attends only to itself: out = v_0
+    assert torch.equal(out[:, 0], qb[:, 0, 2 * D:])                # the first token attends only to itself: P = 1, out = v_0 exactly
     assert hip.lib().uspace_attention_causal_bf16(hip.ptr(qb), hip.ptr(out), B, 161, H, hip.stream_ptr()) != 0
 
 
@@ -127,7 +127,7 @@ def test_frozen_clip_embedder_surface(golden_dir):
     emb = FrozenCLIPEmbedder(tokenizer=_WordTokenizer(), transformer=m, device="cuda")
     ctx = emb.encode(["a photo of a cat", "two dogs are running on the grass"])
     assert ctx.shape == (2, 77, 128) and bool(torch.isfinite(ctx).all())
-    assert torch.equal(emb(["a photo of a cat"]), ctx[:1]) or rel_l2(emb(["a photo of a cat"]).cpu().numpy(), ctx[:1].cpu().numpy()) < 2e-3
+    assert torch.equal(emb(["a photo of a cat"]), ctx[:1])
     assert not any(p.requires_grad for p in emb.parameters())
     assert emb.get_word_inds("two dogs are running", "dogs").tolist() == [2]       # 1-based: <bos> is position 0
     assert emb.get_word_inds("two dogs are running", 3).tolist() == [4]
@@ -146,4 +146,4 @@ def test_clip_large_shape_runs():
     ids = torch.randint(0, 49408, (4, 77), device="cuda")
     out = m(ids)
     assert out.shape == (4, 77, 768) and bool(torch.isfinite(out).all()) and 0.5 < float(out.std()) < 2.0
-    assert rel_l2(m(ids[2:3].contiguous()).cpu().numpy(), out[2:3].cpu().numpy()) < 2e-3
+    assert torch.equal(m(ids[2:3].contiguous()), out[2:3])

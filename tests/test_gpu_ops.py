@@ -139,7 +139,7 @@ def test_gemm_rejects_bad_shapes(hip):
         hip.gemm(A, W, out_f32=out)
 
 
-@pytest.mark.parametrize("M,D", [(5, 64), (1031, 512), (777, 1024), (9, 2048)])
+@pytest.mark.parametrize("M,D", [(5, 64), (1031, 512), (777, 1024), (9, 2048), (77, 768), (4928, 768)])   # D = 768: CLIP-L, NV = 4 with its last quarter masked
 def test_layernorm(hip, M, D):
     rng = np.random.default_rng(D + M)
     x = _rand(rng, M, D, scale=3.0) + 0.7
