@@ -302,6 +302,14 @@ typedef struct uspace_uvit_io {
 USPACE_API int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* blob, void* workspace,
                         size_t workspace_bytes, const uspace_uvit_io* io, int B, uspace_stream_t stream);
 
+/* Test aid: run the forward exactly as uspace_uvit_forward does up to the end of stage `stop_after`, then copy the fp32 residual
+ * stream x [B,L,D] to `dump` (device) and return.  Stages: 0 the tokens after embed + pos_embed, as block 0 reads them; k = 1 ..
+ * depth+1 x after block k-1 (in_blocks, then mid_block at k = depth/2 + 1, then out_blocks).  For the mid block that is the value
+ * after the mid hook's add (what the next block reads; io->mid_tap still receives the value before it).  At stop_after = depth+1
+ * the head runs as well and io->out receives the forward's output. */
+USPACE_API int uspace_uvit_forward_tap(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                       const uspace_uvit_io* io, int B, int stop_after, float* dump, uspace_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * VAE decode (the step after the solve): FrozenAutoencoderKL.decode of libs/autoencoder.py:446-450 =
  * z / scale_factor -> post_quant_conv -> Decoder.forward (libs/autoencoder.py:376-409).

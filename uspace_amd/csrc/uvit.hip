@@ -249,9 +249,14 @@ extern "C" int uspace_uvit_set_ln_fold(int mode) {
 
 extern "C" int uspace_uvit_get_ln_fold(void) { return g_ln_fold.load(); }
 
-extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* blob, void* workspace,
-                                   size_t workspace_bytes, const uspace_uvit_io* io, int B, uspace_stream_t stream) {
+namespace {
+// The forward; stop_after >= 0 (uspace_uvit_forward_tap) copies the residual stream x to `dump` after stage stop_after and
+// returns there (the last stage, depth + 1, runs the head first).  stop_after = -1 is the product forward: the launch sequence
+// is the same for every stop_after up to the stop.
+int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes, const uspace_uvit_io* io,
+                 int B, int stop_after, float* dump, uspace_stream_t stream) {
     if (!valid_cfg(cfg) || !blob || !workspace || !io || B <= 0) return USPACE_ERR_ARG;
+    if (stop_after >= 0 && (!dump || stop_after > cfg->depth + 1)) return USPACE_ERR_ARG;
     if (!io->x || !io->t || !io->out) return USPACE_ERR_ARG;
     if (cfg->n_extra > 0 && !io->context) return USPACE_ERR_ARG;
     const uspace_uvit_config& c = *cfg;
@@ -323,6 +328,10 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
     }
     US_TRY(uspace_embed_tokens(io->x, io->t, io->t_stride, extra, c.n_extra, c.time_first, PF(m.pw), PF(m.pb),
                                PF(m.pos), x, nullptr, B, c.in_chans, c.img_size, c.patch_size, D, stream));
+    auto tap = [&]() {
+        return hipMemcpyAsync(dump, x, MD * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? USPACE_OK : USPACE_ERR_LAUNCH;
+    };
+    if (stop_after == 0) return tap();
 
     const int half = c.depth / 2;
     if (fold) {
@@ -404,6 +413,7 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
                 if (io->mid_delta)
                     US_TRY(uspace_add_broadcast_rows(x, xb, io->mid_delta, io->mid_scale, io->mid_row_scale, B, (long)L * D, stream));
             }
+            if (i + 1 == stop_after && !is_last) return tap();
         }
     } else {
     for (int i = 0; i < m.nblocks; ++i) {
@@ -439,6 +449,7 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
             if (io->mid_delta)  // u-space write hook at the mid block (libs/uvit.py:336, libs/dissection.py:157)
                 US_TRY(uspace_add_broadcast_rows(x, xb, io->mid_delta, io->mid_scale, io->mid_row_scale, B, (long)L * D, stream));
         }
+        if (i + 1 == stop_after && !is_last) return tap();
     }
     }
     if (m.head_img >= 0)     // decoder weights with the last LayerNorm folded in, prepared by uspace_uvit_pack_weights
@@ -447,7 +458,20 @@ extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
     else
         US_TRY(uspace_output_head(x, L, m.extras, PF(m.ng), PF(m.nb), PF(m.dw), PF(m.db), PF(m.convw), PF(m.convb),
                                   (float*)(ws + w.head), io->out, B, c.in_chans, c.img_size, c.patch_size, D, 1e-5f, stream));
+    if (stop_after == m.nblocks) return tap();
     return USPACE_OK;
+}
+}  // namespace
+
+extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* blob, void* workspace,
+                                   size_t workspace_bytes, const uspace_uvit_io* io, int B, uspace_stream_t stream) {
+    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, -1, nullptr, stream);
+}
+
+extern "C" int uspace_uvit_forward_tap(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                       const uspace_uvit_io* io, int B, int stop_after, float* dump, uspace_stream_t stream) {
+    if (stop_after < 0) return USPACE_ERR_ARG;
+    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, stop_after, dump, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -320,6 +320,32 @@ class UViTBase(nn.Module):
                                                   ctypes.byref(io), B, _hip.stream_ptr()), "uspace_uvit_forward")
         return out if (keep_f32 or x.dtype == torch.float32) else out.to(x.dtype)
 
+    def _tap(self, stage, x, timesteps, context=None, mid_delta=None, mid_scale=0.0, mid_tap=None, key_scale=None,
+             mid_row_scale=None, out=None, workspace=None):
+        """Test aid (uspace_uvit_forward_tap): the fp32 residual stream [B, L, D] after ``stage`` (0: the tokens block 0 reads;
+        k = 1 .. depth + 1: after block k - 1, the mid block's after its hook's add) of the forward ``_run`` would run on the same
+        arguments.  At stage depth + 1 the head runs too and writes ``out`` ([B, C, S, S] fp32) if given.  ``workspace``: a uint8
+        tensor of at least ``uspace_uvit_workspace_bytes(B)`` bytes to run in instead of the module's own."""
+        _hip.require_device(x, "x")
+        B = x.shape[0]
+        dev = x.device
+        xin = x.detach().to(torch.float32).contiguous()
+        t = torch.as_tensor(timesteps, dtype=torch.float32, device=dev).detach()
+        t_stride = 0 if t.dim() == 0 else 1
+        t = t.contiguous()
+        if out is None:
+            out = torch.empty(B, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev)
+        dump = torch.empty(B, self.seq_len, self.embed_dim, dtype=torch.float32, device=dev)
+        blob = self._packed_blob(dev)
+        ws = self._workspace_for(B, dev) if workspace is None else workspace
+        io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta),
+                         float(mid_scale), _hip.ptr(mid_tap), _hip.ptr(key_scale), _hip.ptr(out),
+                         _hip.ptr(mid_row_scale))
+        _hip.check(_hip.lib().uspace_uvit_forward_tap(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
+                                                      ctypes.byref(io), B, int(stage), _hip.ptr(dump), _hip.stream_ptr()),
+                   "uspace_uvit_forward_tap")
+        return dump
+
 
 class _GraphEntry:
     """Static buffers + instantiated hipGraph of one (batch size, weights) combination."""
