@@ -244,6 +244,9 @@ USPACE_API int uspace_ode_combine(float* out, const float* y, const float* const
 /* Scaled RMS error norm of an embedded Runge-Kutta step:
  *   result[0] = sqrt(mean((err / (atol + rtol * max(|y0|, |y1|)))^2)),  err = sum_i coef[i]*k[i];
  *   result[1] = the sum of squares itself (a batch sharded over GPUs all-reduces these sums, not the norms).
+ * A non-finite y0[i] or y1[i] makes that element's ratio NaN (max() would drop a NaN and an Inf would make the ratio 0),
+ * so a step whose state is no longer finite yields a non-finite result[0] and result[1], never an accepted step; a
+ * non-finite k[i] reaches err itself.  Finite inputs take the plain arithmetic above.
  * result is a device float[2]; scratch a device float[>=1024]. */
 USPACE_API int uspace_ode_error_norm(const float* y0, const float* y1, const float* const* k, const float* coef,
                           int n_k, float rtol, float atol, long n, float* scratch, float* result,

@@ -117,18 +117,31 @@ def solve(f, y0, t0, t1, method="dopri5", rtol=1e-5, atol=1e-5, step_size=None, 
 
     scale0 = np.float32(atol) + np.float32(rtol) * np.abs(y)
     d0, d1 = _rms(y / scale0), _rms(f0 / scale0)
+    if not (math.isfinite(d0) and math.isfinite(d1)):
+        raise RuntimeError(f"non-finite values in state `y` or its derivative: initial-step norms {d0}, {d1}")
     h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
     f1 = g(t0 + h0, _lin(y, [f0], [h0]))
     d2 = _rms((f1 - f0) / scale0) / h0
+    if not math.isfinite(d2):
+        raise RuntimeError(f"non-finite values in state `y` or its derivative: initial-step probe norm {d2}")
     h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else (0.01 / max(d1, d2)) ** (1.0 / order)   # torchdiffeq passes order - 1 to its heuristic
     h = min(100 * h0, h1)
     t = t0
     counters["accepted"] = counters["rejected"] = 0
     while True:
+        # torchdiffeq's _adaptive_step guards: dt must move t, the state must stay finite (here: a non-finite y or y1 makes
+        # the ratio NaN -- np.maximum keeps a NaN, an Inf would give tol = Inf and a ratio of 0)
+        if not t + h > t:
+            raise RuntimeError(f"underflow in dt {h}")
         y1, ks = attempt(t, h, y, f0)
         err = _lin(np.zeros_like(y), ks, [h * c for c in err_c])
         tol = np.float32(atol) + np.float32(rtol) * np.maximum(np.abs(y), np.abs(y1))
-        ratio = _rms(err / tol)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            ratio = _rms(err / tol)
+        if not (np.isfinite(y).all() and np.isfinite(y1).all()):
+            ratio = float("nan")
+        if not math.isfinite(ratio):
+            raise RuntimeError(f"non-finite values in state `y`: error ratio {ratio} at t={-t if flip else t}, dt={h}")
         if ratio == 0.0:
             h_next = h * 10.0
         else:
@@ -136,6 +149,8 @@ def solve(f, y0, t0, t1, method="dopri5", rtol=1e-5, atol=1e-5, step_size=None, 
             h_next = h * min(10.0, max(0.9 / ratio ** (1.0 / order), lo))
         if ratio <= 1.0:
             counters["accepted"] += 1
+            if "t_accepted" in counters:                       # opt-in record of the accepted grid (true time)
+                counters["t_accepted"].append(-(t + h) if flip else t + h)
             if t + h >= t1:
                 if t + h == t1:
                     return y1

@@ -28,6 +28,10 @@ What is pinned:
                                     uncond write_attr (tail / head) over 100 Euler steps, tiny T2I p2p_rescale encode -> decode, and the
                                     50-step Euler end state of BASELINE configs[2] (U-ViT-L T2I, B = 2); which steps edited is recorded
                                     from the reference's own file reads / hook calls
+  adaptive_traj                     the reference's default error-controlled solves through the reference networks and the
+                                    oracle solver: adaptive dopri5 (rtol = atol = 1e-5) of U-ViT-S / U-ViT-L at B = 2, and hooked
+                                    fixadp (Euler 0.01 to t_edit 0.4, then dopri5) on the tiny network and U-ViT-S, with the
+                                    evaluations the reference's write_attr hook edited (--only-adaptive)
   traj_L_u                          BASELINE config 2 (the headline shape) end to end at B=2: 50 fixed Euler steps and
                                     50 fixed Dormand-Prince steps (FSAL, 301 evaluations) of the reference U-ViT-L,
                                     both driven by loops written here (flow_matching.py:130-151 selects the solver;
@@ -585,6 +589,106 @@ def make_hooked_traj(uvit, uvit_t2i, m_u, x_u, m_t, x_t, ctx_t, timing, skip_lar
 
 
 
+# --------------------------------------------------------------------------- the reference's default error-controlled solves
+ADAPTIVE_HOOK = dict(dissect_task="uspace_uvit", dissect_name="write_attr", t_edit=0.4, edit_loc="tail", ith_attr=2, write_scale=1.0)
+
+
+def save_deterministic(name, **arrays):
+    """np.savez with a fixed zip member timestamp, so that a rerun of the generator writes the same bytes."""
+    import io
+    import zipfile
+    path = os.path.join(HERE, name)
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_STORED) as zf:
+        for key, val in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue())
+    print(f"wrote {name}: {os.path.getsize(path)/1024:.1f} KiB")
+
+
+def make_adaptive_traj(uvit, m_tiny, x_tiny, timing):
+    """The solves the reference runs by default, through the REFERENCE networks (fp32, CPU) and the oracle solver
+    (oracle/odeint_oracle.py; the reference's own integrator is the absent torchdiffeq):
+    (a) decode without dissection, flow_matching.py:78-84: adaptive dopri5, rtol = atol = 1e-5, t 0 -> 1, of U-ViT-S-deep16 and
+        U-ViT-L (seeded weights of big_*_u, B = 2 latents drawn as in traj_L_u) -- end state, NFE, accepted / rejected attempts,
+        the accepted grid and the time of every evaluation;
+    (b) fixadp of every dissection config (configs/lfm_cm256_uvit_large.py:124-130): Euler step 0.01 up to t_edit = 0.4, then
+        dopri5, with the reference's dissect_helper_uvit write_attr hook live (libs/dissection.py:115-186, edit_loc tail) on the
+        tables of hooked_delta_table, for the tiny network of tiny_u and for U-ViT-S -- end state and, per evaluation, its time and
+        whether the reference read a delta table in it (dopri5 stage times in (0.40, 0.405) format to "0.40" and still edit)."""
+    import importlib
+    ROOT = os.path.dirname(os.path.dirname(HERE))
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from oracle import odeint_oracle as OO
+    dis = importlib.import_module("libs.dissection")
+    out = {}
+    B = 2
+
+    def solve_plain(m, z, tag):
+        ts = []
+
+        def f(t, y):
+            ts.append(t)
+            with torch.no_grad():
+                return m(torch.from_numpy(y), expand_t(t, y.shape[0]), None, edit_loc=None)[0].numpy()
+
+        cnt = {"t_accepted": []}
+        t0 = time.perf_counter()
+        x1 = OO.solve(f, z, 0.0, 1.0, method="dopri5", rtol=1e-5, atol=1e-5, counters=cnt)
+        timing[f"adaptive_{tag}_B2_dopri5_total_s"] = time.perf_counter() - t0
+        out.update({f"{tag}_z": z, f"{tag}_x1": x1, f"{tag}_nfe": np.int32(cnt["nfe"]), f"{tag}_accepted": np.int32(cnt["accepted"]),
+                    f"{tag}_rejected": np.int32(cnt["rejected"]), f"{tag}_t_accepted": np.array(cnt["t_accepted"], np.float64),
+                    f"{tag}_t_eval": np.array(ts, np.float64)})
+        print(tag, cnt["nfe"], cnt["accepted"], cnt["rejected"])
+
+    def solve_fixadp(m, z, tag, table_shape):
+        ts, edited = [], []
+        with tempfile.TemporaryDirectory() as d:
+            for k in range(0, 101):
+                np.save(os.path.join(d, f"delta_{k / 100:.2f}.npy"), hooked_delta_table(k, table_shape))
+            reads = []
+            orig = dis._read_npz_bcwh
+
+            def counting(npz_path, ith_ele, device):
+                reads.append(os.path.basename(npz_path))
+                return orig(npz_path=npz_path, ith_ele=ith_ele, device=device)
+
+            kwargs = dict(ADAPTIVE_HOOK, write_path_root=d)
+
+            def f(t, y):
+                n = len(reads)
+                ts.append(t)
+                with torch.no_grad():
+                    v = m(torch.from_numpy(y), expand_t(t, y.shape[0]), None, **kwargs)[0].numpy()
+                edited.append(len(reads) > n)
+                return v
+
+            dis._read_npz_bcwh = counting
+            try:
+                cnt_fix, cnt = {}, {"t_accepted": []}
+                mid = OO.solve(f, z, 0.0, 0.4, method="euler", step_size=0.01, counters=cnt_fix)
+                x1 = OO.solve(f, mid, 0.4, 1.0, method="dopri5", rtol=1e-5, atol=1e-5, counters=cnt)
+            finally:
+                dis._read_npz_bcwh = orig
+        assert cnt_fix["nfe"] == 40 and edited[:40] == [False] + [True] * 39, edited[:40]
+        out.update({f"{tag}_z": z, f"{tag}_x1": x1, f"{tag}_t_eval": np.array(ts, np.float64), f"{tag}_edited": np.array(edited, np.bool_),
+                    f"{tag}_nfe_adaptive": np.int32(cnt["nfe"]), f"{tag}_accepted": np.int32(cnt["accepted"]),
+                    f"{tag}_rejected": np.int32(cnt["rejected"]), f"{tag}_t_accepted": np.array(cnt["t_accepted"], np.float64)})
+        print(tag, len(ts), cnt["accepted"], cnt["rejected"], sum(edited))
+
+    z2 = torch.randn(B, 4, 32, 32, generator=torch.Generator().manual_seed(INPUT_SEED)).numpy()
+    m = build_big(uvit, None, "S", "u")
+    solve_plain(m, z2, "S_u")
+    solve_fixadp(m, z2, "S_u_fixadp", (5, 4, 32, 32))
+    del m
+    solve_fixadp(m_tiny, np.asarray(x_tiny, np.float32), "tiny_fixadp", (5, 4, 16, 16))
+    m = build_big(uvit, None, "L", "u")
+    solve_plain(m, z2, "L_u")
+    del m
+    save_deterministic("adaptive_traj.npz", **out)
+
+
 def make_attr_directions():
     """tools/utils_attr.py:124-145 cal_delta_direction on synthetic features: mean(pos) - mean(neg) per
     attribute (the direction files the write hook consumes)."""
@@ -767,7 +871,16 @@ def main():
     ap.add_argument("--only-clip", action="store_true", help="regenerate only clip_text_tiny.npz (no reference import needed)")
     ap.add_argument("--only-word-inds", action="store_true", help="regenerate only word_inds.json")
     ap.add_argument("--only-hooked", action="store_true", help="regenerate only hooked_traj.npz")
+    ap.add_argument("--only-adaptive", action="store_true", help="regenerate only adaptive_traj.npz")
     args = ap.parse_args()
+    if args.only_adaptive:
+        uvit, _ = _refshim.load_reference()
+        torch.set_grad_enabled(False)
+        torch.manual_seed(WEIGHT_SEED)                     # the tiny network and inputs of tiny_u.npz
+        m_u = uvit.UViT(num_classes=-1, **TINY).eval()
+        x_u = torch.randn(3, 4, 16, 16, generator=torch.Generator().manual_seed(INPUT_SEED)).numpy()
+        make_adaptive_traj(uvit, m_u, x_u, {})
+        return
     if args.only_hooked:
         uvit, uvit_t2i = _refshim.load_reference()
         torch.set_grad_enabled(False)
@@ -823,6 +936,8 @@ def main():
     make_word_inds()
     hooked_timing = {}
     make_hooked_traj(uvit, uvit_t2i, m, x, mt, xt, ctx, hooked_timing, skip_large=args.skip_large)
+    if not args.skip_large:
+        make_adaptive_traj(uvit, m, x.numpy(), {})
     if not args.skip_large:
         timing = dict(threads=torch.get_num_threads(), nproc=os.cpu_count(),
                       cpu=[l.split(":")[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name")][0],

@@ -294,3 +294,46 @@ def test_hooked_trajectories_follow_the_reference(golden_dir, monkeypatch):
     np.testing.assert_allclose(z_enc, z["t_z_enc"], **tol)
     np.testing.assert_allclose(x_dec, z["t_x_dec"], **tol)
     assert np.abs(z["t_x_dec"] - z["t_x_dec_plain"]).max() > 2e-3
+
+
+ADAPTIVE_HOOK = dict(dissect_task="uspace_uvit", dissect_name="write_attr", t_edit=0.4, edit_loc="tail", ith_attr=2, write_scale=1.0)
+
+
+def test_hooked_fixadp_follows_the_reference(golden_dir, monkeypatch):
+    """adaptive_traj.npz (make_golden.py::make_adaptive_traj): the reference's tiny U-ViT with its own write_attr hook live, solved
+    the fixadp way of every dissection config -- Euler 0.01 up to t_edit = 0.4, then dopri5 rtol = atol = 1e-5 -- by the oracle
+    solver.  The oracle forward + hook must edit in the same evaluations (the dopri5 stage at t = 0.4048 formats to "0.40" and
+    edits; the probe at 0.415 does not), take the same attempts and land on the same end state."""
+    from oracle import odeint_oracle as OO
+    z = np.load(os.path.join(golden_dir, "adaptive_traj.npz"))
+    zt, sd = _load(golden_dir, "tiny_u.npz")
+    spec = O.UViTSpec(**TINY)
+    np.testing.assert_array_equal(z["tiny_fixadp_z"], zt["x"])
+    with tempfile.TemporaryDirectory() as d:
+        write_hooked_tables(d)
+        files, ts, edited = [], [], []
+        real_load = np.load
+        monkeypatch.setattr(O.np, "load", lambda p, *a, **k: (files.append(os.path.basename(str(p))), real_load(p, *a, **k))[1])
+        kwargs = dict(ADAPTIVE_HOOK, write_path_root=d)
+
+        def f(t, y):
+            n = len(files)
+            ts.append(t)
+            v = O.uvit_forward(spec, sd, y, t, **kwargs)
+            edited.append(len(files) > n)
+            return v
+
+        cnt_fix, cnt = {}, {"t_accepted": []}
+        mid = OO.solve(f, zt["x"], 0.0, 0.4, method="euler", step_size=0.01, counters=cnt_fix)
+        x1 = OO.solve(f, mid, 0.4, 1.0, method="dopri5", rtol=1e-5, atol=1e-5, counters=cnt)
+        monkeypatch.undo()
+    assert cnt_fix["nfe"] == 40
+    assert edited == z["tiny_fixadp_edited"].tolist()
+    assert edited[40:43] == [True, False, True]              # f0 at 0.40, probe at 0.415 ("0.42"), stage 1 at 0.4048 ("0.40")
+    assert (cnt["nfe"], cnt["accepted"], cnt["rejected"]) == (int(z["tiny_fixadp_nfe_adaptive"]), int(z["tiny_fixadp_accepted"]),
+                                                               int(z["tiny_fixadp_rejected"]))
+    # every time up to the last attempt; that attempt's dt comes from an error ratio at the round-off floor of an almost linear
+    # field (it steps from 0.72 to 2.7, past t1, and the dense output lands on 1.0), so its size differs by a few percent
+    np.testing.assert_allclose(ts[:-6], z["tiny_fixadp_t_eval"][:-6], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(cnt["t_accepted"][:-1], z["tiny_fixadp_t_accepted"][:-1], rtol=1e-5)
+    np.testing.assert_allclose(x1, z["tiny_fixadp_x1"], rtol=2e-4, atol=2e-4)

@@ -310,7 +310,14 @@ def cast_bf16(src):
     return dst
 
 
+def _ode_operands(what, ks, coefs):
+    # ctypes zero-fills an array built from fewer values than its length: a short coefficient list would drop terms silently
+    if len(coefs) != len(ks):
+        raise UspaceHipError(f"{what}: {len(coefs)} coefficients for {len(ks)} operands")
+
+
 def ode_combine(out, y, ks, coefs):
+    _ode_operands("ode_combine", ks, coefs)
     require_device(y, "y")
     n = len(ks)
     karr = (ctypes.c_void_p * max(n, 1))(*[k.data_ptr() for k in ks])
@@ -321,8 +328,11 @@ def ode_combine(out, y, ks, coefs):
 
 def ode_error_norm(y0, y1, ks, coefs, rtol, atol, scratch, result):
     """``result``: device float[2] = [rms, sum of squares]."""
+    _ode_operands("ode_error_norm", ks, coefs)
     if result.numel() < 2:
         raise UspaceHipError("ode_error_norm: result must hold 2 floats (ABI 6)")
+    if scratch.numel() < 1024:
+        raise UspaceHipError("ode_error_norm: scratch must hold 1024 floats (one partial per block)")
     n = len(ks)
     karr = (ctypes.c_void_p * n)(*[k.data_ptr() for k in ks])
     carr = (ctypes.c_float * n)(*[float(c) for c in coefs])

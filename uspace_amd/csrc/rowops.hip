@@ -748,7 +748,9 @@ __global__ __launch_bounds__(256) void ode_combine_kernel(float* __restrict__ ou
     }
 }
 
-// partial sums of (err / (atol + rtol*max(|y0|,|y1|)))^2, one per block, then a 1-block finish
+// partial sums of (err / (atol + rtol*max(|y0|,|y1|)))^2, one per block, then a 1-block finish.  A non-finite y0[i] or
+// y1[i] makes that element's ratio NaN: fmaxf would drop a NaN operand and an infinite one would give tol = Inf, ratio 0,
+// and the solver would accept a step whose state is no longer a number.  Finite elements take the arithmetic unchanged.
 __global__ __launch_bounds__(256) void ode_err_partial_kernel(const float* __restrict__ y0, const float* __restrict__ y1,
                                                               KPtrs kp, float rtol, float atol, long n,
                                                               float* __restrict__ partial) {
@@ -758,8 +760,10 @@ __global__ __launch_bounds__(256) void ode_err_partial_kernel(const float* __res
 #pragma unroll
         for (int j = 0; j < 8; ++j)
             if (j < kp.n) e += kp.c[j] * kp.k[j][i];
-        const float tol = atol + rtol * fmaxf(fabsf(y0[i]), fabsf(y1[i]));
-        const float r = e / tol;
+        const float a0 = fabsf(y0[i]), a1 = fabsf(y1[i]);
+        const float tol = atol + rtol * fmaxf(a0, a1);
+        float r = e / tol;
+        if (!(a0 <= __FLT_MAX__ && a1 <= __FLT_MAX__)) r = __builtin_nanf("");   // NaN compares false, Inf exceeds the max
         s += r * r;
     }
     __shared__ float red[4];

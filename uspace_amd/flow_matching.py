@@ -8,7 +8,7 @@ the external torchdiffeq.  ``sample_ode`` (the name BASELINE.json uses) aliases 
 import torch
 import torch.nn as nn
 
-from .odeint import FIXED, Stats, odeint
+from .odeint import ADAPTIVE, FIXED, Stats, odeint
 
 _RTOL = 1e-5
 _ATOL = 1e-5
@@ -159,12 +159,58 @@ class CNF(CNFBase):
 
     def decode_write_scales(self, z, y, write_scales, **kwargs):
         """The reference's sweep ``for write_scale in write_scales: decode(z, write_scale=...)``
-        (tools/utils_vis.py:189-198, nine full solves of the same z) as ONE solve over len(scales)*B rows
-        with a per-row hook scale.  Returns [n_scales, B, C, H, W].  Exactly equal to the sequential sweep
-        for fixed-step solvers; adaptive solvers would share one step-size sequence across the scales."""
+        (tools/utils_vis.py:189-198, one full solve of the same z per scale).  Returns [n_scales, B, C, H, W].
+
+        A fixed-step solve runs as ONE solve over len(scales)*B rows with a per-row hook scale: the rows never
+        interact, so it equals the sequential sweep.  An error-controlled solve picks its steps from one norm over
+        all its rows, so it is split where the reference's solves differ: ``fixadp`` runs its fixed leg batched
+        and then one adaptive leg per scale over that scale's B rows; ``adaptive`` runs one solve per scale.
+        ``last_stats`` sums the NFE / attempts of every solve."""
         n, B = len(write_scales), z.shape[0]
-        rows = torch.as_tensor([float(s) for s in write_scales], dtype=torch.float32).repeat_interleave(B)
+        scales = [float(s) for s in write_scales]
+        rows = torch.as_tensor(scales, dtype=torch.float32).repeat_interleave(B)
         zz = z.repeat(n, 1, 1, 1)
         yy = y.repeat(n) if torch.is_tensor(y) else y
-        out = self.decode(zz, yy, **dict(kwargs, write_scale=rows))
-        return out.view(n, B, *z.shape[1:])
+        split = self._error_controlled_legs(kwargs)
+        if split is None:
+            out = self.decode(zz, yy, **dict(kwargs, write_scale=rows))
+            return out.view(n, B, *z.shape[1:])
+        stats = Stats()
+        if split == "adaptive":
+            outs = []
+            for s in scales:
+                outs.append(self.decode(z, y, **dict(kwargs, write_scale=s)))
+                _add_stats(stats, self.last_stats)
+        else:                                   # fixadp: batched fixed leg to t_edit, then one adaptive leg per scale
+            t_mid = kwargs["t_edit"]
+            assert 0 <= t_mid <= 1, f"t_mid={t_mid}"
+            fixed_kw, adaptive_kw = self.get_ode_kwargs(**kwargs)
+            kw_rows = dict(kwargs, write_scale=rows)
+            self.last_stats = stats
+            mid = self._integrate(lambda t, xx: self._velocity(t, xx, yy, kw_rows), zz, 0.0, t_mid, fixed_kw)
+            outs = []
+            for i, s in enumerate(scales):
+                kw_i = dict(kwargs, write_scale=s)
+                self.last_stats = stats
+                outs.append(self._integrate(lambda t, xx, kw_i=kw_i: self._velocity(t, xx, y, kw_i), mid[i * B:(i + 1) * B],
+                                            t_mid, 1.0, adaptive_kw))
+        self.last_stats = stats
+        return torch.stack(outs)
+
+    def _error_controlled_legs(self, kwargs):
+        """Which legs of decode(**kwargs) are error-controlled: None (none: fixed steps), "adaptive" (the whole solve) or
+        "fixadp" (the leg after t_edit).  Follows _solve's selection."""
+        sk = kwargs["solver_kwargs"]
+        n_steps = sk.get("n_steps") if hasattr(sk, "get") else None
+        if sk["solver"] in ("fixed", "adaptive"):
+            okw = self.get_ode_kwargs(**kwargs)
+            return "adaptive" if okw["method"] in ADAPTIVE and n_steps is None else None
+        if sk["solver"] == "fixadp":
+            return "fixadp" if self.get_ode_kwargs(**kwargs)[1]["method"] in ADAPTIVE else None
+        return None
+
+
+def _add_stats(total, part):
+    total.nfe += part.nfe
+    total.accepted += part.accepted
+    total.rejected += part.rejected

@@ -232,10 +232,14 @@ def odeint(func, y0, t0, t1, *, method="dopri5", rtol=1e-5, atol=1e-5, step_size
     order = tab["order"]
     d0 = ops.scaled_norm(y, y, [y], [1.0], rtol, atol)
     d1 = ops.scaled_norm(y, y, [f0], [1.0], rtol, atol)
+    if not (math.isfinite(d0) and math.isfinite(d1)):
+        raise RuntimeError(f"non-finite values in state `y` or its derivative: initial-step norms {d0}, {d1}")
     h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else 0.01 * d0 / d1
     y_probe = ops.combine(y, [f0], [h0])
     f_probe = f_eval(t0 + h0, y_probe)
     d2 = ops.scaled_norm(y, y, [f_probe, f0], [1.0, -1.0], rtol, atol) / h0
+    if not math.isfinite(d2):
+        raise RuntimeError(f"non-finite values in state `y` or its derivative: initial-step probe norm {d2}")
     # torchdiffeq hands `order - 1` to its initial-step heuristic (rk_common.py: _select_initial_step(..., self.order - 1,
     # ...)), whose exponent is 1 / (that + 1): 1/5 for dopri5, not Hairer's 1/(order + 1)
     h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else (0.01 / max(d1, d2)) ** (1.0 / order)
@@ -244,9 +248,16 @@ def odeint(func, y0, t0, t1, *, method="dopri5", rtol=1e-5, atol=1e-5, step_size
     t = t0
     steps = 0
     while True:
-        # step until the accepted interval [t, t+dt] covers t1, then evaluate the dense output at t1
+        # step until the accepted interval [t, t+dt] covers t1, then evaluate the dense output at t1.  As torchdiffeq's
+        # _adaptive_step: a dt that no longer moves t (underflow, or NaN) and a state that is no longer finite end the solve.
+        # The error norm is NaN whenever y, y1 or a weighted stage is (uspace_ode_error_norm), so a non-finite ratio is
+        # that check at no extra cost; without it a NaN ratio would grow dt tenfold per rejection and an Inf one shrink it.
+        if not t + dt > t:
+            raise RuntimeError(f"underflow in dt {dt}")
         y1, f1, ks, ratio = _adaptive_try(func, tab, ops, t, dt, y, f0, sign, stats, rtol, atol)
         steps += 1
+        if not math.isfinite(ratio):
+            raise RuntimeError(f"non-finite values in state `y`: error ratio {ratio} at t={sign * t}, dt={dt}")
         if steps > max_num_steps:
             raise RuntimeError("max_num_steps exceeded")
         accept = ratio <= 1.0

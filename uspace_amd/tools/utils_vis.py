@@ -4,8 +4,9 @@ the main process writes one grid image per round.  This is the single entry poin
 u-space hook, batch 256 over 8 GPUs).
 
 Extension: ``sweep_fn(input_z=..., write_scales=[...], batch_id=..., **kwargs) -> [n_scales, B, C, H, W]`` runs the whole
-sweep as ONE solve over n_scales * B rows (flow_matching.CNF.decode_write_scales, exact for fixed-step solvers) instead of
-``len(write_scales)`` sequential solves; the written image is the same."""
+sweep at once (flow_matching.CNF.decode_write_scales): ONE solve over n_scales * B rows for fixed-step solvers, and for the
+error-controlled ones the fixed leg of ``fixadp`` batched and one adaptive solve per scale, each with its own steps as in the
+reference's sequential loop; the written image is the same."""
 import datetime
 import os
 
