@@ -380,6 +380,34 @@ USPACE_API int uspace_vae_encode_tap(const uspace_vae_config* cfg, const void* b
 USPACE_API int uspace_vae_sample(const float* moments, const float* noise, float scale, float* z, int B, int h,
                                  uspace_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * FID: the Inception-v3 feature extractor of pytorch-fid (reference tools/inception.py, fid_inception_v3 up to the final
+ * average pool) and the fp64 statistics of its features (tools/fid_score.py).  fp32 operands on the fp32 matrix cores;
+ * each output is a fixed k-ordered fp32 fma chain, so each image's features are bit-identical across batch sizes.
+ * ------------------------------------------------------------------------------------- */
+/* 470 parameter tensors: per BasicConv2d in torchvision Inception3's state_dict order, conv.weight [Cout,Cin,kh,kw] then
+ * bn.weight, bn.bias, bn.running_mean, bn.running_var [Cout] (fp32, device).  Packing folds BN (eps 1e-3) in fp64. */
+USPACE_API int uspace_inception_num_params(void);
+USPACE_API long uspace_inception_param_numel(int index);
+USPACE_API size_t uspace_inception_weight_bytes(void);
+USPACE_API size_t uspace_inception_workspace_bytes(int B, int H, int W);
+USPACE_API int uspace_inception_pack_weights(const float* const* params, int n_params, void* blob, size_t blob_bytes,
+                                             uspace_stream_t stream);
+/* x [B,3,H,W] fp32 (NCHW, values in [0,1]) -> bilinear resize to 299 x 299 (align_corners=False), 2x - 1, the network up to
+ * block `last_block` (0: first max pool, 64; 1: second max pool, 192; 2: Mixed_6e, 768; 3: Mixed_7c, 2048) and its global
+ * spatial mean -> feat [B, dims] fp32.  B * 147 * 147 * 64 and B * 3 * H * W must stay below 2^31 (run in chunks). */
+USPACE_API int uspace_inception_forward(const void* blob, void* workspace, size_t workspace_bytes, const float* x, int B,
+                                        int H, int W, int last_block, float* feat, uspace_stream_t stream);
+/* Test aid: run up to `stage` and copy its output to `out` (device, large enough): 0 the resized, normalised input
+ * [B,299,299,3]; 1-3 Conv2d_1a/2a/2b; 4 max pool; 5-6 Conv2d_3b/4a; 7 max pool; 8-10 Mixed_5b-5d; 11 Mixed_6a; 12-15
+ * Mixed_6b-6e; 16 Mixed_7a; 17-18 Mixed_7b/7c (all NHWC [B,H,W,C]); 19 the global mean [B,2048]. */
+USPACE_API int uspace_inception_tap(const void* blob, void* workspace, size_t workspace_bytes, const float* x, int B, int H,
+                                    int W, int stage, float* out, uspace_stream_t stream);
+/* In place, in fp64: s1[F] += sum_b (feat[b] - shift), s2[F,F] += sum_b (feat[b] - shift)(feat[b] - shift)^T for
+ * feat [B,F] fp32; shift [F] fp64 (the first batch's mean).  Deterministic: every element has one owner. */
+USPACE_API int uspace_fid_stats_accumulate(const float* feat, int B, int F, const double* shift, double* s1, double* s2,
+                                           uspace_stream_t stream);
+
 /* hipGraph form of the forward.  _create() runs the forward once eagerly on `capture_stream` (must be a
  * real, non-NULL stream), then captures the same launch sequence and instantiates it.  The pointers in
  * `io`, the blob and the workspace are baked in: keep them alive and stable, refresh their CONTENTS

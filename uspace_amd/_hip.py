@@ -121,6 +121,14 @@ SIGNATURES = {
     "uspace_vae_enc_pack_weights": (_I, [ctypes.POINTER(VaeConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
     "uspace_vae_encode_moments": (_I, [ctypes.POINTER(VaeConfig), _P, _P, _SZ, _P, _P, _I, _P]),
     "uspace_vae_encode_tap": (_I, [ctypes.POINTER(VaeConfig), _P, _P, _SZ, _P, _I, _I, _P, ctypes.POINTER(_I), _P]),
+    "uspace_inception_num_params": (_I, []),
+    "uspace_inception_param_numel": (_L, [_I]),
+    "uspace_inception_weight_bytes": (_SZ, []),
+    "uspace_inception_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "uspace_inception_pack_weights": (_I, [ctypes.POINTER(_P), _I, _P, _SZ, _P]),
+    "uspace_inception_forward": (_I, [_P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P]),
+    "uspace_inception_tap": (_I, [_P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P]),
+    "uspace_fid_stats_accumulate": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "uspace_vae_sample": (_I, [_P, _P, _F, _P, _I, _I, _P]),
     "uspace_clip_num_params": (_I, [ctypes.POINTER(ClipConfig)]),
     "uspace_clip_param_numel": (_L, [ctypes.POINTER(ClipConfig), _I]),

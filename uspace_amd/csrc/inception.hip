@@ -1,0 +1,687 @@
+// FID feature extractor on gfx950: the FID variant of Inception-v3 (pytorch-fid's fid_inception_v3, reference
+// tools/inception.py) up to the final average pool, and the fp64 running statistics of its features
+// (reference tools/fid_score.py: np.mean / np.cov of the pool_3 activations).
+//
+// Precision: fp32 operands on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).  That instruction is bit-for-bit a
+// k-ordered fp32 fma chain, so every output element of a convolution is fma(..fma(a_0 b_0, 0)..) over K in the fixed
+// (tap, channel) order, whatever the batch size: each image's features are bit-identical across batch sizes.
+//
+// Layout: activations NHWC fp32 in the caller's workspace.  Every BasicConv2d (conv(bias=False) -> BatchNorm2d(eps=1e-3)
+// -> ReLU) is one launch of the implicit-GEMM kernel below with BN folded into the packed weights (in fp64, rounded once)
+// and the bias + ReLU in its epilogue; the epilogue stores at a channel offset and row stride of the block's output, so the
+// torch.cat of every Mixed block costs nothing.
+#include <math.h>
+
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kIn = 299;              // resize target (pytorch-fid resizes every input to 299 x 299)
+constexpr double kBnEps = 1e-3;       // BatchNorm2d(eps=0.001) of torchvision's BasicConv2d
+constexpr int kNumConvs = 94;
+constexpr int kParamsPerConv = 5;     // conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var
+constexpr int kNumStages = 20;        // 0 resized input .. 18 Mixed_7c, 19 global mean
+// per-image buffer sizes (floats): P/Q hold block inputs and outputs (largest: Conv2d_2b_3x3, 147 x 147 x 64), T1-T3 the
+// branch intermediates (largest: the pooled input of Mixed_5d, 35 x 35 x 288; the resized input, 299 x 299 x 3, lives in T1)
+constexpr long kBigPer = 147L * 147 * 64;
+constexpr long kTmpPer = 35L * 35 * 288;
+
+struct ConvSpec {
+    int cin, cout, kh, kw, s, ph, pw;
+};
+
+// the 94 BasicConv2d of torchvision's Inception3 with the FID patches, in state_dict (= execution) order
+const std::vector<ConvSpec>& conv_specs() {
+    static const std::vector<ConvSpec> specs = [] {
+        std::vector<ConvSpec> v;
+        auto c = [&](int ci, int co, int kh, int kw, int s, int ph, int pw) { v.push_back({ci, co, kh, kw, s, ph, pw}); };
+        c(3, 32, 3, 3, 2, 0, 0);      // Conv2d_1a_3x3
+        c(32, 32, 3, 3, 1, 0, 0);     // Conv2d_2a_3x3
+        c(32, 64, 3, 3, 1, 1, 1);     // Conv2d_2b_3x3
+        c(64, 80, 1, 1, 1, 0, 0);     // Conv2d_3b_1x1
+        c(80, 192, 3, 3, 1, 0, 0);    // Conv2d_4a_3x3
+        const int a_in[3] = {192, 256, 288}, a_pool[3] = {32, 64, 64};
+        for (int i = 0; i < 3; ++i) {  // Mixed_5b-5d (InceptionA)
+            c(a_in[i], 64, 1, 1, 1, 0, 0);
+            c(a_in[i], 48, 1, 1, 1, 0, 0);
+            c(48, 64, 5, 5, 1, 2, 2);
+            c(a_in[i], 64, 1, 1, 1, 0, 0);
+            c(64, 96, 3, 3, 1, 1, 1);
+            c(96, 96, 3, 3, 1, 1, 1);
+            c(a_in[i], a_pool[i], 1, 1, 1, 0, 0);
+        }
+        c(288, 384, 3, 3, 2, 0, 0);    // Mixed_6a (InceptionB)
+        c(288, 64, 1, 1, 1, 0, 0);
+        c(64, 96, 3, 3, 1, 1, 1);
+        c(96, 96, 3, 3, 2, 0, 0);
+        const int c7s[4] = {128, 160, 160, 192};
+        for (int i = 0; i < 4; ++i) {  // Mixed_6b-6e (InceptionC)
+            const int c7 = c7s[i];
+            c(768, 192, 1, 1, 1, 0, 0);
+            c(768, c7, 1, 1, 1, 0, 0);
+            c(c7, c7, 1, 7, 1, 0, 3);
+            c(c7, 192, 7, 1, 1, 3, 0);
+            c(768, c7, 1, 1, 1, 0, 0);
+            c(c7, c7, 7, 1, 1, 3, 0);
+            c(c7, c7, 1, 7, 1, 0, 3);
+            c(c7, c7, 7, 1, 1, 3, 0);
+            c(c7, 192, 1, 7, 1, 0, 3);
+            c(768, 192, 1, 1, 1, 0, 0);
+        }
+        c(768, 192, 1, 1, 1, 0, 0);    // Mixed_7a (InceptionD)
+        c(192, 320, 3, 3, 2, 0, 0);
+        c(768, 192, 1, 1, 1, 0, 0);
+        c(192, 192, 1, 7, 1, 0, 3);
+        c(192, 192, 7, 1, 1, 3, 0);
+        c(192, 192, 3, 3, 2, 0, 0);
+        const int e_in[2] = {1280, 2048};
+        for (int i = 0; i < 2; ++i) {  // Mixed_7b, 7c (InceptionE)
+            c(e_in[i], 320, 1, 1, 1, 0, 0);
+            c(e_in[i], 384, 1, 1, 1, 0, 0);
+            c(384, 384, 1, 3, 1, 0, 1);
+            c(384, 384, 3, 1, 1, 1, 0);
+            c(e_in[i], 448, 1, 1, 1, 0, 0);
+            c(448, 384, 3, 3, 1, 1, 1);
+            c(384, 384, 1, 3, 1, 0, 1);
+            c(384, 384, 3, 1, 1, 1, 0);
+            c(e_in[i], 192, 1, 1, 1, 0, 0);
+        }
+        return v;
+    }();
+    return specs;
+}
+
+inline int conv_k(const ConvSpec& c) { return c.kh * c.kw * c.cin; }
+inline int conv_kpad(const ConvSpec& c) { return (conv_k(c) + 15) & ~15; }
+
+// packed blob: per conv, W [K_pad, Cout] then bias [Cout], every piece starting at a multiple of 16 floats
+struct BlobLayout {
+    std::vector<size_t> w_off, b_off;
+    size_t floats = 0;
+};
+const BlobLayout& blob_layout() {
+    static const BlobLayout L = [] {
+        BlobLayout l;
+        size_t o = 0;
+        for (const ConvSpec& c : conv_specs()) {
+            l.w_off.push_back(o);
+            o += ((size_t)conv_kpad(c) * c.cout + 15) & ~(size_t)15;
+            l.b_off.push_back(o);
+            o += ((size_t)c.cout + 15) & ~(size_t)15;
+        }
+        l.floats = o;
+        return l;
+    }();
+    return L;
+}
+
+// ---- weight packing: BN folded in fp64, rounded once to fp32; W'[k = (ty * kw + tx) * Cin + c][n], zero rows k >= K
+__global__ __launch_bounds__(256) void pack_conv_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, const float* __restrict__ mean,
+                                                        const float* __restrict__ var, float* __restrict__ wout,
+                                                        float* __restrict__ bout, int cin, int cout, int kh, int kw, int K,
+                                                        int Kpad) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long nw = (long)Kpad * cout;
+    if (idx < nw) {
+        const int k = (int)(idx / cout), n = (int)(idx - (long)k * cout);
+        float v = 0.f;
+        if (k < K) {
+            const int tap = k / cin, c = k - tap * cin, ty = tap / kw, tx = tap - ty * kw;
+            const double s = (double)gamma[n] / sqrt((double)var[n] + kBnEps);
+            v = (float)((double)w[(((long)n * cin + c) * kh + ty) * kw + tx] * s);
+        }
+        wout[idx] = v;
+    } else if (idx < nw + cout) {
+        const int n = (int)(idx - nw);
+        const double s = (double)gamma[n] / sqrt((double)var[n] + kBnEps);
+        bout[n] = (float)((double)beta[n] - (double)mean[n] * s);
+    }
+}
+
+// ---- input: bilinear resize (align_corners=False) of NCHW [B,3,H,W] to 299 x 299, then 2x - 1, written NHWC
+__global__ __launch_bounds__(256) void resize_input_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int H,
+                                                           int W) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (b, oy, ox)
+    if (idx >= (long)B * kIn * kIn) return;
+    const int b = (int)(idx / (kIn * kIn));
+    const int r = (int)(idx - (long)b * kIn * kIn);
+    const int oy = r / kIn, ox = r - oy * kIn;
+    const float sh = (float)H / kIn, sw = (float)W / kIn;
+    const float fy = fmaxf(((float)oy + 0.5f) * sh - 0.5f, 0.f);
+    const float fx = fmaxf(((float)ox + 0.5f) * sw - 0.5f, 0.f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* p = x + ((long)b * 3 + c) * H * W;
+        const float v = hy * (hx * p[(long)y0 * W + x0] + lx * p[(long)y0 * W + x1]) +
+                        ly * (hx * p[(long)y1 * W + x0] + lx * p[(long)y1 * W + x1]);
+        out[idx * 3 + c] = 2.f * v - 1.f;
+    }
+}
+
+// ---- 3 x 3 pooling over NHWC, 4 channels per thread.  MAX: max_pool2d (padding never wins: taps outside are skipped);
+// AVG: avg_pool2d(count_include_pad=False), the 9 (or fewer) valid taps summed in row-major order over their count.
+template <bool MAX>
+__global__ __launch_bounds__(256) void pool3_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W,
+                                                    int C, int s, int p, int Ho, int Wo, int ldo, int coff) {
+    const int C4 = C >> 2;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)B * Ho * Wo * C4) return;
+    const int c = (int)(idx % C4) * 4;
+    const long pix = idx / C4;
+    const int b = (int)(pix / ((long)Ho * Wo));
+    const int r = (int)(pix - (long)b * Ho * Wo);
+    const int oy = r / Wo, ox = r - oy * Wo;
+    f32x4 acc = MAX ? (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY} : (f32x4){0.f, 0.f, 0.f, 0.f};
+    int cnt = 0;
+    for (int dy = 0; dy < 3; ++dy) {
+        const int iy = oy * s - p + dy;
+        if (iy < 0 || iy >= H) continue;
+        for (int dx = 0; dx < 3; ++dx) {
+            const int ix = ox * s - p + dx;
+            if (ix < 0 || ix >= W) continue;
+            const f32x4 v = *(const f32x4*)(x + (((long)b * H + iy) * W + ix) * C + c);
+            if (MAX) {
+                acc[0] = fmaxf(acc[0], v[0]); acc[1] = fmaxf(acc[1], v[1]);
+                acc[2] = fmaxf(acc[2], v[2]); acc[3] = fmaxf(acc[3], v[3]);
+            } else {
+                acc += v;
+            }
+            ++cnt;
+        }
+    }
+    if (!MAX) acc /= (float)cnt;
+    *(f32x4*)(y + pix * ldo + coff + c) = acc;
+}
+
+// ---- global spatial mean: feat[b, c] = mean over H*W of x[b, :, :, c] (fp64 sum in pixel order, rounded once)
+__global__ __launch_bounds__(256) void spatial_mean_kernel(const float* __restrict__ x, float* __restrict__ feat, int B, int HW,
+                                                           int C) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)B * C) return;
+    const int b = (int)(idx / C), c = (int)(idx - (long)b * C);
+    const float* p = x + (long)b * HW * C + c;
+    double s = 0.0;
+    for (int i = 0; i < HW; ++i) s += p[(long)i * C];
+    feat[idx] = (float)(s / HW);
+}
+
+// ---- implicit-GEMM convolution, fp32 MFMA.  GEMM view: M = B*Ho*Wo output pixels, N = Cout, K = kh*kw*Cin ordered
+// (tap, channel).  Workgroup = 128 x 64 output tile, 4 waves of 64 x 32 (two 32 x 32 accumulators sharing the B
+// operand); K advances 16 at a time through LDS (A as [k][m], B as [k][n]: both MFMA operand reads are 32 consecutive
+// floats), the next K slice is prefetched into registers while the current one is multiplied.  VEC: Cin % 16 == 0,
+// so a K slice is 16 consecutive channels of one tap and each thread loads 8 of them as two 16-B loads; otherwise
+// (Conv2d_1a, Cin = 3) the slice is gathered element by element.  Padding and rows beyond M read as zeros.
+struct ConvArgs {
+    const float* x;
+    const float* w;
+    const float* bias;
+    float* y;
+    int H, W, cin, Ho, Wo, cout, kw, s, ph, pw, K, Kpad, ldo, coff, M;
+};
+
+constexpr int BM = 128, BN = 64, BK = 16;
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void conv_kernel(ConvArgs a) {
+    __shared__ float As[BK][BM];
+    __shared__ float Bs[BK][BN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    // A loader: one output pixel, 8 consecutive k of the slice
+    const int lm = tid & (BM - 1), lh = tid >> 7;
+    const int m = m0 + lm;
+    const bool mvalid = m < a.M;
+    int b = 0, oy = 0, ox = 0;
+    if (mvalid) {
+        const int hw = a.Ho * a.Wo;
+        b = m / hw;
+        const int r = m - b * hw;
+        oy = r / a.Wo;
+        ox = r - oy * a.Wo;
+    }
+    const int iy0 = oy * a.s - a.ph, ix0 = ox * a.s - a.pw;
+    const float* xb = a.x + (size_t)b * a.H * a.W * a.cin;
+    // B loader: one k row, 4 consecutive n
+    const int bk = tid >> 4, bn = n0 + (tid & 15) * 4;
+    const bool nvalid = bn < a.cout;
+
+    float ra[8];
+    f32x4 rb;
+    auto load = [&](int k0) {
+        if (VEC) {
+            const int tap = k0 / a.cin, c0 = k0 - tap * a.cin + lh * 8;
+            const int ty = tap / a.kw, tx = tap - ty * a.kw;
+            const int iy = iy0 + ty, ix = ix0 + tx;
+            if (mvalid && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
+                const float* p = xb + ((size_t)iy * a.W + ix) * a.cin + c0;
+                const f32x4 v0 = *(const f32x4*)p, v1 = *(const f32x4*)(p + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ra[j] = v0[j];
+                    ra[4 + j] = v1[j];
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ra[j] = 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = k0 + lh * 8 + j;
+                float v = 0.f;
+                if (mvalid && k < a.K) {
+                    const int tap = k / a.cin, c = k - tap * a.cin;
+                    const int ty = tap / a.kw, tx = tap - ty * a.kw;
+                    const int iy = iy0 + ty, ix = ix0 + tx;
+                    if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v = xb[((size_t)iy * a.W + ix) * a.cin + c];
+                }
+                ra[j] = v;
+            }
+        }
+        rb = nvalid ? *(const f32x4*)(a.w + (size_t)(k0 + bk) * a.cout + bn) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    };
+    auto store = [&]() {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) As[lh * 8 + j][lm] = ra[j];
+        *(f32x4*)&Bs[bk][(tid & 15) * 4] = rb;
+    };
+
+    const int wm = wave >> 1, wn = wave & 1;
+    const int l32 = lane & 31, kh = lane >> 5;
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        acc0[r] = 0.f;
+        acc1[r] = 0.f;
+    }
+    const int nk = a.Kpad / BK;
+    load(0);
+    store();
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) load((kt + 1) * BK);
+#pragma unroll
+        for (int kk = 0; kk < BK / 2; ++kk) {
+            const int kr = 2 * kk + kh;
+            const float a0 = As[kr][wm * 64 + l32];
+            const float a1 = As[kr][wm * 64 + 32 + l32];
+            const float bv = Bs[kr][wn * 32 + l32];
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, acc1, 0, 0, 0);
+        }
+        __syncthreads();
+        if (kt + 1 < nk) {
+            store();
+            __syncthreads();
+        }
+    }
+    // C/D of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    const int n = n0 + wn * 32 + l32;
+    if (n >= a.cout) return;
+    const float bias = a.bias[n];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int mA = m0 + wm * 64 + row, mB = mA + 32;
+        if (mA < a.M) a.y[(size_t)mA * a.ldo + a.coff + n] = fmaxf(acc0[r] + bias, 0.f);
+        if (mB < a.M) a.y[(size_t)mB * a.ldo + a.coff + n] = fmaxf(acc1[r] + bias, 0.f);
+    }
+}
+
+// ---- fp64 statistics: S2[i, j] += sum_b (x[b,i] - c[i]) (x[b,j] - c[j]) on v_mfma_f64_16x16x4_f64.  Workgroup = one
+// 64 x 64 tile of the upper triangle (4 waves of 32 x 32, 2 x 2 MFMA tiles), mirrored on store; inside a diagonal tile only
+// the lanes with i <= j read-modify-write, so no element is touched by two lanes.  The MFMA's k index is the sample: lane
+// l supplies sample k0 + (l >> 4) of feature (l & 15) of its sub-tile; samples beyond B contribute exact zeros.
+typedef __attribute__((ext_vector_type(4))) double f64x4;
+
+__global__ __launch_bounds__(256) void stats_s2_kernel(const float* __restrict__ x, const double* __restrict__ c,
+                                                       double* __restrict__ S2, int B, int F, int tiles) {
+    int ti = 0, rem = blockIdx.x;
+    while (rem >= tiles - ti) {
+        rem -= tiles - ti;
+        ++ti;
+    }
+    const int tj = ti + rem;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wi = wave >> 1, wj = wave & 1;
+    const int r16 = lane & 15, g = lane >> 4;
+    int fa[2], fb[2];
+    double ca[2], cb[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        fa[t] = min(ti * 64 + wi * 32 + t * 16 + r16, F - 1);
+        fb[t] = min(tj * 64 + wj * 32 + t * 16 + r16, F - 1);
+        ca[t] = c[fa[t]];
+        cb[t] = c[fb[t]];
+    }
+    f64x4 acc[2][2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) acc[p][q] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < B; k0 += 4) {
+        const int bb = k0 + g;
+        double va[2], vb[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            va[t] = bb < B ? (double)x[(size_t)bb * F + fa[t]] - ca[t] : 0.0;
+            vb[t] = bb < B ? (double)x[(size_t)bb * F + fb[t]] - cb[t] : 0.0;
+        }
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[p], vb[q], acc[p][q], 0, 0, 0);
+    }
+    // C/D of the f64 MFMA: column = lane & 15 (operand B's row), row = (lane >> 4) + 4 * reg (operand A's row)
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = ti * 64 + wi * 32 + p * 16 + g + 4 * r;
+                const int j = tj * 64 + wj * 32 + q * 16 + r16;
+                if (i < F && j < F && i <= j) {
+                    const double v = S2[(size_t)i * F + j] + acc[p][q][r];
+                    S2[(size_t)i * F + j] = v;
+                    S2[(size_t)j * F + i] = v;
+                }
+            }
+}
+
+// S1[f] += sum_b (x[b,f] - c[f]), in sample order
+__global__ __launch_bounds__(256) void stats_s1_kernel(const float* __restrict__ x, const double* __restrict__ c,
+                                                       double* __restrict__ S1, int B, int F) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F) return;
+    const double cf = c[f];
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += (double)x[(size_t)b * F + f] - cf;
+    S1[f] += s;
+}
+
+// ---- host side: the forward as a sequence of launches over the workspace
+struct Act {
+    float* p;
+    int H, W, C;
+};
+
+struct Runner {
+    const float* blob;
+    hipStream_t st;
+    int B;
+    int conv_i = 0;
+
+    int conv(const Act& in, float* out, int ldo, int coff, Act* res) {
+        const ConvSpec& c = conv_specs()[conv_i];
+        const BlobLayout& L = blob_layout();
+        if (c.cin != in.C) return USPACE_ERR_ARG;
+        ConvArgs a;
+        a.x = in.p;
+        a.w = blob + L.w_off[conv_i];
+        a.bias = blob + L.b_off[conv_i];
+        a.y = out;
+        a.H = in.H;
+        a.W = in.W;
+        a.cin = c.cin;
+        a.Ho = (in.H + 2 * c.ph - c.kh) / c.s + 1;
+        a.Wo = (in.W + 2 * c.pw - c.kw) / c.s + 1;
+        a.cout = c.cout;
+        a.kw = c.kw;
+        a.s = c.s;
+        a.ph = c.ph;
+        a.pw = c.pw;
+        a.K = conv_k(c);
+        a.Kpad = conv_kpad(c);
+        a.ldo = ldo;
+        a.coff = coff;
+        a.M = B * a.Ho * a.Wo;
+        ++conv_i;
+        const dim3 grid(us_cdiv(a.M, BM), us_cdiv(c.cout, BN));
+        if (c.cin % 16 == 0)
+            hipLaunchKernelGGL(conv_kernel<true>, grid, dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL(conv_kernel<false>, grid, dim3(256), 0, st, a);
+        US_CHECK_LAUNCH();
+        if (res) *res = {out, a.Ho, a.Wo, ldo};
+        return USPACE_OK;
+    }
+    // 3 x 3 pool of `in` (stride s, padding p) into out at channel offset coff of rows of ldo channels
+    int pool(const Act& in, bool mx, int s, int p, float* out, int ldo, int coff, Act* res) {
+        const int Ho = (in.H + 2 * p - 3) / s + 1, Wo = (in.W + 2 * p - 3) / s + 1;
+        const long n = (long)B * Ho * Wo * (in.C / 4);
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        if (mx)
+            hipLaunchKernelGGL(pool3_kernel<true>, dim3(blocks), dim3(256), 0, st, in.p, out, B, in.H, in.W, in.C, s, p, Ho, Wo,
+                               ldo, coff);
+        else
+            hipLaunchKernelGGL(pool3_kernel<false>, dim3(blocks), dim3(256), 0, st, in.p, out, B, in.H, in.W, in.C, s, p, Ho,
+                               Wo, ldo, coff);
+        US_CHECK_LAUNCH();
+        if (res) *res = {out, Ho, Wo, ldo};
+        return USPACE_OK;
+    }
+};
+
+struct Work {
+    float *P, *Q, *T1, *T2, *T3;
+};
+
+size_t workspace_bytes_for(int B) { return (size_t)B * (2 * kBigPer + 3 * kTmpPer) * sizeof(float); }
+
+Work carve(void* ws, int B) {
+    float* f = (float*)ws;
+    Work w;
+    w.P = f;
+    w.Q = w.P + (size_t)B * kBigPer;
+    w.T1 = w.Q + (size_t)B * kBigPer;
+    w.T2 = w.T1 + (size_t)B * kTmpPer;
+    w.T3 = w.T2 + (size_t)B * kTmpPer;
+    return w;
+}
+
+// InceptionA (FID): 1x1 | 1x1 -> 5x5 | 1x1 -> 3x3 -> 3x3 | avg-pool (excl. pad) -> 1x1
+int block_a(Runner& R, const Act& x, float* y, const Work& w, int pool_ch, Act* out) {
+    const int ld = 64 + 64 + 96 + pool_ch;
+    Act t1, t2, t3;
+    US_TRY(R.conv(x, y, ld, 0, nullptr));
+    US_TRY(R.conv(x, w.T1, 48, 0, &t1));
+    US_TRY(R.conv(t1, y, ld, 64, nullptr));
+    US_TRY(R.conv(x, w.T1, 64, 0, &t1));
+    US_TRY(R.conv(t1, w.T2, 96, 0, &t2));
+    US_TRY(R.conv(t2, y, ld, 128, nullptr));
+    US_TRY(R.pool(x, false, 1, 1, w.T3, x.C, 0, &t3));
+    US_TRY(R.conv(t3, y, ld, 224, out));
+    out->C = ld;
+    return USPACE_OK;
+}
+
+// InceptionB: 3x3 s2 | 1x1 -> 3x3 -> 3x3 s2 | max-pool 3/2
+int block_b(Runner& R, const Act& x, float* y, const Work& w, Act* out) {
+    const int ld = 384 + 96 + x.C;
+    Act t1, t2;
+    US_TRY(R.conv(x, y, ld, 0, out));
+    US_TRY(R.conv(x, w.T1, 64, 0, &t1));
+    US_TRY(R.conv(t1, w.T2, 96, 0, &t2));
+    US_TRY(R.conv(t2, y, ld, 384, nullptr));
+    US_TRY(R.pool(x, true, 2, 0, y, ld, 480, nullptr));
+    out->C = ld;
+    return USPACE_OK;
+}
+
+// InceptionC (FID): 1x1 | 1x1 -> 1x7 -> 7x1 | 1x1 -> 7x1 -> 1x7 -> 7x1 -> 1x7 | avg-pool (excl. pad) -> 1x1
+int block_c(Runner& R, const Act& x, float* y, const Work& w, int c7, Act* out) {
+    const int ld = 768;
+    Act t1, t2, t3;
+    US_TRY(R.conv(x, y, ld, 0, out));
+    US_TRY(R.conv(x, w.T1, c7, 0, &t1));
+    US_TRY(R.conv(t1, w.T2, c7, 0, &t2));
+    US_TRY(R.conv(t2, y, ld, 192, nullptr));
+    US_TRY(R.conv(x, w.T1, c7, 0, &t1));
+    US_TRY(R.conv(t1, w.T2, c7, 0, &t2));
+    US_TRY(R.conv(t2, w.T1, c7, 0, &t1));
+    US_TRY(R.conv(t1, w.T2, c7, 0, &t2));
+    US_TRY(R.conv(t2, y, ld, 384, nullptr));
+    US_TRY(R.pool(x, false, 1, 1, w.T3, x.C, 0, &t3));
+    US_TRY(R.conv(t3, y, ld, 576, nullptr));
+    out->C = ld;
+    return USPACE_OK;
+}
+
+// InceptionD: 1x1 -> 3x3 s2 | 1x1 -> 1x7 -> 7x1 -> 3x3 s2 | max-pool 3/2
+int block_d(Runner& R, const Act& x, float* y, const Work& w, Act* out) {
+    const int ld = 320 + 192 + x.C;
+    Act t1, t2;
+    US_TRY(R.conv(x, w.T1, 192, 0, &t1));
+    US_TRY(R.conv(t1, y, ld, 0, out));
+    US_TRY(R.conv(x, w.T1, 192, 0, &t1));
+    US_TRY(R.conv(t1, w.T2, 192, 0, &t2));
+    US_TRY(R.conv(t2, w.T1, 192, 0, &t1));
+    US_TRY(R.conv(t1, y, ld, 320, nullptr));
+    US_TRY(R.pool(x, true, 2, 0, y, ld, 512, nullptr));
+    out->C = ld;
+    return USPACE_OK;
+}
+
+// InceptionE (FID): 1x1 | 1x1 -> [1x3, 3x1] | 1x1 -> 3x3 -> [1x3, 3x1] | pool (avg excl. pad; max in Mixed_7c) -> 1x1
+int block_e(Runner& R, const Act& x, float* y, const Work& w, bool max_pool, Act* out) {
+    const int ld = 2048;
+    Act t1, t2, t3;
+    US_TRY(R.conv(x, y, ld, 0, out));
+    US_TRY(R.conv(x, w.T1, 384, 0, &t1));
+    US_TRY(R.conv(t1, y, ld, 320, nullptr));
+    US_TRY(R.conv(t1, y, ld, 704, nullptr));
+    US_TRY(R.conv(x, w.T1, 448, 0, &t1));
+    US_TRY(R.conv(t1, w.T2, 384, 0, &t2));
+    US_TRY(R.conv(t2, y, ld, 1088, nullptr));
+    US_TRY(R.conv(t2, y, ld, 1472, nullptr));
+    US_TRY(R.pool(x, max_pool, 1, 1, w.T3, x.C, 0, &t3));
+    US_TRY(R.conv(t3, y, ld, 1856, nullptr));
+    out->C = ld;
+    return USPACE_OK;
+}
+
+int spatial_mean(const Act& a, float* feat, int B, hipStream_t st) {
+    const long n = (long)B * a.C;
+    hipLaunchKernelGGL(spatial_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.p, feat, B, a.H * a.W, a.C);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+// Runs stages 0 .. last.  With tap_out, copies stage `last` (NHWC, or [B, 2048] for stage 19) there; with feat, writes
+// the spatial mean of stage `last` (4, 7, 15 or 18) to feat [B, C].
+int run(const void* blob, void* ws, size_t ws_bytes, const float* x, int B, int H, int W, int last, float* tap_out,
+        float* feat, hipStream_t st) {
+    if (!blob || !ws || !x || B <= 0 || H <= 0 || W <= 0 || last < 0 || last >= kNumStages) return USPACE_ERR_ARG;
+    // every NHWC tensor (and the input) stays below 2^31 elements
+    if ((long)B * kBigPer >= (1L << 31) || (long)B * 3 * H * W >= (1L << 31)) return USPACE_ERR_ARG;
+    if (ws_bytes < workspace_bytes_for(B)) return USPACE_ERR_WORKSPACE;
+    const Work w = carve(ws, B);
+    Runner R{(const float*)blob, st, B};
+    int stage = 0;
+    Act cur{w.T1, kIn, kIn, 3};
+    {
+        const long n = (long)B * kIn * kIn;
+        hipLaunchKernelGGL(resize_input_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, w.T1, B, H, W);
+        US_CHECK_LAUNCH();
+    }
+    float* bufs[2] = {w.P, w.Q};
+    int nb = 0;
+    auto next = [&]() { float* p = bufs[nb]; nb ^= 1; return p; };
+    // stem and the blocks, one stage each
+    for (stage = 1; stage <= last && stage <= 18; ++stage) {
+        Act o;
+        float* y = next();
+        switch (stage) {
+            case 1: case 2: case 3: case 5: case 6: US_TRY(R.conv(cur, y, conv_specs()[R.conv_i].cout, 0, &o)); break;
+            case 4: case 7: US_TRY(R.pool(cur, true, 2, 0, y, cur.C, 0, &o)); break;
+            case 8: US_TRY(block_a(R, cur, y, w, 32, &o)); break;
+            case 9: case 10: US_TRY(block_a(R, cur, y, w, 64, &o)); break;
+            case 11: US_TRY(block_b(R, cur, y, w, &o)); break;
+            case 12: US_TRY(block_c(R, cur, y, w, 128, &o)); break;
+            case 13: case 14: US_TRY(block_c(R, cur, y, w, 160, &o)); break;
+            case 15: US_TRY(block_c(R, cur, y, w, 192, &o)); break;
+            case 16: US_TRY(block_d(R, cur, y, w, &o)); break;
+            case 17: US_TRY(block_e(R, cur, y, w, false, &o)); break;
+            case 18: US_TRY(block_e(R, cur, y, w, true, &o)); break;
+        }
+        o.p = y;
+        cur = o;
+    }
+    if (tap_out) {
+        if (last == 19) return spatial_mean(cur, tap_out, B, st);
+        const size_t bytes = (size_t)B * cur.H * cur.W * cur.C * sizeof(float);
+        if (hipMemcpyAsync(tap_out, cur.p, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return USPACE_ERR_LAUNCH;
+        return USPACE_OK;
+    }
+    return spatial_mean(cur, feat, B, st);
+}
+
+}  // namespace
+
+extern "C" int uspace_inception_num_params(void) { return kNumConvs * kParamsPerConv; }
+
+extern "C" long uspace_inception_param_numel(int index) {
+    if (index < 0 || index >= kNumConvs * kParamsPerConv) return -1;
+    const ConvSpec& c = conv_specs()[index / kParamsPerConv];
+    return index % kParamsPerConv == 0 ? (long)c.cout * c.cin * c.kh * c.kw : (long)c.cout;
+}
+
+extern "C" size_t uspace_inception_weight_bytes(void) { return blob_layout().floats * sizeof(float); }
+
+extern "C" size_t uspace_inception_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return workspace_bytes_for(B);
+}
+
+extern "C" int uspace_inception_pack_weights(const float* const* params, int n_params, void* blob, size_t blob_bytes,
+                                             uspace_stream_t stream) {
+    if (!params || !blob || n_params != kNumConvs * kParamsPerConv) return USPACE_ERR_ARG;
+    const BlobLayout& L = blob_layout();
+    if (blob_bytes < L.floats * sizeof(float)) return USPACE_ERR_WORKSPACE;
+    for (int i = 0; i < kNumConvs * kParamsPerConv; ++i)
+        if (!params[i]) return USPACE_ERR_ARG;
+    float* out = (float*)blob;
+    for (int i = 0; i < kNumConvs; ++i) {
+        const ConvSpec& c = conv_specs()[i];
+        const float* const* p = params + i * kParamsPerConv;
+        const long n = (long)conv_kpad(c) * c.cout + c.cout;
+        hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p[0], p[1],
+                           p[2], p[3], p[4], out + L.w_off[i], out + L.b_off[i], c.cin, c.cout, c.kh, c.kw, conv_k(c),
+                           conv_kpad(c));
+        US_CHECK_LAUNCH();
+    }
+    return USPACE_OK;
+}
+
+extern "C" int uspace_inception_forward(const void* blob, void* workspace, size_t workspace_bytes, const float* x, int B,
+                                        int H, int W, int last_block, float* feat, uspace_stream_t stream) {
+    static const int block_stage[4] = {4, 7, 15, 18};
+    if (!feat || last_block < 0 || last_block > 3) return USPACE_ERR_ARG;
+    return run(blob, workspace, workspace_bytes, x, B, H, W, block_stage[last_block], nullptr, feat, (hipStream_t)stream);
+}
+
+extern "C" int uspace_inception_tap(const void* blob, void* workspace, size_t workspace_bytes, const float* x, int B, int H,
+                                    int W, int stage, float* out, uspace_stream_t stream) {
+    if (!out) return USPACE_ERR_ARG;
+    return run(blob, workspace, workspace_bytes, x, B, H, W, stage, out, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int uspace_fid_stats_accumulate(const float* feat, int B, int F, const double* shift, double* s1, double* s2,
+                                           uspace_stream_t stream) {
+    if (!feat || !shift || !s1 || !s2 || B <= 0 || F <= 0 || (long)B * F >= (1L << 31)) return USPACE_ERR_ARG;
+    const int tiles = us_cdiv(F, 64);
+    const long blocks = (long)tiles * (tiles + 1) / 2;
+    hipLaunchKernelGGL(stats_s2_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, feat, shift, s2, B, F, tiles);
+    US_CHECK_LAUNCH();
+    hipLaunchKernelGGL(stats_s1_kernel, dim3(us_cdiv(F, 256)), dim3(256), 0, (hipStream_t)stream, feat, shift, s1, B, F);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
