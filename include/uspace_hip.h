@@ -182,6 +182,16 @@ USPACE_API int uspace_layernorm_f32_bf16(const float* x, const float* gamma, con
 USPACE_API int uspace_attention_bf16(const uint16_t* qkv, const float* key_scale, uint16_t* out,
                           int B, int L, int H, uspace_stream_t stream);
 
+/* Head-mean attention map of the same packed qkv (what tools/utils_t2i.py:141-193 vis_attention_map draws from the reference's
+ * [B, H, L, L] softmax, libs/uvit_t2i.py:101-103):
+ *     out[b, i, j] = (1/H) * sum_h softmax_k( q[b,h,q0+i] . k[b,h,k] * 64^-0.5 )[k0+j]       fp32, [B, nq, nk]
+ * The softmax runs over ALL L keys, not the window.  No key_scale: the reference shows the map before the edit
+ * (tools/utils_t2i.py:283 precedes :286).  P stays fp32; the heads are summed in the order 0 .. H-1 by the one workgroup that owns
+ * a (sample, 16-query tile): no atomics, bit-equal from run to run and for any B.  head_dim 64, L <= 336, 0 <= q0, nq >= 1,
+ * q0 + nq <= L and the same for k0 / nk; anything else returns USPACE_ERR_ARG. */
+USPACE_API int uspace_attention_map_bf16(const uint16_t* qkv, float* out, int B, int L, int H,
+                                         int q0, int nq, int k0, int nk, uspace_stream_t stream);
+
 /* Token assembly (libs/uvit.py:315-327, libs/uvit_t2i.py:309-324): patch-embed conv (k=s=p) +
  * sinusoidal time token + optional extra tokens + pos_embed, fp32 -> residual stream
  * tok[B, L, D] fp32 (+ bf16 copy if tok_bf16 != NULL).
@@ -304,6 +314,15 @@ typedef struct uspace_uvit_io {
 
 USPACE_API int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* blob, void* workspace,
                         size_t workspace_bytes, const uspace_uvit_io* io, int B, uspace_stream_t stream);
+
+/* uspace_uvit_forward, and after every block's qkv GEMM the head-mean map (uspace_attention_map_bf16, window q0 / nq / k0 / nk) of
+ * that block's attention into maps[(i * B + b) * nq * nk ...], i = 0 .. depth (in-blocks, mid, out-blocks = the reference's
+ * _counter["block_id"], libs/uvit_t2i.py:107,316).  maps: caller-owned device float[(depth + 1) * B * nq * nk]; the workspace is that
+ * of uspace_uvit_forward.  Every other launch is the one uspace_uvit_forward issues, in the same order, so io->out is bit-equal to
+ * its; io->key_scale edits io->out and the later blocks as there, never the map of the block it is applied in. */
+USPACE_API int uspace_uvit_forward_maps(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                        const uspace_uvit_io* io, int B, int q0, int nq, int k0, int nk, float* maps,
+                                        uspace_stream_t stream);
 
 /* Test aid: run the forward exactly as uspace_uvit_forward does up to the end of stage `stop_after`, then copy the fp32 residual
  * stream x [B,L,D] to `dump` (device) and return.  Stages: 0 the tokens after embed + pos_embed, as block 0 reads them; k = 1 ..

@@ -83,6 +83,7 @@ SIGNATURES = {
     "uspace_gemm_slabs_bf16": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_I), _I, _P, _P, _I, _P, _I, _P, _I, _P]),
     "uspace_layernorm_f32_bf16": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "uspace_attention_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "uspace_attention_map_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "uspace_embed_tokens": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "uspace_output_head": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "uspace_add_broadcast": (_I, [_P, _P, _P, _F, _I, _L, _P]),
@@ -101,6 +102,7 @@ SIGNATURES = {
     "uspace_uvit_workspace_bytes": (_SZ, [ctypes.POINTER(UvitConfig), _I]),
     "uspace_uvit_pack_weights": (_I, [ctypes.POINTER(UvitConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
     "uspace_uvit_forward": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _P]),
+    "uspace_uvit_forward_maps": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _I, _I, _I, _I, _P, _P]),
     "uspace_uvit_forward_tap": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _I, _P, _P]),
     "uspace_uvit_graph_create": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _P,
                                       ctypes.POINTER(_P)]),
@@ -295,6 +297,17 @@ def attention(qkv, B, L, H, key_scale=None):
     out = torch.empty(B * L, H * 64, dtype=torch.bfloat16, device=qkv.device)
     check(lib().uspace_attention_bf16(ptr(qkv), ptr(key_scale), ptr(out), B, L, H, stream_ptr()),
           "uspace_attention_bf16")
+    return out
+
+
+def attention_map(qkv, B, L, H, q0, nq, k0, nk):
+    """Head-mean softmax map of the packed bf16 qkv [B * L, 3 * H * 64]: rows q0 .. q0 + nq - 1, columns k0 .. k0 + nk - 1 of the
+    [L, L] map (softmax over all L keys) -> fp32 [B, nq, nk]."""
+    require_device(qkv, "qkv")
+    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.numel() == B * L * 3 * H * 64
+    out = torch.empty(B, max(int(nq), 0), max(int(nk), 0), dtype=torch.float32, device=qkv.device)
+    check(lib().uspace_attention_map_bf16(ptr(qkv), ptr(out), B, L, H, int(q0), int(nq), int(k0), int(nk), stream_ptr()),
+          "uspace_attention_map_bf16")
     return out
 
 

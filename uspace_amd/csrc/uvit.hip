@@ -252,9 +252,12 @@ extern "C" int uspace_uvit_get_ln_fold(void) { return g_ln_fold.load(); }
 namespace {
 // The forward; stop_after >= 0 (uspace_uvit_forward_tap) copies the residual stream x to `dump` after stage stop_after and
 // returns there (the last stage, depth + 1, runs the head first).  stop_after = -1 is the product forward: the launch sequence
-// is the same for every stop_after up to the stop.
+// is the same for every stop_after up to the stop.  maps != NULL (uspace_uvit_forward_maps): one more launch per block, the head-mean
+// attention map of the window mw = {q0, nq, k0, nk} right after the block's qkv GEMM; with maps == NULL the launch sequence is
+// the product forward's.
+struct MapWindow { int q0, nq, k0, nk; };
 int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes, const uspace_uvit_io* io,
-                 int B, int stop_after, float* dump, uspace_stream_t stream) {
+                 int B, int stop_after, float* dump, uspace_stream_t stream, float* maps = nullptr, MapWindow mw = MapWindow{0, 0, 0, 0}) {
     if (!valid_cfg(cfg) || !blob || !workspace || !io || B <= 0) return USPACE_ERR_ARG;
     if (stop_after >= 0 && (!dump || stop_after > cfg->depth + 1)) return USPACE_ERR_ARG;
     if (!io->x || !io->t || !io->out) return USPACE_ERR_ARG;
@@ -269,6 +272,8 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
 
     const int D = c.embed_dim, Hd = c.mlp_hidden, L = m.L, H = c.num_heads;
     const int M = B * L;
+    if (maps && (mw.q0 < 0 || mw.nq < 1 || mw.q0 > L - mw.nq || mw.k0 < 0 || mw.nk < 1 || mw.k0 > L - mw.nk)) return USPACE_ERR_ARG;
+    const size_t map_stride = maps ? (size_t)B * mw.nq * mw.nk : 0;      // floats per block
     const char* wb = (const char*)blob;
     char* ws = (char*)workspace;
     auto PF = [&](int idx) { return (const float*)(wb + m.lay.p[idx].offset); };
@@ -378,6 +383,7 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
             cons.colsum = PFx(b.qkv_cs);
             US_TRY(us_gemm_bf16_ext(cen_in, D, nullptr, 0, D, PH(b.qkv_f), D, M, 3 * D, D, L_ | B_ | H_, PFx(b.qkv_fb), nullptr, 0,
                                     nullptr, 0, qkv, 3 * D, &cons, sk_on, stream));
+            if (maps) US_TRY(uspace_attention_map_bf16(qkv, maps + (size_t)i * map_stride, B, L, H, mw.q0, mw.nq, mw.k0, mw.nk, stream));
             const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
             US_TRY(uspace_attention_bf16(qkv, ks, h, B, L, H, stream));
             US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, C_ | B_ | R_ | F_, PF(b.projb), x, D, x, D,
@@ -429,6 +435,7 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
         US_TRY(uspace_layernorm_f32_bf16(x, PF(b.n1w), PF(b.n1b), h, M, D, 1e-5f, stream));
         US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.qkv), D, M, 3 * D, D, H_, nullptr, nullptr, 0, nullptr, 0,
                                 qkv, 3 * D, nullptr, sk_on, stream));
+        if (maps) US_TRY(uspace_attention_map_bf16(qkv, maps + (size_t)i * map_stride, B, L, H, mw.q0, mw.nq, mw.k0, mw.nk, stream));
         const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
         US_TRY(uspace_attention_bf16(qkv, ks, h, B, L, H, stream));
         US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, B_ | R_ | F_, PF(b.projb), x, D, x, D,
@@ -472,6 +479,13 @@ extern "C" int uspace_uvit_forward_tap(const uspace_uvit_config* cfg, const void
                                        const uspace_uvit_io* io, int B, int stop_after, float* dump, uspace_stream_t stream) {
     if (stop_after < 0) return USPACE_ERR_ARG;
     return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, stop_after, dump, stream);
+}
+
+extern "C" int uspace_uvit_forward_maps(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                        const uspace_uvit_io* io, int B, int q0, int nq, int k0, int nk, float* maps,
+                                        uspace_stream_t stream) {
+    if (!maps) return USPACE_ERR_ARG;
+    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, -1, nullptr, stream, maps, MapWindow{q0, nq, k0, nk});
 }
 
 // ------------------------------------------------------------------------------------------

@@ -284,16 +284,27 @@ class UViTBase(nn.Module):
 
     # ------------------------------------------------------------------ the single HIP call
     def _run(self, x, timesteps, context=None, mid_delta=None, mid_scale=0.0, mid_tap=None, key_scale=None,
-             mid_row_scale=None, keep_f32=False):
-        """``keep_f32``: return the fp32 result even for a half-precision ``x`` (the caller still has fp32 work to do)."""
+             mid_row_scale=None, keep_f32=False, attn_maps=None):
+        """``keep_f32``: return the fp32 result even for a half-precision ``x`` (the caller still has fp32 work to do).
+        ``attn_maps``: a ``(q0, nq, k0, nk)`` token window; the call then goes through ``uspace_uvit_forward_maps`` and returns
+        ``(out, maps)`` with maps [depth + 1, B, nq, nk] fp32, the head-mean attention map of every block (before any ``key_scale``
+        edit of that block).  A maps evaluation always runs eagerly, never through the captured hipGraph: the graph holds the plain
+        launch sequence and its own static buffers, which a maps evaluation neither replays nor touches."""
         _hip.require_device(x, "x")
         if x.dim() != 4 or x.shape[1] != self.in_chans or x.shape[2] != self.img_size or x.shape[3] != self.img_size:
             raise ValueError(f"x must be [B,{self.in_chans},{self.img_size},{self.img_size}], got {tuple(x.shape)}")
         B = x.shape[0]
         dev = x.device
+        if attn_maps is not None:
+            q0, nq, k0, nk = (int(v) for v in attn_maps)
+            if q0 < 0 or nq < 1 or q0 + nq > self.seq_len or k0 < 0 or nk < 1 or k0 + nk > self.seq_len:
+                raise ValueError(f"attn_maps window {(q0, nq, k0, nk)} does not lie inside the {self.seq_len} tokens")
         if B == 0:                                  # empty batch: the reference returns an empty prediction
-            return torch.empty(0, self.in_chans, self.img_size, self.img_size,
-                               dtype=torch.float32 if keep_f32 else x.dtype, device=dev)
+            empty = torch.empty(0, self.in_chans, self.img_size, self.img_size,
+                                dtype=torch.float32 if keep_f32 else x.dtype, device=dev)
+            if attn_maps is not None:
+                return empty, torch.empty(self.depth + 1, 0, nq, nk, dtype=torch.float32, device=dev)
+            return empty
         xin = x.detach().to(torch.float32).contiguous()
         t = timesteps
         if not torch.is_tensor(t):
@@ -308,7 +319,7 @@ class UViTBase(nn.Module):
             if t_stride not in (0, 1):
                 t = t.contiguous(); t_stride = 1
         plain = mid_delta is None and mid_tap is None and key_scale is None
-        if self.use_graph and plain and t_stride == 0:
+        if self.use_graph and plain and t_stride == 0 and attn_maps is None:
             return self._run_graph(xin, t, context, B, dev, torch.float32 if keep_f32 else x.dtype)
         out = torch.empty(B, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev)
         blob = self._packed_blob(dev)
@@ -316,6 +327,12 @@ class UViTBase(nn.Module):
         io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta),
                          float(mid_scale), _hip.ptr(mid_tap), _hip.ptr(key_scale), _hip.ptr(out),
                          _hip.ptr(mid_row_scale))
+        if attn_maps is not None:
+            maps = torch.empty(self.depth + 1, B, nq, nk, dtype=torch.float32, device=dev)
+            _hip.check(_hip.lib().uspace_uvit_forward_maps(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
+                                                           ctypes.byref(io), B, q0, nq, k0, nk, _hip.ptr(maps), _hip.stream_ptr()),
+                       "uspace_uvit_forward_maps")
+            return (out if (keep_f32 or x.dtype == torch.float32) else out.to(x.dtype)), maps
         _hip.check(_hip.lib().uspace_uvit_forward(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
                                                   ctypes.byref(io), B, _hip.stream_ptr()), "uspace_uvit_forward")
         return out if (keep_f32 or x.dtype == torch.float32) else out.to(x.dtype)

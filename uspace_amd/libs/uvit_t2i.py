@@ -5,6 +5,9 @@
 77 CLIP context tokens are embedded by the HIP GEMM and prepended after the time token.
 The prompt-to-prompt attention-map edit (dissect_name in {p2p, local_prompt,
 sampled_image_editing}) is applied inside the fused attention kernel as a per-key factor.
+The map itself -- the reference's ``vis_am_path`` pictures (tools/utils_t2i.py:141-193) and
+``attention_maps`` -- comes from a kernel of its own (csrc/attention_map.hip): the fused kernel
+never holds it.
 """
 import numpy as np
 import torch
@@ -45,7 +48,9 @@ class UViT(UViTBase):
     def _extra_canonical(self):
         return [self.context_embed.weight, self.context_embed.bias]
 
-    def forward(self, x, timesteps, context, **kwargs):
+    def _prepare(self, x, timesteps, context, kwargs):
+        """What ``forward`` and ``attention_maps`` share: the checked fp32 context, this step's key_scale table (or None) and the
+        timestep digit (None off the attention-edit path).  One place, so that a map always sees the edit ``forward`` applies."""
         _hip.require_device(x, "x")
         B = x.shape[0]
         dev = x.device
@@ -53,14 +58,40 @@ class UViT(UViTBase):
                 or context.shape[2] != self.clip_dim:
             raise ValueError(f"context must be [{B},{self.num_clip_token},{self.clip_dim}], got {tuple(context.shape)}")
         ctx = context.detach().to(device=dev, dtype=torch.float32).contiguous()   # libs/uvit_t2i.py:318
-        key_scale = None
+        key_scale = digit = None
         if utils_t2i.uses_attention_edit_path(kwargs):
             digit = timestep_digit(host_timestep(timesteps, kwargs))
             table = utils_t2i.key_scale_table(self.depth + 1, B, self.seq_len, digit, kwargs)
             if table is not None:
                 key_scale = self._device_table(table, dev)
-        out = self._run(x, timesteps, context=ctx, key_scale=key_scale)
+        return ctx, key_scale, digit
+
+    def forward(self, x, timesteps, context, **kwargs):
+        ctx, key_scale, digit = self._prepare(x, timesteps, context, kwargs)
+        # tools/utils_t2i.py:279-283: on the edit path the decode direction shows the map (before the edit) when vis_am_path is set
+        if not (digit in utils_t2i.VIS_DIGITS and kwargs.get("fm_direction") == "decode" and kwargs.get("vis_am_path") is not None):
+            return self._run(x, timesteps, context=ctx, key_scale=key_scale), None
+        window = self.token_range("image") + self.token_range("context")
+        out, maps = self._run(x, timesteps, context=ctx, key_scale=key_scale, attn_maps=window)
+        kw = {k: v for k, v in kwargs.items() if k != "grid"}
+        utils_t2i.vis_attention_map(maps, digit, grid=self.img_size // self.patch_size, **kw)
         return out, None
+
+    def token_range(self, name):
+        """(first token, count) of ``"image"``, ``"context"``, ``"time"`` or ``"all"`` in this network's token order: time (1),
+        context (``num_clip_token``), image."""
+        return utils_t2i.token_range(name, self.num_clip_token, self.num_patches)
+
+    def attention_maps(self, x, timesteps, context, queries="image", keys="context", **kwargs):
+        """Head-mean attention map of every block, [depth + 1, B, nq, nk] fp32 (block order: in-blocks, mid, out-blocks = the
+        reference's ``_counter["block_id"]``): rows ``queries``, columns ``keys`` of the [L, L] softmax, each ``"image"``, ``"context"``,
+        ``"time"``, ``"all"`` or an explicit ``(first, count)``.  The softmax runs over all L keys.  ``kwargs`` are those of
+        ``forward``: a live p2p edit acts on the prediction and on the later blocks, the map of a block is always the one before its
+        edit.  With ``queries="image", keys="image"`` this is the input of the reference's tools/attention_vis.py:54
+        show_self_attention_comp.  Nothing is written, whatever ``vis_am_path`` says."""
+        ctx, key_scale, _ = self._prepare(x, timesteps, context, kwargs)
+        window = self.token_range(queries) + self.token_range(keys)
+        return self._run(x, timesteps, context=ctx, key_scale=key_scale, attn_maps=window)[1]
 
     def _device_table(self, table, dev):
         key = (table.shape, hash(table.tobytes()), str(dev))
