@@ -178,9 +178,15 @@ USPACE_API int uspace_layernorm_f32_bf16(const float* x, const float* gamma, con
  * qkv [B*L, 3*H*64] bf16 with columns ordered (3, H, 64); out [B*L, H*64] bf16.
  * key_scale (optional, [B, L] fp32): the post-softmax map is multiplied column-wise by it
  * before P.V, without renormalisation -- the attention-map edit of
- * tools/utils_t2i.py:196-224 at libs/uvit_t2i.py:101-105, applied as a row scaling of V. */
+ * tools/utils_t2i.py:196-224 at libs/uvit_t2i.py:101-105, applied as a row scaling of V.
+ * L <= 336; which kernel form and grid a call launches: uspace_attention_plan. */
 USPACE_API int uspace_attention_bf16(const uint16_t* qkv, const float* key_scale, uint16_t* out,
                           int B, int L, int H, uspace_stream_t stream);
+/* host-side, no GPU work: out[8] = {NT, LC, NW, QS, HPW, grid, block, dynamic LDS bytes} of the launch
+ * uspace_attention_bf16 takes for (B, L, H, key_scale != NULL); USPACE_ERR_ARG where that call would refuse.
+ * NT 16-key tiles the kernel is compiled for, LC its compile-time length (0 = any length up to 16 NT), NW waves per workgroup,
+ * QS workgroups per (batch, head), HPW heads per workgroup. */
+USPACE_API int uspace_attention_plan(int B, int L, int H, int scaled, int* out);
 
 /* Head-mean attention map of the same packed qkv (what tools/utils_t2i.py:141-193 vis_attention_map draws from the reference's
  * [B, H, L, L] softmax, libs/uvit_t2i.py:101-103):

@@ -18,8 +18,8 @@ DATA_SETS = ("workflow", "flat", "sharp", "voff", "edges")
 
 
 # ------------------------------------------------------------------------------------------------------------------ dispatch
-# Mirrors, in attention.hip: uspace_attention_bf16 (L -> NT, LC), launch_attn (NT -> NW, key_scale -> SCALED) and launch_attn2
-# (B * H -> QS, HPW and the grid).  tests/test_attention_cases.py ties it to the built library.
+# Mirrors att_plan of attention.hip: L -> NT, LC; NT -> NW; key_scale -> SCALED; B * H -> QS, HPW and the grid.
+# tests/test_attention_cases.py ties it to the built library: to its kernels and to uspace_attention_plan.
 def _instantiation(L):
     nt = (L + 15) // 16
     if L == 257:
@@ -33,7 +33,7 @@ def _instantiation(L):
 
 
 def launch_branch(B, L, H, scaled):
-    """Which of the five launches of launch_attn2 a call takes: 'small' (QS = ceil(NT / NW) workgroups per head), 'two' (QS = 2),
+    """Which of the five launches of att_plan a call takes: 'small' (QS = ceil(NT / NW) workgroups per head), 'two' (QS = 2),
     'hpw2' / 'hpw4' (two / four heads per workgroup) or 'one' (one workgroup per head)."""
     NT, LC = _instantiation(L)
     NW = 8 if NT > 17 else 4
@@ -75,7 +75,7 @@ def launch_grid(B, L, H, scaled):
 
 
 def all_launches():
-    """Every (NT, LC, scaled, branch) launch_attn2 can take: 38.  They are 36 distinct kernels: with NT = 6 on four waves
+    """Every (NT, LC, scaled, branch) att_plan can take: 38.  They are 36 distinct kernels: with NT = 6 on four waves
     ceil(NT / NW) is 2, so 'small' and 'two' launch the same instantiation."""
     out = []
     for NT, LC in INSTANTIATIONS:
@@ -102,7 +102,7 @@ def case_launch(case):
     return NT, LC, bool(scaled), launch_branch(B, L, H, scaled)
 
 
-# (B, L, H, scaled, data set).  Every launch of all_launches(); B * H on both sides of every switch of launch_attn2 at L = 334 (64 / 65,
+# (B, L, H, scaled, data set).  Every launch of all_launches(); B * H on both sides of every switch of att_plan at L = 334 (64 / 65,
 # 128 / 129, 256 / 257, 512 / 513, 768 / 769, 1024 / 1040; H = 1 gives any product); several-heads launches whose last workgroups own
 # fewer heads than the others ((257, 334, 1), (513, 334, 1), (37, 334, 16)); L on both sides of every tile count the dispatch switches
 # at and at exact tile multiples.  'flat' is the most frequent set: it is the one that sees a wrong mask or row sum.

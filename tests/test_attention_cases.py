@@ -1,6 +1,7 @@
 """tests/attention_cases.py pinned on the CPU: its mirror of the attention launch dispatch against the kernels the built library
 holds, the coverage of its case list, and the sensitivity of every bound of tests/test_gpu_attention_parity.py -- each faulty
 reference must lie at least twice the bound away from the true one, in the metric the GPU test uses."""
+import ctypes
 import importlib.util
 import os
 import re
@@ -69,7 +70,7 @@ def test_mirror_boundaries():
 def test_mirror_matches_the_kernels_of_the_built_library():
     """The non-causal product instantiations of attention_kernel in libuspace_hip.so (template arguments NT, LC, SCALED, NW, CAUSAL,
     QS, HPW, W4 read from the mangled names) are exactly the forms the mirror can return: a launch added to or removed from
-    launch_attn2 without its mirror fails here."""
+    att_plan / att_dispatch_form without its mirror fails here."""
     if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
         pytest.skip("llvm-objdump not available")
     spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
@@ -83,6 +84,39 @@ def test_mirror_matches_the_kernels_of_the_built_library():
     lib = {(NT, LC, NW, bool(SC), QS, HPW) for NT, LC, SC, NW, CAUSAL, QS, HPW, W4 in args if not CAUSAL and NW != 6 and not W4}
     assert len(lib) == len([a for a in args if not a[4]]), "a lab instantiation (NW = 6 / W4) in the product library"
     assert lib == AC.all_forms(), (sorted(lib - AC.all_forms()), sorted(AC.all_forms() - lib))
+
+
+# B * H on both sides of every switch of att_plan (64, 128, rounds of 256 heads up to four) and beyond
+PLAN_BH = (1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 767, 768, 769, 1023, 1024, 1025, 1040, 2048)
+USPACE_ERR_ARG = -1
+
+
+def test_mirror_matches_the_plan_of_the_built_library():
+    """uspace_attention_plan (the att_plan that uspace_attention_bf16 launches from; host-side, no GPU) against the mirror for every
+    L the kernel takes, both key_scale settings and B * H around every switch, as B x 1 head and as B / 16 x 16 heads: kernel form and
+    grid from the mirror, block and dynamic LDS bytes from the kernel's layout (K rows, V rows, key scales).  A boundary moved in
+    attention.hip without its mirror fails here."""
+    from uspace_amd import _hip
+    plan = _hip.lib().uspace_attention_plan
+    out = (ctypes.c_int * 8)()
+    shapes = [(bh, 1) for bh in PLAN_BH] + [(bh // 16, 16) for bh in PLAN_BH if bh % 16 == 0]
+    assert len(shapes) > len(PLAN_BH)
+    seen = set()
+    for L in range(1, 337):
+        for scaled in (0, 1):
+            for B, H in shapes:
+                assert plan(B, L, H, scaled, out) == 0, (B, L, H, scaled)
+                NT, LC, NW, QS, HPW, grid, block, lds = out
+                where = (B, L, H, scaled, list(out))
+                assert (NT, LC, NW, bool(scaled), QS, HPW) == AC.launch_form(B, L, H, scaled), where
+                assert grid == AC.launch_grid(B, L, H, scaled), where
+                assert block == 64 * NW, where
+                assert lds == NT * 16 * 128 + -(-NT // 2) * 32 * 128 + (NT * 16 * 4 if scaled else 0) and lds <= 160 * 1024, where
+                seen.add((NT, LC, NW, bool(scaled), QS, HPW))
+    assert seen == AC.all_forms()
+    for scaled in (0, 1):
+        for B, L, H in ((1, 337, 1), (64, 337, 16), (1, 0, 1), (0, 257, 1), (0, 334, 16)):
+            assert plan(B, L, H, scaled, out) == USPACE_ERR_ARG, (B, L, H, scaled)
 
 
 # ------------------------------------------------------------------------------------------------------------------ data

@@ -83,6 +83,7 @@ SIGNATURES = {
     "uspace_gemm_slabs_bf16": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_I), _I, _P, _P, _I, _P, _I, _P, _I, _P]),
     "uspace_layernorm_f32_bf16": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "uspace_attention_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "uspace_attention_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I)]),
     "uspace_attention_map_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "uspace_embed_tokens": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "uspace_output_head": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),

@@ -80,6 +80,12 @@ __device__ __forceinline__ uint2 lds_read_tr16(const char* p) {
     return c.u;
 }
 
+// The dynamic LDS of a workgroup, for the kernel's pointers and the host's launch alike: K rows (16 per key tile), V rows (32 per
+// P.V step of two key tiles), 128 B each, then one fp32 key scale per K row (SCALED only).
+constexpr int att_k_rows(int NT) { return NT * 16; }
+constexpr int att_v_rows(int NT) { return (NT + 1) / 2 * 32; }
+constexpr int att_lds_bytes(int NT, bool scaled) { return (att_k_rows(NT) + att_v_rows(NT)) * KROW_BYTES + (scaled ? att_k_rows(NT) * 4 : 0); }
+
 // NT = number of 16-key tiles the kernel is compiled for (keys beyond L are masked).
 // LC > 0: the sequence length is a compile-time constant (the production lengths 257 and 334), so
 // the tail-tile masks, the tile-skip tests and the V^T stride fold away; LC == 0: generic length.
@@ -103,11 +109,11 @@ __global__ __launch_bounds__(64 * NW, NW == 6 ? 3 : (W4 ? 4 : 2)) void attention
     const int L = LC > 0 ? LC : L_rt;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NP = (NT + 1) / 2;       // 32-key steps of the P.V product
-    constexpr int VROWS = NP * 32;         // V rows staged (rows >= L: row L-1 again on the LDS-DMA path, zeros on the register path of HPW > 1 -- finite, their P is 0)
-    constexpr int KROWS = NT * 16;
+    constexpr int VROWS = att_v_rows(NT);  // V rows staged (rows >= L: row L-1 again on the LDS-DMA path, zeros on the register path of HPW > 1 -- finite, their P is 0)
+    constexpr int KROWS = att_k_rows(NT);
     char* sK = smem;                                   // [KROWS][64] bf16, 16-B chunks swizzled (k_off)
     char* sV = smem + KROWS * KROW_BYTES;              // [VROWS][64] bf16, 32-B chunks swizzled (v_off)
-    float* sKs = (float*)(sV + VROWS * KROW_BYTES);    // [KROWS] key scale (SCALED only)
+    float* sKs = (float*)(smem + att_lds_bytes(NT, false));   // [KROWS] key scale (SCALED only)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -440,93 +446,80 @@ __global__ __launch_bounds__(64 * NW, NW == 6 ? 3 : (W4 ? 4 : 2)) void attention
     }
 }
 
-template <int NT, int LC, bool SCALED, int NW>
-int launch_attn2(const bf16_t* qkv, const float* ks, bf16_t* out, int B, int L, int H, hipStream_t s) {
-    constexpr int NP = (NT + 1) / 2;
-    const size_t lds = (size_t)NT * 16 * KROW_BYTES + (size_t)NP * 32 * KROW_BYTES + (SCALED ? NT * 16 * 4 : 0);
-    static std::atomic<uint64_t> lds_ok{0}, lds_ok_q4{0}, lds_ok_q2{0};
-    const int rec = us_rec_begin(US_REC_ATTENTION, SCALED ? 1 : 0, B * H, L, 64, s);
-    // a quarter of the CUs or less: as many workgroups per head as it takes to give every wave at most ONE query tile (17 tiles on 4-wave
-    // workgroups: 5, not 4 -- with 4 the first wave of a head runs two tiles back to back; 21 tiles on 8-wave workgroups: 3)
-    constexpr int QSMALL = (NT + NW - 1) / NW;
-    if (B * H <= 64) {
-        US_TRY(us_opt_in_lds((const void*)attention_kernel<NT, LC, SCALED, NW, false, QSMALL>, 160 * 1024, lds_ok_q4));
-        hipLaunchKernelGGL((attention_kernel<NT, LC, SCALED, NW, false, QSMALL>), dim3(B * H * QSMALL), dim3(64 * NW), lds, s, qkv, ks, out, L, H, B * H);
-        us_rec_end(rec, s);
-        US_CHECK_LAUNCH();
-        return USPACE_OK;
-    }
-    if (B * H <= 128) {         // half of the CUs: two (12.1 -> 8.9 us at B * H = 128; three: no faster; nothing above that)
-        US_TRY(us_opt_in_lds((const void*)attention_kernel<NT, LC, SCALED, NW, false, 2>, 160 * 1024, lds_ok_q2));
-        hipLaunchKernelGGL((attention_kernel<NT, LC, SCALED, NW, false, 2>), dim3(B * H * 2), dim3(64 * NW), lds, s, qkv, ks, out, L, H, B * H);
-        us_rec_end(rec, s);
-        US_CHECK_LAUNCH();
-        return USPACE_OK;
-    }
-    if constexpr (!SCALED && NW == 8 && LC > 0) {     // (the generic-length instantiation spills with the prefetch registers)
+// ---- host side.  att_plan alone decides what a call launches, att_launch alone launches; uspace_attention_plan reports the same plan.
+struct AttPlan { int NT, LC, NW, QS, HPW, grid, block, lds; };
+struct AttArgs { const bf16_t* qkv; const float* ks; bf16_t* out; int B, L, H; hipStream_t s; };
+
+int att_plan(int B, int L, int H, bool scaled, bool causal, AttPlan* p) {
+    if (B <= 0 || L <= 0 || H <= 0) return USPACE_ERR_ARG;
+    const int nt = us_cdiv(L, 16), BH = B * H;
+    // sequences longer than 336 tokens do not occur on this path; causal (CLIP: 77 tokens = 5 key tiles): 160, generic length only
+    if (nt > (causal ? 10 : 21)) return USPACE_ERR_ARG;
+    const int NT = nt <= 6 ? 6 : nt <= 10 ? 10 : nt <= 17 ? 17 : 21;
+    const int LC = !causal && (L == 257 || L == 334) ? L : 0;     // uncond: 1 + 256 tokens; T2I: 1 + 77 + 256 tokens
+    int NW = NT > 17 ? 8 : 4;     // > 80 KB of LDS per workgroup: one workgroup per CU, so give it 8 waves
+    int QS = 1, HPW = 1, grid = BH;                               // one workgroup per head, unless:
+    if (causal) {                 // (the text encoder's few heads: never split, never shared)
+    } else if (BH <= 64) {
+        // a quarter of the CUs or less: as many workgroups per head as it takes to give every wave at most ONE query tile (17 tiles on
+        // 4-wave workgroups: 5, not 4 -- with 4 the first wave of a head runs two tiles back to back; 21 tiles on 8-wave workgroups: 3)
+        QS = us_cdiv(NT, NW);
+    } else if (BH <= 128) {       // half of the CUs: two (12.1 -> 8.9 us at B * H = 128; three: no faster; nothing above that)
+        QS = 2;
+    } else if (!scaled && NW == 8 && LC > 0) {     // (the generic-length instantiation spills with the prefetch registers)
         // (measured: L = 334 at B * H = 1024 60.8 -> 54.8 us; the 4-wave form of L = 257, two workgroups per CU whose rounds overlap by
         // themselves, 39.1 -> 39.4 us: not taken there)
         // more heads than resident workgroups (one per CU for the 8-wave form): one workgroup walks
         // `rounds` heads and fetches the next head's K / V through registers under the current head's query tiles
         constexpr int SLOTS = 256;
-        const int rounds = us_cdiv(B * H, SLOTS);
-        static std::atomic<uint64_t> lds_ok_h2{0}, lds_ok_h4{0};
-        if (rounds == 2) {
-            US_TRY(us_opt_in_lds((const void*)attention_kernel<NT, LC, false, NW, false, 1, 2>, 160 * 1024, lds_ok_h2));
-            hipLaunchKernelGGL((attention_kernel<NT, LC, false, NW, false, 1, 2>), dim3(us_cdiv(B * H, 2)), dim3(64 * NW), lds, s, qkv, ks, out, L, H, B * H);
-            us_rec_end(rec, s);
-            US_CHECK_LAUNCH();
-            return USPACE_OK;
-        }
-        if (rounds == 3 || rounds == 4) {
-            US_TRY(us_opt_in_lds((const void*)attention_kernel<NT, LC, false, NW, false, 1, 4>, 160 * 1024, lds_ok_h4));
-            hipLaunchKernelGGL((attention_kernel<NT, LC, false, NW, false, 1, 4>), dim3(us_cdiv(B * H, rounds)), dim3(64 * NW), lds, s, qkv, ks, out, L, H, B * H);
-            us_rec_end(rec, s);
-            US_CHECK_LAUNCH();
-            return USPACE_OK;
-        }
+        const int rounds = us_cdiv(BH, SLOTS);
+        if (rounds >= 2 && rounds <= 4) HPW = rounds == 2 ? 2 : 4, grid = us_cdiv(BH, rounds);
     }
-#if USPACE_ATT_W6
-    if constexpr (!SCALED && NW == 4 && LC > 0) {     // lab: six waves per workgroup, two workgroups per CU = three waves per SIMD
-        static std::atomic<uint64_t> lds_ok_w6{0};
-        US_TRY(us_opt_in_lds((const void*)attention_kernel<NT, LC, false, 6>, 160 * 1024, lds_ok_w6));
-        hipLaunchKernelGGL((attention_kernel<NT, LC, false, 6>), dim3(B * H), dim3(384), lds, s, qkv, ks, out, L, H, B * H);
-        us_rec_end(rec, s);
-        US_CHECK_LAUNCH();
-        return USPACE_OK;
-    }
+#if USPACE_ATT_W6 || USPACE_ATT_W4
+    // lab: six waves per workgroup, two workgroups per CU = three waves per SIMD; or eight (W4), four per SIMD
+    if (BH > 128 && !scaled && NW == 4 && LC > 0) NW = USPACE_ATT_W6 ? 6 : 8;
 #endif
-#if USPACE_ATT_W4
-    if constexpr (!SCALED && NW == 4 && LC > 0) {
-        static std::atomic<uint64_t> lds_ok_w4{0};
-        US_TRY(us_opt_in_lds((const void*)attention_kernel<NT, LC, false, 8, false, 1, 1, true>, 160 * 1024, lds_ok_w4));
-        hipLaunchKernelGGL((attention_kernel<NT, LC, false, 8, false, 1, 1, true>), dim3(B * H), dim3(512), lds, s, qkv, ks, out, L, H, B * H);
-        us_rec_end(rec, s);
-        US_CHECK_LAUNCH();
-        return USPACE_OK;
-    }
-#endif
-    US_TRY(us_opt_in_lds((const void*)attention_kernel<NT, LC, SCALED, NW>, 160 * 1024, lds_ok));
-    hipLaunchKernelGGL((attention_kernel<NT, LC, SCALED, NW>), dim3(B * H), dim3(64 * NW), lds, s, qkv, ks, out, L, H, B * H);
-    us_rec_end(rec, s);
+    *p = AttPlan{NT, LC, NW, QS, HPW, grid * QS, 64 * NW, att_lds_bytes(NT, scaled && !causal)};
+    return USPACE_OK;
+}
+
+// One instantiation per kernel form, each with its own record of the devices whose large-LDS opt-in is done.  The launch recorder
+// (bench.py's roofline) wraps the non-causal launches only.
+template <int NT, int LC, bool SCALED, int NW, bool CAUSAL = false, int QS = 1, int HPW = 1, bool W4 = false>
+int att_launch(const AttPlan& p, const AttArgs& a) {
+    static std::atomic<uint64_t> opted_in{0};
+    const auto kernel = attention_kernel<NT, LC, SCALED, NW, CAUSAL, QS, HPW, W4>;
+    const int rec = CAUSAL ? -1 : us_rec_begin(US_REC_ATTENTION, SCALED ? 1 : 0, a.B * a.H, a.L, 64, a.s);
+    US_TRY(us_opt_in_lds((const void*)kernel, 160 * 1024, opted_in));
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, a.s, a.qkv, a.ks, a.out, a.L, a.H, a.B * a.H);
+    us_rec_end(rec, a.s);
     US_CHECK_LAUNCH();
     return USPACE_OK;
+}
+
+// the plan's (QS, HPW) -> the instantiation; `if constexpr` keeps the forms no plan asks for out of the library
+template <int NT, int LC, bool SCALED>
+int att_dispatch_form(const AttPlan& p, const AttArgs& a) {
+    constexpr int NW = NT > 17 ? 8 : 4, QSMALL = (NT + NW - 1) / NW;
+    static_assert(QSMALL > 1, "QS = 1 is the plain form");
+    if (p.QS == QSMALL) return att_launch<NT, LC, SCALED, NW, false, QSMALL>(p, a);
+    if (p.QS == 2) return att_launch<NT, LC, SCALED, NW, false, 2>(p, a);
+    if constexpr (!SCALED && NW == 8 && LC > 0) {
+        if (p.HPW == 2) return att_launch<NT, LC, false, NW, false, 1, 2>(p, a);
+        if (p.HPW == 4) return att_launch<NT, LC, false, NW, false, 1, 4>(p, a);
+    }
+#if USPACE_ATT_W6
+    if constexpr (!SCALED && NW == 4 && LC > 0) { if (p.NW == 6) return att_launch<NT, LC, false, 6>(p, a); }
+#endif
+#if USPACE_ATT_W4
+    if constexpr (!SCALED && NW == 4 && LC > 0) { if (p.NW == 8) return att_launch<NT, LC, false, 8, false, 1, 1, true>(p, a); }
+#endif
+    return att_launch<NT, LC, SCALED, NW>(p, a);
 }
 
 template <int NT, int LC>
-int launch_attn(const bf16_t* qkv, const float* ks, bf16_t* out, int B, int L, int H, hipStream_t s) {
-    constexpr int NW = NT > 17 ? 8 : 4;     // > 80 KB of LDS per workgroup: one workgroup per CU, so give it 8 waves
-    return ks ? launch_attn2<NT, LC, true, NW>(qkv, ks, out, B, L, H, s)
-              : launch_attn2<NT, LC, false, NW>(qkv, ks, out, B, L, H, s);
-}
-
-template <int NT>
-int launch_attn_causal(const bf16_t* qkv, bf16_t* out, int B, int L, int H, hipStream_t s) {
-    constexpr int NP = (NT + 1) / 2;
-    const size_t lds = (size_t)NT * 16 * KROW_BYTES + (size_t)NP * 32 * KROW_BYTES;
-    hipLaunchKernelGGL((attention_kernel<NT, 0, false, 4, true>), dim3(B * H), dim3(256), lds, s, qkv, nullptr, out, L, H, B * H);
-    US_CHECK_LAUNCH();
-    return USPACE_OK;
+int att_dispatch(const AttPlan& p, const AttArgs& a) {
+    return a.ks ? att_dispatch_form<NT, LC, true>(p, a) : att_dispatch_form<NT, LC, false>(p, a);
 }
 
 }  // namespace
@@ -537,25 +530,33 @@ extern "C" __attribute__((visibility("default"))) int uspace_lab_att_trace(unsig
 }
 #endif
 
+extern "C" int uspace_attention_plan(int B, int L, int H, int scaled, int* out) {
+    AttPlan p;
+    if (!out) return USPACE_ERR_ARG;
+    US_TRY(att_plan(B, L, H, scaled != 0, false, &p));
+    const int v[8] = {p.NT, p.LC, p.NW, p.QS, p.HPW, p.grid, p.block, p.lds};
+    std::copy(v, v + 8, out);
+    return USPACE_OK;
+}
+
 extern "C" int uspace_attention_causal_bf16(const uint16_t* qkv, uint16_t* out, int B, int L, int H, uspace_stream_t stream) {
-    if (!qkv || !out || B <= 0 || L <= 0 || H <= 0) return USPACE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int nt = (L + 15) / 16;
-    if (nt <= 6) return launch_attn_causal<6>(qkv, out, B, L, H, s);     // CLIP: 77 tokens = 5 key tiles
-    if (nt <= 10) return launch_attn_causal<10>(qkv, out, B, L, H, s);
-    return USPACE_ERR_ARG;
+    AttPlan p;
+    if (!qkv || !out) return USPACE_ERR_ARG;
+    US_TRY(att_plan(B, L, H, false, true, &p));
+    const AttArgs a{qkv, nullptr, out, B, L, H, (hipStream_t)stream};
+    return p.NT == 6 ? att_launch<6, 0, false, 4, true>(p, a) : att_launch<10, 0, false, 4, true>(p, a);
 }
 
 extern "C" int uspace_attention_bf16(const uint16_t* qkv, const float* key_scale, uint16_t* out, int B, int L, int H,
                                      uspace_stream_t stream) {
-    if (!qkv || !out || B <= 0 || L <= 0 || H <= 0) return USPACE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int nt = (L + 15) / 16;
-    if (L == 257) return launch_attn<17, 257>(qkv, key_scale, out, B, L, H, s);   // uncond: 1 + 256 tokens
-    if (L == 334) return launch_attn<21, 334>(qkv, key_scale, out, B, L, H, s);   // T2I: 1 + 77 + 256 tokens
-    if (nt <= 6) return launch_attn<6, 0>(qkv, key_scale, out, B, L, H, s);
-    if (nt <= 10) return launch_attn<10, 0>(qkv, key_scale, out, B, L, H, s);
-    if (nt <= 17) return launch_attn<17, 0>(qkv, key_scale, out, B, L, H, s);
-    if (nt <= 21) return launch_attn<21, 0>(qkv, key_scale, out, B, L, H, s);
-    return USPACE_ERR_ARG;  // sequences longer than 336 tokens do not occur on this path
+    AttPlan p;
+    if (!qkv || !out) return USPACE_ERR_ARG;
+    US_TRY(att_plan(B, L, H, key_scale != nullptr, false, &p));
+    const AttArgs a{qkv, key_scale, out, B, L, H, (hipStream_t)stream};
+    if (p.LC == 257) return att_dispatch<17, 257>(p, a);
+    if (p.LC == 334) return att_dispatch<21, 334>(p, a);
+    if (p.NT == 6) return att_dispatch<6, 0>(p, a);
+    if (p.NT == 10) return att_dispatch<10, 0>(p, a);
+    if (p.NT == 17) return att_dispatch<17, 0>(p, a);
+    return att_dispatch<21, 0>(p, a);
 }
