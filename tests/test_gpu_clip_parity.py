@@ -232,13 +232,13 @@ def test_poisoned_workspace_gives_the_same_bits(models, B):
     ids = S.prompt_ids(8, seed=800)[:B]
     for L in (33, 64, 77):
         dev = ids[:, :L].contiguous().cuda()
-        m._ws = {}
+        m._ws.clear()
         fresh = m(dev)
         (key, ws), = m._ws.items()
         ws.fill_(0xFF)                                            # every fp32 / bf16 word of the workspace a NaN
         assert torch.equal(m(dev), fresh), L
         assert m._ws[key] is ws                                   # ... and the forward ran on it
-    m._ws = {}
+    m._ws.clear()
 
 
 # ------------------------------------------------------------------------------------------------------------------ G

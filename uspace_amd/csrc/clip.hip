@@ -5,15 +5,17 @@
 // sequence instead of re-instantiating the encoder (tools/utils_t2i.py:25-39 does that on every call).
 #include <vector>
 
-#include "common.h"
+#include "blob.h"
 
 namespace {
 
 struct ClipLayer {
     size_t wqkv, bqkv, wo, bo, ln1g, ln1b, w1, b1, w2, b2, ln2g, ln2b;
 };
+// the table is the one statement of the parameter shapes and order; the offsets beside it are what the forward reads
 struct ClipModel {
-    size_t tok, pos, fg, fb, total;
+    ParamTable t;
+    size_t tok, pos, fg, fb;
     std::vector<ClipLayer> layers;
 };
 
@@ -24,61 +26,39 @@ bool valid_clip(const uspace_clip_config* c) {
     return true;
 }
 
-inline size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
-ClipModel build_clip(const uspace_clip_config& c) {
-    ClipModel m;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = al(off + bytes);
-        return o;
-    };
-    const size_t D = c.dim, F = c.ffn;
-    m.tok = take((size_t)c.vocab * D * 4);
-    m.pos = take((size_t)c.max_pos * D * 4);
-    for (int i = 0; i < c.layers; ++i) {
-        ClipLayer l;
-        l.wqkv = take(3 * D * D * 2);
-        l.bqkv = take(3 * D * 4);
-        l.wo = take(D * D * 2);
-        l.bo = take(D * 4);
-        l.ln1g = take(D * 4);
-        l.ln1b = take(D * 4);
-        l.w1 = take(F * D * 2);
-        l.b1 = take(F * 4);
-        l.w2 = take(D * F * 2);
-        l.b2 = take(D * 4);
-        l.ln2g = take(D * 4);
-        l.ln2b = take(D * 4);
-        m.layers.push_back(l);
-    }
-    m.fg = take(D * 4);
-    m.fb = take(D * 4);
-    m.total = off;
-    return m;
-}
-
 // HF state_dict order: embeddings.{token,position}_embedding.weight; per layer self_attn.{k,v,q,out}_proj.{weight,bias},
 // layer_norm1.{weight,bias}, mlp.fc1.{weight,bias}, mlp.fc2.{weight,bias}, layer_norm2.{weight,bias}; final_layer_norm.*
-constexpr int PER_LAYER = 16;
-
-long clip_param_numel(const uspace_clip_config& c, int idx) {
+ClipModel build_clip(const uspace_clip_config& c) {
+    ClipModel m;
+    ParamTable& t = m.t;
+    auto put = [&t](long numel, PKind k) { return t.at(t.add(numel, k)); };
     const long D = c.dim, F = c.ffn;
-    if (idx == 0) return (long)c.vocab * D;
-    if (idx == 1) return (long)c.max_pos * D;
-    const int n = 2 + PER_LAYER * c.layers;
-    if (idx >= n) return D;                      // final_layer_norm.weight / .bias
-    switch ((idx - 2) % PER_LAYER) {
-        case 0: case 2: case 4: case 6: return D * D;    // k, v, q, out weights
-        case 1: case 3: case 5: case 7: return D;        // their biases
-        case 8: case 9: return D;                        // layer_norm1
-        case 10: return F * D;
-        case 11: return F;
-        case 12: return D * F;
-        case 13: return D;
-        default: return D;                               // layer_norm2
+    m.tok = put((long)c.vocab * D, P_F32);
+    m.pos = put((long)c.max_pos * D, P_F32);
+    for (int i = 0; i < c.layers; ++i) {
+        ClipLayer l;
+        // packed projection rows: q | k | v (the attention kernel's layout); HF lists k, v, q
+        l.wqkv = t.arena.take(3 * D * D * 2);
+        l.bqkv = t.arena.take(3 * D * 4);
+        for (const int slot : {1, 2, 0}) {
+            t.add_at(l.wqkv + slot * D * D * 2, D * D, P_BF16);
+            t.add_at(l.bqkv + slot * D * 4, D, P_F32);
+        }
+        l.wo = put(D * D, P_BF16);
+        l.bo = put(D, P_F32);
+        l.ln1g = put(D, P_F32);
+        l.ln1b = put(D, P_F32);
+        l.w1 = put(F * D, P_BF16);
+        l.b1 = put(F, P_F32);
+        l.w2 = put(D * F, P_BF16);
+        l.b2 = put(D, P_F32);
+        l.ln2g = put(D, P_F32);
+        l.ln2b = put(D, P_F32);
+        m.layers.push_back(l);
     }
+    m.fg = put(D, P_F32);
+    m.fb = put(D, P_F32);
+    return m;
 }
 
 struct ClipWs {
@@ -86,35 +66,28 @@ struct ClipWs {
 };
 ClipWs plan_clip_ws(const uspace_clip_config& c, int B) {
     ClipWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = al(off + bytes);
-        return o;
-    };
+    Arena a;
     const size_t M = (size_t)B * c.max_pos, D = c.dim;
-    w.x = take(M * D * 4);
-    w.h = take(M * D * 2);
-    w.qkv = take(M * 3 * D * 2);
-    w.att = take(M * D * 2);
-    w.f = take(M * (size_t)c.ffn * 2);
-    w.total = off;
+    w.x = a.take(M * D * 4);
+    w.h = a.take(M * D * 2);
+    w.qkv = a.take(M * 3 * D * 2);
+    w.att = a.take(M * D * 2);
+    w.f = a.take(M * (size_t)c.ffn * 2);
+    w.total = a.off;
     return w;
 }
 
 }  // namespace
 
 extern "C" int uspace_clip_num_params(const uspace_clip_config* cfg) {
-    if (!valid_clip(cfg)) return USPACE_ERR_ARG;
-    return 2 + PER_LAYER * cfg->layers + 2;
+    return valid_clip(cfg) ? build_clip(*cfg).t.n_params : USPACE_ERR_ARG;
 }
 
 extern "C" long uspace_clip_param_numel(const uspace_clip_config* cfg, int index) {
-    if (!valid_clip(cfg) || index < 0 || index >= 2 + PER_LAYER * cfg->layers + 2) return USPACE_ERR_ARG;
-    return clip_param_numel(*cfg, index);
+    return valid_clip(cfg) ? build_clip(*cfg).t.numel(index) : (long)USPACE_ERR_ARG;
 }
 
-extern "C" size_t uspace_clip_weight_bytes(const uspace_clip_config* cfg) { return valid_clip(cfg) ? build_clip(*cfg).total : 0; }
+extern "C" size_t uspace_clip_weight_bytes(const uspace_clip_config* cfg) { return valid_clip(cfg) ? build_clip(*cfg).t.bytes() : 0; }
 
 extern "C" size_t uspace_clip_workspace_bytes(const uspace_clip_config* cfg, int B) {
     return (valid_clip(cfg) && B > 0) ? plan_clip_ws(*cfg, B).total : 0;
@@ -122,45 +95,8 @@ extern "C" size_t uspace_clip_workspace_bytes(const uspace_clip_config* cfg, int
 
 extern "C" int uspace_clip_pack_weights(const uspace_clip_config* cfg, const float* const* params, int n_params, void* blob,
                                         size_t blob_bytes, uspace_stream_t stream) {
-    if (!valid_clip(cfg) || !params || !blob) return USPACE_ERR_ARG;
-    const ClipModel m = build_clip(*cfg);
-    if (n_params != 2 + PER_LAYER * cfg->layers + 2 || blob_bytes < m.total) return USPACE_ERR_ARG;
-    for (int i = 0; i < n_params; ++i)
-        if (!params[i]) return USPACE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)blob;
-    const size_t D = cfg->dim, F = cfg->ffn;
-    auto f32 = [&](const float* src, size_t off, size_t n) {
-        return hipMemcpyAsync(base + off, src, n * 4, hipMemcpyDeviceToDevice, s) == hipSuccess ? USPACE_OK : USPACE_ERR_LAUNCH;
-    };
-    auto b16 = [&](const float* src, size_t off, size_t n) { return uspace_cast_f32_bf16(src, (uint16_t*)(base + off), (long)n, stream); };
-    US_TRY(f32(params[0], m.tok, (size_t)cfg->vocab * D));
-    US_TRY(f32(params[1], m.pos, (size_t)cfg->max_pos * D));
-    for (int i = 0; i < cfg->layers; ++i) {
-        const float* const* p = params + 2 + PER_LAYER * i;
-        const ClipLayer& l = m.layers[i];
-        // packed projection rows: q | k | v (the attention kernel's layout); HF order is k, v, q
-        US_TRY(b16(p[4], l.wqkv, D * D));
-        US_TRY(b16(p[0], l.wqkv + D * D * 2, D * D));
-        US_TRY(b16(p[2], l.wqkv + 2 * D * D * 2, D * D));
-        US_TRY(f32(p[5], l.bqkv, D));
-        US_TRY(f32(p[1], l.bqkv + D * 4, D));
-        US_TRY(f32(p[3], l.bqkv + 2 * D * 4, D));
-        US_TRY(b16(p[6], l.wo, D * D));
-        US_TRY(f32(p[7], l.bo, D));
-        US_TRY(f32(p[8], l.ln1g, D));
-        US_TRY(f32(p[9], l.ln1b, D));
-        US_TRY(b16(p[10], l.w1, F * D));
-        US_TRY(f32(p[11], l.b1, F));
-        US_TRY(b16(p[12], l.w2, D * F));
-        US_TRY(f32(p[13], l.b2, D));
-        US_TRY(f32(p[14], l.ln2g, D));
-        US_TRY(f32(p[15], l.ln2b, D));
-    }
-    const float* const* pf = params + 2 + PER_LAYER * cfg->layers;
-    US_TRY(f32(pf[0], m.fg, D));
-    US_TRY(f32(pf[1], m.fb, D));
-    return USPACE_OK;
+    if (!valid_clip(cfg)) return USPACE_ERR_ARG;
+    return us_pack_table(build_clip(*cfg).t, params, n_params, blob, blob_bytes, stream);
 }
 
 extern "C" int uspace_clip_text_forward(const uspace_clip_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,

@@ -9,31 +9,9 @@
 #include <mutex>
 #include <vector>
 
-#include "common.h"
+#include "blob.h"
 
 namespace {
-
-constexpr size_t ALIGN = 256;
-inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-
-enum Kind { F32 = 0, BF16 = 1 };
-
-struct ParamDesc {
-    long numel;
-    Kind kind;
-    size_t offset;  // byte offset in the blob
-};
-
-struct Layout {
-    std::vector<ParamDesc> p;
-    size_t bytes = 0;
-    int add(long numel, Kind k) {
-        ParamDesc d{numel, k, bytes};
-        bytes = align_up(bytes + (size_t)numel * (k == BF16 ? 2 : 4));
-        p.push_back(d);
-        return (int)p.size() - 1;
-    }
-};
 
 struct BlockIdx {
     int skip_w = -1, skip_b = -1;
@@ -45,13 +23,12 @@ struct BlockIdx {
 };
 
 struct Model {
-    Layout lay;
+    ParamTable lay;
     int pos, pw, pb, cw = -1, cb = -1;
     std::vector<BlockIdx> blk;
     int ng, nb, dw, db, convw, convb;
     int head_img = -1;   // derived: the output head's weight image (rowops.hip head_weight_image), when the fast path applies
     int L, extras, npatch, nblocks;
-    int n_params;   // entries of lay.p that are parameters; the rest are derived tensors
 };
 
 bool valid_cfg(const uspace_uvit_config* c) {
@@ -74,52 +51,52 @@ Model build_model(const uspace_uvit_config& c) {
     m.npatch = g * g;
     m.extras = 1 + c.n_extra;
     m.L = m.extras + m.npatch;
-    m.pos = m.lay.add((long)m.L * D, F32);
-    m.pw = m.lay.add(D * c.in_chans * c.patch_size * c.patch_size, F32);
-    m.pb = m.lay.add(D, F32);
+    m.pos = m.lay.add((long)m.L * D, P_F32);
+    m.pw = m.lay.add(D * c.in_chans * c.patch_size * c.patch_size, P_F32);
+    m.pb = m.lay.add(D, P_F32);
     if (c.clip_dim > 0) {
-        m.cw = m.lay.add(D * c.clip_dim, BF16);
-        m.cb = m.lay.add(D, F32);
+        m.cw = m.lay.add(D * c.clip_dim, P_BF16);
+        m.cb = m.lay.add(D, P_F32);
     }
     const int half = c.depth / 2;
     m.nblocks = c.depth + 1;
     for (int i = 0; i < m.nblocks; ++i) {
         BlockIdx b;
         if (i > half) {
-            b.skip_w = m.lay.add(D * 2 * D, BF16);
-            b.skip_b = m.lay.add(D, F32);
+            b.skip_w = m.lay.add(D * 2 * D, P_BF16);
+            b.skip_b = m.lay.add(D, P_F32);
         }
-        b.n1w = m.lay.add(D, F32);
-        b.n1b = m.lay.add(D, F32);
-        b.qkv = m.lay.add(3 * D * D, BF16);
-        b.projw = m.lay.add(D * D, BF16);
-        b.projb = m.lay.add(D, F32);
-        b.n2w = m.lay.add(D, F32);
-        b.n2b = m.lay.add(D, F32);
-        b.fc1w = m.lay.add(Hd * D, BF16);
-        b.fc1b = m.lay.add(Hd, F32);
-        b.fc2w = m.lay.add(D * Hd, BF16);
-        b.fc2b = m.lay.add(D, F32);
+        b.n1w = m.lay.add(D, P_F32);
+        b.n1b = m.lay.add(D, P_F32);
+        b.qkv = m.lay.add(3 * D * D, P_BF16);
+        b.projw = m.lay.add(D * D, P_BF16);
+        b.projb = m.lay.add(D, P_F32);
+        b.n2w = m.lay.add(D, P_F32);
+        b.n2b = m.lay.add(D, P_F32);
+        b.fc1w = m.lay.add(Hd * D, P_BF16);
+        b.fc1b = m.lay.add(Hd, P_F32);
+        b.fc2w = m.lay.add(D * Hd, P_BF16);
+        b.fc2b = m.lay.add(D, P_F32);
         m.blk.push_back(b);
     }
-    m.ng = m.lay.add(D, F32);
-    m.nb = m.lay.add(D, F32);
+    m.ng = m.lay.add(D, P_F32);
+    m.nb = m.lay.add(D, P_F32);
     const long PD = (long)c.patch_size * c.patch_size * c.in_chans;
-    m.dw = m.lay.add(PD * D, F32);
-    m.db = m.lay.add(PD, F32);
-    m.convw = m.lay.add((long)c.in_chans * c.in_chans * 9, F32);
-    m.convb = m.lay.add(c.in_chans, F32);
-    m.n_params = (int)m.lay.p.size();
+    m.dw = m.lay.add(PD * D, P_F32);
+    m.db = m.lay.add(PD, P_F32);
+    m.convw = m.lay.add((long)c.in_chans * c.in_chans * 9, P_F32);
+    m.convb = m.lay.add(c.in_chans, P_F32);
+    m.lay.derived = true;   // from here on: tensors uspace_uvit_pack_weights computes
     for (BlockIdx& b : m.blk) {
-        b.qkv_f = m.lay.add(3 * D * D, BF16);
-        b.qkv_fb = m.lay.add(3 * D, F32);
-        b.qkv_cs = m.lay.add(3 * D, F32);
-        b.fc1_f = m.lay.add(Hd * D, BF16);
-        b.fc1_fb = m.lay.add(Hd, F32);
-        b.fc1_cs = m.lay.add(Hd, F32);
-        if (b.skip_w >= 0) b.skip_cs2 = m.lay.add(D, F32);
+        b.qkv_f = m.lay.add(3 * D * D, P_BF16);
+        b.qkv_fb = m.lay.add(3 * D, P_F32);
+        b.qkv_cs = m.lay.add(3 * D, P_F32);
+        b.fc1_f = m.lay.add(Hd * D, P_BF16);
+        b.fc1_fb = m.lay.add(Hd, P_F32);
+        b.fc1_cs = m.lay.add(Hd, P_F32);
+        if (b.skip_w >= 0) b.skip_cs2 = m.lay.add(D, P_F32);
     }
-    if ((D & 31) == 0 && D <= 2048) m.head_img = m.lay.add((long)us_head_image_floats((int)D), F32);
+    if ((D & 31) == 0 && D <= 2048) m.head_img = m.lay.add((long)us_head_image_floats((int)D), P_F32);
     return m;
 }
 
@@ -134,33 +111,32 @@ inline int sk_launches(const uspace_uvit_config& c) { return 5 * (c.depth + 1) +
 Workspace plan_workspace(const uspace_uvit_config& c, const Model& m, int B, bool sk_on) {
     Workspace w;
     const size_t M = (size_t)B * m.L, D = c.embed_dim;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-    w.x = take(M * D * 4);
-    w.xb = take(M * D * 2);
-    w.h = take(M * D * 2);
-    w.qkv = take(M * 3 * D * 2);
-    w.f = take(M * (size_t)c.mlp_hidden * 2);
-    w.skips = take((size_t)(c.depth / 2) * M * D * 2);
-    w.ctx_bf = take(c.clip_dim > 0 ? (size_t)B * c.n_extra * c.clip_dim * 2 : 0);
-    w.ctx_f32 = take(c.clip_dim > 0 ? (size_t)B * c.n_extra * D * 4 : 0);
-    w.head = take((size_t)B * c.in_chans * c.img_size * c.img_size * 4);
-    w.xc = take(M * D * 2);                          // LayerNorm folding: centred bf16 copy of the residual stream
-    w.part = take(M * (size_t)us_cdiv((int)D, 64) * 2 * 4);    // per-row partial sums, one slot per producer N tile (64 columns at the least)
-    w.cbuf = take(M * 4);                            // per-row centring constants (row means at the last norm)
-    w.cskip = take((size_t)(c.depth / 2) * M * 4);   // ... of the centred copies kept on the long-skip stack, one per in-block
+    Arena a;
+    w.x = a.take(M * D * 4);
+    w.xb = a.take(M * D * 2);
+    w.h = a.take(M * D * 2);
+    w.qkv = a.take(M * 3 * D * 2);
+    w.f = a.take(M * (size_t)c.mlp_hidden * 2);
+    w.skips = a.take((size_t)(c.depth / 2) * M * D * 2);
+    w.ctx_bf = a.take(c.clip_dim > 0 ? (size_t)B * c.n_extra * c.clip_dim * 2 : 0);
+    w.ctx_f32 = a.take(c.clip_dim > 0 ? (size_t)B * c.n_extra * D * 4 : 0);
+    w.head = a.take((size_t)B * c.in_chans * c.img_size * c.img_size * 4);
+    w.xc = a.take(M * D * 2);                          // LayerNorm folding: centred bf16 copy of the residual stream
+    w.part = a.take(M * (size_t)us_cdiv((int)D, 64) * 2 * 4);    // per-row partial sums, one slot per producer N tile (64 columns at the least)
+    w.cbuf = a.take(M * 4);                            // per-row centring constants (row means at the last norm)
+    w.cskip = a.take((size_t)(c.depth / 2) * M * 4);   // ... of the centred copies kept on the long-skip stack, one per in-block
     // fp32 partial sums of the K-split form the GEMM uses for small batches (proj, skip_linear, fc2: N = D)
     w.splitk_bytes = std::max(std::max(uspace_gemm_split_ws_bytes((int)M, (int)D, (int)D), uspace_gemm_split_ws_bytes((int)M, (int)D, 2 * (int)D)),
                               uspace_gemm_split_ws_bytes((int)M, (int)D, c.mlp_hidden));
-    w.splitk = take(w.splitk_bytes);
+    w.splitk = a.take(w.splitk_bytes);
     // partial-sum slabs of the in-launch K-split tail (qkv; proj, skip_linear, fc2: N = D) and the launches' arrival counters
     auto sk_ws = [&](size_t n, size_t k) { return us_gemm_sk_ws_bytes((int)M, (int)n, (int)k, sk_on); };
     w.sk_bytes = std::max(std::max(sk_ws(D, D), sk_ws(D, 2 * D)), std::max(sk_ws(D, c.mlp_hidden), sk_ws(3 * D, D)));
     w.sk_bytes = std::max(w.sk_bytes, sk_ws(c.mlp_hidden, D));
-    w.sk = take(w.sk_bytes);
+    w.sk = a.take(w.sk_bytes);
     w.skcnt_bytes = w.sk_bytes ? (size_t)sk_launches(c) * USPACE_GEMM_SK_COUNTERS * 4 : 0;
-    w.skcnt = take(w.skcnt_bytes);
-    w.total = off;
+    w.skcnt = a.take(w.skcnt_bytes);
+    w.total = a.off;
     return w;
 }
 
@@ -168,19 +144,17 @@ Workspace plan_workspace(const uspace_uvit_config& c, const Model& m, int B, boo
 
 extern "C" int uspace_uvit_num_params(const uspace_uvit_config* cfg) {
     if (!valid_cfg(cfg)) return USPACE_ERR_ARG;
-    return build_model(*cfg).n_params;
+    return build_model(*cfg).lay.n_params;
 }
 
 extern "C" long uspace_uvit_param_numel(const uspace_uvit_config* cfg, int index) {
     if (!valid_cfg(cfg)) return USPACE_ERR_ARG;
-    const Model m = build_model(*cfg);
-    if (index < 0 || index >= m.n_params) return USPACE_ERR_ARG;
-    return m.lay.p[index].numel;
+    return build_model(*cfg).lay.numel(index);
 }
 
 extern "C" size_t uspace_uvit_weight_bytes(const uspace_uvit_config* cfg) {
     if (!valid_cfg(cfg)) return 0;
-    return build_model(*cfg).lay.bytes;
+    return build_model(*cfg).lay.bytes();
 }
 
 extern "C" size_t uspace_uvit_workspace_bytes(const uspace_uvit_config* cfg, int B) {
@@ -191,22 +165,10 @@ extern "C" size_t uspace_uvit_workspace_bytes(const uspace_uvit_config* cfg, int
 
 extern "C" int uspace_uvit_pack_weights(const uspace_uvit_config* cfg, const float* const* params, int n_params,
                                         void* blob, size_t blob_bytes, uspace_stream_t stream) {
-    if (!valid_cfg(cfg) || !params || !blob) return USPACE_ERR_ARG;
+    if (!valid_cfg(cfg)) return USPACE_ERR_ARG;
     const Model m = build_model(*cfg);
-    if (n_params != m.n_params) return USPACE_ERR_ARG;
-    if (blob_bytes < m.lay.bytes) return USPACE_ERR_WORKSPACE;
+    US_TRY(us_pack_table(m.lay, params, n_params, blob, blob_bytes, stream));
     hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < n_params; ++i) {
-        const ParamDesc& d = m.lay.p[i];
-        if (!params[i]) return USPACE_ERR_ARG;
-        char* dst = (char*)blob + d.offset;
-        if (d.kind == BF16) {
-            US_TRY(uspace_cast_f32_bf16(params[i], (uint16_t*)dst, d.numel, stream));
-        } else {
-            if (hipMemcpyAsync(dst, params[i], (size_t)d.numel * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-                return USPACE_ERR_LAUNCH;
-        }
-    }
     // LayerNorm folding: W' = bf16(W * gamma), bias' = bias + W beta, column sums of W' (qkv has no bias of its own)
     const int D = cfg->embed_dim, Hd = cfg->mlp_hidden;
     auto at = [&](int idx) { return (char*)blob + m.lay.p[idx].offset; };

@@ -13,12 +13,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
+#include "blob.h"
 
 namespace {
-
-constexpr size_t ALIGN = 256;
-inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 
 // ------------------------------------------------------------------------------------------ kernels
 // z/scale -> post_quant_conv (1x1) -> conv_in (3x3, pad 1): one block per latent pixel.
@@ -478,15 +475,6 @@ inline int grid_for(long items, int cap = 4096) {
 }
 
 // ------------------------------------------------------------------------------------------ model description
-enum PKind { P_F32 = 0, P_CONV3_BF16 = 1, P_CONV1_BF16 = 2, P_CONV3_F32T = 3 };
-
-struct PDesc {
-    long numel;
-    PKind kind;
-    int co, ci;
-    size_t offset, bytes;
-};
-
 struct ResIdx {
     int n1w, n1b, c1w, c1b, n2w, n2b, c2w, c2b, sw = -1, sb = -1;
     int cin, cout;
@@ -497,16 +485,7 @@ struct AttnIdx {   // single-head AttnBlock (libs/autoencoder.py:139-195): norm,
 };
 
 // parameter list of one packed blob, in the reference's state_dict order
-struct ParamTable {
-    std::vector<PDesc> p;
-    size_t blob_bytes = 0;
-    int add(long numel, PKind k, int co = 0, int ci = 0) {
-        PDesc d{numel, k, co, ci, blob_bytes, 0};
-        d.bytes = (size_t)numel * ((k == P_CONV3_BF16 || k == P_CONV1_BF16) ? 2 : 4);
-        blob_bytes = align_up(blob_bytes + d.bytes);
-        p.push_back(d);
-        return (int)p.size() - 1;
-    }
+struct VaeTable : ParamTable {
     ResIdx add_res(int cin, int cout) {
         ResIdx r;
         r.cin = cin; r.cout = cout;
@@ -514,21 +493,21 @@ struct ParamTable {
         r.c1w = add((long)cout * cin * 9, P_CONV3_BF16, cout, cin); r.c1b = add(cout, P_F32);
         r.n2w = add(cout, P_F32); r.n2b = add(cout, P_F32);
         r.c2w = add((long)cout * cout * 9, P_CONV3_BF16, cout, cout); r.c2b = add(cout, P_F32);
-        if (cin != cout) { r.sw = add((long)cout * cin, P_CONV1_BF16, cout, cin); r.sb = add(cout, P_F32); }
+        if (cin != cout) { r.sw = add((long)cout * cin, P_BF16, cout, cin); r.sb = add(cout, P_F32); }
         return r;
     }
     AttnIdx add_attn(int c) {
         AttnIdx a;
         a.nw = add(c, P_F32); a.nb = add(c, P_F32);
-        a.q_w = add((long)c * c, P_CONV1_BF16, c, c); a.q_b = add(c, P_F32);
-        a.k_w = add((long)c * c, P_CONV1_BF16, c, c); a.k_b = add(c, P_F32);
-        a.v_w = add((long)c * c, P_CONV1_BF16, c, c); a.v_b = add(c, P_F32);
-        a.po_w = add((long)c * c, P_CONV1_BF16, c, c); a.po_b = add(c, P_F32);
+        a.q_w = add((long)c * c, P_BF16, c, c); a.q_b = add(c, P_F32);
+        a.k_w = add((long)c * c, P_BF16, c, c); a.k_b = add(c, P_F32);
+        a.v_w = add((long)c * c, P_BF16, c, c); a.v_b = add(c, P_F32);
+        a.po_w = add((long)c * c, P_BF16, c, c); a.po_b = add(c, P_F32);
         return a;
     }
 };
 
-struct VaeModel : ParamTable {
+struct VaeModel : VaeTable {
     int conv_in_w, conv_in_b;
     ResIdx mid1, mid2;
     AttnIdx attn;
@@ -583,7 +562,7 @@ VaeModel build_vae(const uspace_vae_config& c) {
 }
 
 // Encoder (libs/autoencoder.py:215-300) with double_z, 3 input channels and no attention in the down path, then quant_conv
-struct EncModel : ParamTable {
+struct EncModel : VaeTable {
     int conv_in_w, conv_in_b;
     std::vector<std::vector<ResIdx>> down;   // [level][block]
     std::vector<int> ds_w, ds_b;             // downsample conv per level (-1 at the last level)
@@ -630,99 +609,64 @@ struct VaeWs {
 
 inline size_t map_rows(int B, int res) { return (size_t)B * (res + 2) * (res + 2) + 2 * (size_t)(res + 3); }
 
-// everything after the four maps: GroupNorm statistics and the mid-block attention's buffers
-template <class Take>
-void plan_stats_attn(VaeWs& w, Take take, int B, int z_res, int c_top) {
-    w.stats = take((size_t)B * (1 + USPACE_GN_MAX_CHUNKS) * 64 * 4);
-    const size_t T = (size_t)B * z_res * z_res, Cc = c_top, HW = (size_t)z_res * z_res;
-    w.tok = take(T * Cc * 2); w.q = take(T * Cc * 2); w.k = take(T * Cc * 2); w.v = take(T * Cc * 2);
-    w.vt = take(T * Cc * 2); w.s = take(HW * HW * 4); w.pr = take(HW * HW * 2); w.o = take(T * Cc * 2);
-    w.po = take(T * Cc * 4);
-}
-
-VaeWs plan_vae_ws(const uspace_vae_config& c, const VaeModel& m, int B) {
-    VaeWs w;
-    // largest map: at each level the upsample conv keeps that level's channels at twice the resolution
-    size_t max_f = 0, max_h = 0;
-    int res = m.z_res;
-    int chan = m.c_top;
-    for (int lvl = c.n_levels - 1; lvl >= 0; --lvl) {
-        const size_t rows = map_rows(B, res);
-        const int cmax = chan > c.ch * c.ch_mult[lvl] ? chan : c.ch * c.ch_mult[lvl];
-        max_f = std::max(max_f, rows * cmax * 4);
-        max_h = std::max(max_h, rows * cmax * 2);
-        chan = c.ch * c.ch_mult[lvl];
-        if (lvl != 0) {
-            res *= 2;
-            const size_t rows2 = map_rows(B, res);
-            max_h = std::max(max_h, rows2 * chan * 2);
-            max_f = std::max(max_f, rows2 * chan * 4);
-        }
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-    w.fa = take(max_f); w.fb = take(max_f); w.hb = take(max_h); w.xb = take(max_h);
-    plan_stats_attn(w, take, B, m.z_res, m.c_top);
-    w.total = off;
-    return w;
-}
-
 // one downsample phase map (guard rows included): the phase stride of the stride-2 convolution, in rows
 inline long phase_rows(int B, int Ho) { return (long)map_rows(B, Ho); }
 
-VaeWs plan_enc_ws(const uspace_vae_config& c, const EncModel& m, int B) {
-    VaeWs w;
-    size_t max_f = 0, max_h = 0;
-    int res = c.resolution, chan = c.ch;
-    for (int lvl = 0; lvl < c.n_levels; ++lvl) {
-        const int bo = c.ch * c.ch_mult[lvl];
-        const size_t cmax = chan > bo ? chan : bo;
-        max_f = std::max(max_f, map_rows(B, res) * cmax * 4);
-        max_h = std::max(max_h, map_rows(B, res) * cmax * 2);
-        chan = bo;
-        if (lvl != c.n_levels - 1) {
-            res /= 2;
-            max_h = std::max(max_h, 4 * (size_t)phase_rows(B, res) * chan * 2);   // the four phase maps
-            max_f = std::max(max_f, map_rows(B, res) * chan * 4);
+// A map the walk holds: `chan` channels at resolution `res`, as one fp32 map and `phases` bf16 operand maps (4: the phase maps
+// of a downsample, one otherwise).
+struct MapStep { int res, chan, phases; };
+
+// decode: at each level the widest res block, then the upsample conv keeps that level's channels at twice the resolution
+std::vector<MapStep> dec_steps(const uspace_vae_config& c, const VaeModel& m) {
+    std::vector<MapStep> st;
+    int res = m.z_res, chan = m.c_top;
+    for (int lvl = c.n_levels - 1; lvl >= 0; --lvl) {
+        st.push_back({res, std::max(chan, c.ch * c.ch_mult[lvl]), 1});
+        chan = c.ch * c.ch_mult[lvl];
+        if (lvl != 0) {
+            res *= 2;
+            st.push_back({res, chan, 1});
         }
     }
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-    w.fa = take(max_f); w.fb = take(max_f); w.hb = take(max_h); w.xb = take(max_h);
-    plan_stats_attn(w, take, B, m.z_res, m.c_top);
-    w.total = off;
-    return w;
+    return st;
 }
 
-// fp32 checkpoint tensors -> packed blob (the layouts of PKind)
-int pack_params(const ParamTable& m, const float* const* params, int n_params, void* blob, size_t blob_bytes,
-                uspace_stream_t stream) {
-    if (n_params != (int)m.p.size()) return USPACE_ERR_ARG;
-    if (blob_bytes < m.blob_bytes) return USPACE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < n_params; ++i) {
-        const PDesc& d = m.p[i];
-        if (!params[i]) return USPACE_ERR_ARG;
-        char* dst = (char*)blob + d.offset;
-        switch (d.kind) {
-            case P_F32:
-                if (hipMemcpyAsync(dst, params[i], d.bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return USPACE_ERR_LAUNCH;
-                break;
-            case P_CONV1_BF16:
-                US_TRY(uspace_cast_f32_bf16(params[i], (uint16_t*)dst, d.numel, stream));
-                break;
-            case P_CONV3_BF16:
-                hipLaunchKernelGGL(repack_conv3_bf16_kernel, dim3(grid_for(d.numel)), dim3(256), 0, s, params[i], (bf16_t*)dst, d.co, d.ci);
-                US_CHECK_LAUNCH();
-                break;
-            case P_CONV3_F32T:
-                hipLaunchKernelGGL(repack_conv3_f32_kernel, dim3(grid_for(d.numel)), dim3(256), 0, s, params[i], (float*)dst, d.co, d.ci);
-                US_CHECK_LAUNCH();
-                break;
+// encode: at each level the widest res block, then the four phase maps of the downsample at half the resolution
+std::vector<MapStep> enc_steps(const uspace_vae_config& c) {
+    std::vector<MapStep> st;
+    int res = c.resolution, chan = c.ch;
+    for (int lvl = 0; lvl < c.n_levels; ++lvl) {
+        st.push_back({res, std::max(chan, c.ch * c.ch_mult[lvl]), 1});
+        chan = c.ch * c.ch_mult[lvl];
+        if (lvl != c.n_levels - 1) {
+            res /= 2;
+            st.push_back({res, chan, 4});
         }
     }
-    return USPACE_OK;
+    return st;
 }
+
+// two fp32 maps and two bf16 operand buffers sized for the largest step, GroupNorm statistics, the mid-block attention's buffers
+VaeWs plan_ws(const std::vector<MapStep>& steps, int B, int z_res, int c_top) {
+    VaeWs w;
+    size_t max_f = 0, max_h = 0;
+    for (const MapStep& st : steps) {
+        const size_t elems = map_rows(B, st.res) * st.chan;
+        max_f = std::max(max_f, elems * 4);
+        max_h = std::max(max_h, st.phases * elems * 2);
+    }
+    Arena a;
+    w.fa = a.take(max_f); w.fb = a.take(max_f); w.hb = a.take(max_h); w.xb = a.take(max_h);
+    w.stats = a.take((size_t)B * (1 + USPACE_GN_MAX_CHUNKS) * 64 * 4);
+    const size_t T = (size_t)B * z_res * z_res, Cc = c_top, HW = (size_t)z_res * z_res;
+    w.tok = a.take(T * Cc * 2); w.q = a.take(T * Cc * 2); w.k = a.take(T * Cc * 2); w.v = a.take(T * Cc * 2);
+    w.vt = a.take(T * Cc * 2); w.s = a.take(HW * HW * 4); w.pr = a.take(HW * HW * 2); w.o = a.take(T * Cc * 2);
+    w.po = a.take(T * Cc * 4);
+    w.total = a.off;
+    return w;
+}
+VaeWs plan_vae_ws(const uspace_vae_config& c, const VaeModel& m, int B) { return plan_ws(dec_steps(c, m), B, m.z_res, m.c_top); }
+VaeWs plan_enc_ws(const uspace_vae_config& c, const EncModel& m, int B) { return plan_ws(enc_steps(c), B, m.z_res, m.c_top); }
 
 // What the decode and the encode share: the workspace maps, GroupNorm(+SiLU), the 9-slab 3x3 convolution, the ResnetBlock
 // and the mid-block attention.  Two fp32 maps alternate as the residual stream (cur / tmp); hb / xb hold bf16 operands.
@@ -868,32 +812,35 @@ extern "C" int uspace_groupnorm_map_bf16(const float* x, const float* gamma, con
     return USPACE_OK;
 }
 
+int us_repack_conv3(const float* src, void* dst, int co, int ci, bool to_bf16, hipStream_t s) {
+    const dim3 grid(grid_for((long)co * ci * 9)), block(256);
+    if (to_bf16) hipLaunchKernelGGL(repack_conv3_bf16_kernel, grid, block, 0, s, src, (bf16_t*)dst, co, ci);
+    else hipLaunchKernelGGL(repack_conv3_f32_kernel, grid, block, 0, s, src, (float*)dst, co, ci);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
 extern "C" int uspace_vae_num_params(const uspace_vae_config* cfg) {
-    if (!valid_vae(cfg)) return USPACE_ERR_ARG;
-    return (int)build_vae(*cfg).p.size();
+    return valid_vae(cfg) ? build_vae(*cfg).n_params : USPACE_ERR_ARG;
 }
 
 extern "C" long uspace_vae_param_numel(const uspace_vae_config* cfg, int index) {
-    if (!valid_vae(cfg)) return USPACE_ERR_ARG;
-    const VaeModel m = build_vae(*cfg);
-    if (index < 0 || index >= (int)m.p.size()) return USPACE_ERR_ARG;
-    return m.p[index].numel;
+    return valid_vae(cfg) ? build_vae(*cfg).numel(index) : (long)USPACE_ERR_ARG;
 }
 
 extern "C" size_t uspace_vae_weight_bytes(const uspace_vae_config* cfg) {
-    return valid_vae(cfg) ? build_vae(*cfg).blob_bytes : 0;
+    return valid_vae(cfg) ? build_vae(*cfg).bytes() : 0;
 }
 
 extern "C" size_t uspace_vae_workspace_bytes(const uspace_vae_config* cfg, int B) {
     if (!valid_vae(cfg) || B <= 0) return 0;
-    const VaeModel m = build_vae(*cfg);
-    return plan_vae_ws(*cfg, m, B).total;
+    return plan_vae_ws(*cfg, build_vae(*cfg), B).total;
 }
 
 extern "C" int uspace_vae_pack_weights(const uspace_vae_config* cfg, const float* const* params, int n_params,
                                        void* blob, size_t blob_bytes, uspace_stream_t stream) {
-    if (!valid_vae(cfg) || !params || !blob) return USPACE_ERR_ARG;
-    return pack_params(build_vae(*cfg), params, n_params, blob, blob_bytes, stream);
+    if (!valid_vae(cfg)) return USPACE_ERR_ARG;
+    return us_pack_table(build_vae(*cfg), params, n_params, blob, blob_bytes, stream);
 }
 
 static int vae_decode_impl(const uspace_vae_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
@@ -996,31 +943,26 @@ extern "C" int uspace_vae_decode_tap(const uspace_vae_config* cfg, const void* b
 
 // ------------------------------------------------------------------------------------------ encoder
 extern "C" int uspace_vae_enc_num_params(const uspace_vae_config* cfg) {
-    if (!valid_enc(cfg)) return USPACE_ERR_ARG;
-    return (int)build_enc(*cfg).p.size();
+    return valid_enc(cfg) ? build_enc(*cfg).n_params : USPACE_ERR_ARG;
 }
 
 extern "C" long uspace_vae_enc_param_numel(const uspace_vae_config* cfg, int index) {
-    if (!valid_enc(cfg)) return USPACE_ERR_ARG;
-    const EncModel m = build_enc(*cfg);
-    if (index < 0 || index >= (int)m.p.size()) return USPACE_ERR_ARG;
-    return m.p[index].numel;
+    return valid_enc(cfg) ? build_enc(*cfg).numel(index) : (long)USPACE_ERR_ARG;
 }
 
 extern "C" size_t uspace_vae_enc_weight_bytes(const uspace_vae_config* cfg) {
-    return valid_enc(cfg) ? build_enc(*cfg).blob_bytes : 0;
+    return valid_enc(cfg) ? build_enc(*cfg).bytes() : 0;
 }
 
 extern "C" size_t uspace_vae_enc_workspace_bytes(const uspace_vae_config* cfg, int B) {
     if (!valid_enc(cfg) || B <= 0) return 0;
-    const EncModel m = build_enc(*cfg);
-    return plan_enc_ws(*cfg, m, B).total;
+    return plan_enc_ws(*cfg, build_enc(*cfg), B).total;
 }
 
 extern "C" int uspace_vae_enc_pack_weights(const uspace_vae_config* cfg, const float* const* params, int n_params,
                                            void* blob, size_t blob_bytes, uspace_stream_t stream) {
-    if (!valid_enc(cfg) || !params || !blob) return USPACE_ERR_ARG;
-    return pack_params(build_enc(*cfg), params, n_params, blob, blob_bytes, stream);
+    if (!valid_enc(cfg)) return USPACE_ERR_ARG;
+    return us_pack_table(build_enc(*cfg), params, n_params, blob, blob_bytes, stream);
 }
 
 static int vae_encode_impl(const uspace_vae_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
@@ -1030,15 +972,8 @@ static int vae_encode_impl(const uspace_vae_config* cfg, const void* blob, void*
     const uspace_vae_config& c = *cfg;
     const EncModel m = build_enc(c);
     // 32-bit element offsets (GEMM operands, GroupNorm rows): every map of the chunk stays below 2^30 elements
-    {
-        int res = c.resolution, chan = c.ch;
-        for (int lvl = 0; lvl < c.n_levels; ++lvl) {
-            const int bo = c.ch * c.ch_mult[lvl];
-            if ((long)B * (res + 2) * (res + 2) * std::max(chan, bo) >= (1L << 30)) return USPACE_ERR_ARG;
-            chan = bo;
-            if (lvl != c.n_levels - 1) res /= 2;
-        }
-    }
+    for (const MapStep& st : enc_steps(c))
+        if ((long)B * (st.res + 2) * (st.res + 2) * st.chan >= (1L << 30)) return USPACE_ERR_ARG;
     const VaeWs w = plan_enc_ws(c, m, B);
     if (workspace_bytes < w.total) return USPACE_ERR_WORKSPACE;
     VaeRun r(m, w, blob, workspace, B, stream);

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
+from .._blob import PackedWeights, WorkspaceCache
 
 
 class ParamGroup(nn.Module):
@@ -68,8 +69,11 @@ class UViTBase(nn.Module):
         self.seq_len = self.extras + self.num_patches
         self._cfg = _hip.UvitConfig(img_size, patch_size, in_chans, embed_dim, depth, num_heads, self.hidden,
                                     n_extra, clip_dim, time_first)
-        self._packed = None          # (device, versions, blob)
-        self._workspace = {}         # (B, device) -> uint8 tensor, at most _MAX_WORKSPACES, least recently used first
+        self._packed = PackedWeights("uspace_uvit_", "U-ViT", self._canonical_params, self._cfg)
+        # The two most recently used batch sizes stay resident: the ``write_scales`` sweep of BASELINE config 5 alternates one
+        # B x n_scales solve with plain B solves (tools/utils_vis.py:189-198), and one slot would reallocate hundreds of MB at
+        # every switch.
+        self._workspace = WorkspaceCache(2)
         self._delta_cache = {}
         # Replay a captured hipGraph for plain (un-hooked) evaluations.  Off by default since round 3: one C call enqueues a whole
         # evaluation and the kernels take longer to run than to launch at every batch size, so the replay only adds its three small
@@ -176,60 +180,20 @@ class UViTBase(nn.Module):
         return []
 
     def _packed_blob(self, device):
-        ps = self._canonical_params()
-        versions = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._packed is not None and self._packed[0] == device and self._packed[1] == versions:
-            return self._packed[2]
-        L = _hip.lib()
-        cfg = self._cfg
-        n = L.uspace_uvit_num_params(ctypes.byref(cfg))
-        if n != len(ps):
-            raise _hip.UspaceHipError(f"parameter count mismatch: module {len(ps)} vs library {n}")
-        srcs = []
-        for i, p in enumerate(ps):
-            _hip.require_device(p, "parameter")
-            want = L.uspace_uvit_param_numel(ctypes.byref(cfg), i)
-            if p.numel() != want:
-                raise _hip.UspaceHipError(f"parameter {i}: numel {p.numel()} != {want}")
-            srcs.append(p.detach().to(torch.float32).contiguous())
-        nbytes = L.uspace_uvit_weight_bytes(ctypes.byref(cfg))
-        blob = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        arr = (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs])
-        _hip.check(L.uspace_uvit_pack_weights(ctypes.byref(cfg), arr, n, _hip.ptr(blob), nbytes, _hip.stream_ptr()),
-                   "uspace_uvit_pack_weights")
-        _hip.sync_current_stream()   # srcs may be temporaries
-        self._packed = (device, versions, blob)
-        return blob
+        return self._packed.blob(device)
 
     def invalidate_packed(self):
         """Forget the packed bf16 weight blob (and the hipGraphs captured over it): the next forward repacks from the
-        parameters.  Needed only after IN-PLACE edits through ``p.data`` (``p.data.copy_(w)``, ``p.data.mul_()``), which
-        change neither the parameter's version counter nor its storage -- the two things ``_packed_blob`` watches;
-        ``load_state_dict``, ``.to()``, optimiser steps and plain in-place ops on the parameter are picked up by itself."""
-        self._packed = None
+        parameters.  When that is needed: ``PackedWeights.invalidate``."""
+        self._packed.invalidate()
         for ent in self._graphs.values():
             ent.destroy()
         self._graphs = {}
 
     repack = invalidate_packed
 
-    _MAX_WORKSPACES = 2
-
     def _workspace_for(self, B, device):
-        """Workspace of ``uspace_uvit_workspace_bytes(B)`` bytes.  The two most recently used batch sizes stay resident
-        (least recently used goes first): the ``write_scales`` sweep of BASELINE config 5 alternates one B x n_scales solve
-        with plain B solves (tools/utils_vis.py:189-198), and one slot would reallocate hundreds of MB at every switch."""
-        key = (B, str(device))
-        ws = self._workspace.pop(key, None)
-        # (asked every time: a host-side query; the size depends on the library's process-wide switches -- uspace_gemm_set_sk --, and a
-        # workspace sized under another setting must not be handed on)
-        nbytes = _hip.lib().uspace_uvit_workspace_bytes(ctypes.byref(self._cfg), B)
-        if ws is None or ws.numel() < nbytes:
-            while len(self._workspace) >= self._MAX_WORKSPACES:
-                self._workspace.pop(next(iter(self._workspace)))          # dicts keep insertion order: the oldest use
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self._workspace[key] = ws            # most recently used last
-        return ws
+        return self._workspace.take(B, device, _hip.lib().uspace_uvit_workspace_bytes(ctypes.byref(self._cfg), B))
 
     # ------------------------------------------------------------------ hipGraph replay (plain evaluations)
     _MAX_GRAPHS = 4

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
+from .._blob import PackedWeights, WorkspaceCache
 from ._uvit_core import ParamGroup
 
 
@@ -115,10 +116,12 @@ class FrozenAutoencoderKL(nn.Module):
         self.post_quant_conv.add("weight", self.z_channels, embed_dim, 1, 1)
         self.post_quant_conv.add("bias", self.z_channels)
         self._reference_init_()
-        self._packed = None
-        self._packed_enc = None
-        self._ws = {}
-        self._ws_enc = {}
+        mult = (ctypes.c_int * 4)(*(list(self.ch_mult) + [0] * (4 - nres)))
+        self._cfg = _hip.VaeConfig(self.ch, mult, nres, self.num_res_blocks, self.resolution)
+        self._packed = PackedWeights("uspace_vae_", "VAE", self._canonical_params, self._cfg)
+        self._packed_enc = PackedWeights("uspace_vae_enc_", "VAE encoder", self._canonical_enc_params, self._cfg)
+        self._ws = WorkspaceCache(1)
+        self._ws_enc = WorkspaceCache(1)
         if pretrained_path is not None:
             self.load_state_dict(torch.load(pretrained_path, map_location="cpu"))
         self.eval()
@@ -217,52 +220,30 @@ class FrozenAutoencoderKL(nn.Module):
 
     # ------------------------------------------------------------------ HIP decode
     def invalidate_packed(self):
-        """Forget the packed weight blobs; needed only after in-place edits through ``p.data`` (same contract as
-        UViT.invalidate_packed)."""
-        self._packed = None
-        self._packed_enc = None
+        """Forget the packed weight blobs; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
+        self._packed.invalidate()
+        self._packed_enc.invalidate()
 
-    def _config(self):
-        mult = (ctypes.c_int * 4)(*(list(self.ch_mult) + [0] * (4 - len(self.ch_mult))))
-        self._cfg = _hip.VaeConfig(self.ch, mult, len(self.ch_mult), self.num_res_blocks, self.resolution)
-        return self._cfg
+    def _canonical_params(self):
+        """The decoder half (decoder.*, post_quant_conv.*), packed for uspace_vae_decode."""
+        return list(self.decoder.parameters()) + list(self.post_quant_conv.parameters())
 
-    def _pack(self, ps, cached, prefix, what, device):
-        """(blob, cache entry) of ``ps`` packed by the library's ``{prefix}pack_weights``; reuses ``cached`` while no
-        parameter has changed."""
-        versions = tuple((p.data_ptr(), p._version) for p in ps)
-        if cached is not None and cached[0] == device and cached[1] == versions:
-            return cached[2], cached
-        L = _hip.lib()
-        cfg = ctypes.byref(self._config())
-        n = getattr(L, prefix + "num_params")(cfg)
-        if n != len(ps):
-            raise _hip.UspaceHipError(f"{what} parameter count mismatch: module {len(ps)} vs library {n}")
-        srcs = []
-        for i, p in enumerate(ps):
-            _hip.require_device(p, "parameter")
-            if p.numel() != getattr(L, prefix + "param_numel")(cfg, i):
-                raise _hip.UspaceHipError(f"{what} parameter {i}: unexpected size {tuple(p.shape)}")
-            srcs.append(p.detach().to(torch.float32).contiguous())
-        nbytes = getattr(L, prefix + "weight_bytes")(cfg)
-        blob = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        arr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-        _hip.check(getattr(L, prefix + "pack_weights")(cfg, arr, n, _hip.ptr(blob), nbytes, _hip.stream_ptr()),
-                   prefix + "pack_weights")
-        torch.cuda.current_stream().synchronize()
-        return blob, (device, versions, blob)
+    def _canonical_enc_params(self):
+        """The encoder half (encoder.*, quant_conv.*), packed for uspace_vae_encode_moments."""
+        return list(self.encoder.parameters()) + list(self.quant_conv.parameters())
 
     def _packed_blob(self, device):
-        """The decoder half (decoder.*, post_quant_conv.*) packed for uspace_vae_decode."""
-        ps = list(self.decoder.parameters()) + list(self.post_quant_conv.parameters())
-        blob, self._packed = self._pack(ps, self._packed, "uspace_vae_", "VAE", device)
-        return blob
+        return self._packed.blob(device)
 
     def _packed_enc_blob(self, device):
-        """The encoder half (encoder.*, quant_conv.*) packed for uspace_vae_encode_moments."""
-        ps = list(self.encoder.parameters()) + list(self.quant_conv.parameters())
-        blob, self._packed_enc = self._pack(ps, self._packed_enc, "uspace_vae_enc_", "VAE encoder", device)
-        return blob
+        return self._packed_enc.blob(device)
+
+    def _tap_map(self, dump, hc, B):
+        """What a ``*_tap`` entry point left in ``dump`` (zero-bordered NHWC, hc = {H, C}) as [B, C, H, W]."""
+        torch.cuda.synchronize()
+        H, C = hc[0], hc[1]
+        m = dump[: B * (H + 2) * (H + 2) * C].view(B, H + 2, H + 2, C)
+        return m[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).contiguous()
 
     def decode(self, z, chunk=8):
         """z [B,4,h,h] (scaled latents, as produced by the sampler) -> images [B,3,R,R] fp32.  Decodes ``chunk``
@@ -280,11 +261,7 @@ class FrozenAutoencoderKL(nn.Module):
         out = torch.empty(B, self.out_ch, self.resolution, self.resolution, dtype=torch.float32, device=dev)
         max_chunk = _max_chunk([(self.resolution, 512)])
         chunk = max(1, min(chunk, max_chunk, B))
-        key = (chunk, str(dev))
-        if key not in self._ws:
-            nbytes = L.uspace_vae_workspace_bytes(ctypes.byref(self._cfg), chunk)
-            self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=dev)}
-        ws = self._ws[key]
+        ws = self._ws.take(chunk, dev, L.uspace_vae_workspace_bytes(ctypes.byref(self._cfg), chunk))
         for lo in range(0, B, chunk):
             n = min(chunk, B - lo)
             _hip.check(L.uspace_vae_decode(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
@@ -306,10 +283,7 @@ class FrozenAutoencoderKL(nn.Module):
         _hip.check(L.uspace_vae_decode_tap(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(zin),
                                            float(self.scale_factor), B, int(stage), _hip.ptr(dump), hc, _hip.stream_ptr()),
                    "uspace_vae_decode_tap")
-        torch.cuda.synchronize()
-        H, C = hc[0], hc[1]
-        m = dump[: B * (H + 2) * (H + 2) * C].view(B, H + 2, H + 2, C)
-        return m[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).contiguous()
+        return self._tap_map(dump, hc, B)
 
     # ------------------------------------------------------------------ HIP encode
     def _require_encoder(self, what):
@@ -346,11 +320,7 @@ class FrozenAutoencoderKL(nn.Module):
         B = xin.shape[0]
         out = torch.empty(B, 2 * self.embed_dim, h, h, dtype=torch.float32, device=dev)
         chunk = max(1, min(chunk, self.max_encode_chunk(), B))
-        key = (chunk, str(dev))
-        if key not in self._ws_enc:
-            nbytes = L.uspace_vae_enc_workspace_bytes(ctypes.byref(self._cfg), chunk)
-            self._ws_enc = {key: torch.empty(nbytes, dtype=torch.uint8, device=dev)}
-        ws = self._ws_enc[key]
+        ws = self._ws_enc.take(chunk, dev, L.uspace_vae_enc_workspace_bytes(ctypes.byref(self._cfg), chunk))
         for lo in range(0, B, chunk):
             n = min(chunk, B - lo)
             _hip.check(L.uspace_vae_encode_moments(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
@@ -396,10 +366,7 @@ class FrozenAutoencoderKL(nn.Module):
         hc = (ctypes.c_int * 2)()
         _hip.check(L.uspace_vae_encode_tap(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(xin),
                                            B, int(stage), _hip.ptr(dump), hc, _hip.stream_ptr()), "uspace_vae_encode_tap")
-        torch.cuda.synchronize()
-        H, C = hc[0], hc[1]
-        m = dump[: B * (H + 2) * (H + 2) * C].view(B, H + 2, H + 2, C)
-        return m[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).contiguous()
+        return self._tap_map(dump, hc, B)
 
     def forward(self, inputs, fn):
         if fn == "decode":

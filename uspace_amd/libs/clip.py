@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
+from .._blob import PackedWeights, WorkspaceCache
 from ._uvit_core import ParamGroup
 
 CLIP_L_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
@@ -110,8 +111,8 @@ class CLIPTextTransformer(nn.Module):
                     prm.zero_()
                 else:
                     prm.normal_(0.0, 0.02)
-        self._packed = None
-        self._ws = {}
+        self._packed = PackedWeights("uspace_clip_", "CLIP", self._canonical_params, self._c_cfg())
+        self._ws = WorkspaceCache(1)
         self.eval()
         self.requires_grad_(False)
 
@@ -132,34 +133,14 @@ class CLIPTextTransformer(nn.Module):
         return _hip.ClipConfig(c["vocab"], c["dim"], c["heads"], c["layers"], c["ffn"], c["max_pos"], c["eps"])
 
     def invalidate_packed(self):
-        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (same contract as
-        UViT.invalidate_packed)."""
-        self._packed = None
+        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
+        self._packed.invalidate()
+
+    def _canonical_params(self):
+        return list(self.parameters())
 
     def _packed_blob(self, device):
-        ps = list(self.parameters())
-        versions = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._packed is not None and self._packed[0] == device and self._packed[1] == versions:
-            return self._packed[2]
-        L = _hip.lib()
-        cfg = self._c_cfg()
-        n = L.uspace_clip_num_params(ctypes.byref(cfg))
-        if n != len(ps):
-            raise _hip.UspaceHipError(f"CLIP parameter count mismatch: module {len(ps)} vs library {n}")
-        srcs = []
-        for i, p in enumerate(ps):
-            _hip.require_device(p, "parameter")
-            if p.numel() != L.uspace_clip_param_numel(ctypes.byref(cfg), i):
-                raise _hip.UspaceHipError(f"CLIP parameter {i}: unexpected size {tuple(p.shape)}")
-            srcs.append(p.detach().to(torch.float32).contiguous())
-        nbytes = L.uspace_clip_weight_bytes(ctypes.byref(cfg))
-        blob = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        arr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-        _hip.check(L.uspace_clip_pack_weights(ctypes.byref(cfg), arr, n, _hip.ptr(blob), nbytes, _hip.stream_ptr()),
-                   "uspace_clip_pack_weights")
-        torch.cuda.current_stream().synchronize()
-        self._packed = (device, versions, blob)
-        return blob
+        return self._packed.blob(device)
 
     def forward(self, input_ids, hidden_state=None):
         """input_ids [B, L<=max_pos] integer tensor -> last_hidden_state [B, L, D] fp32 (``hidden_state=k``: the state
@@ -176,10 +157,7 @@ class CLIPTextTransformer(nn.Module):
         L = _hip.lib()
         cfg = self._c_cfg()
         B, T = input_ids.shape
-        key = (B, str(dev))
-        if key not in self._ws:
-            self._ws = {key: torch.empty(L.uspace_clip_workspace_bytes(ctypes.byref(cfg), B), dtype=torch.uint8, device=dev)}
-        ws = self._ws[key]
+        ws = self._ws.take(B, dev, L.uspace_clip_workspace_bytes(ctypes.byref(cfg), B))
         ids = input_ids.to(torch.int32).contiguous()
         out = torch.empty(B, T, self.cfg["dim"], dtype=torch.float32, device=dev)
         _hip.check(L.uspace_clip_text_forward(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(ids),

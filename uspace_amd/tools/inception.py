@@ -5,13 +5,13 @@ or from pytorch-fid's cache, ``torch.hub.get_dir()/checkpoints/pt_inception-2015
 The module's state_dict uses the keys of torchvision's ``Inception3`` (``Conv2d_1a_3x3.conv.weight``,
 ``Mixed_5b.branch1x1.bn.running_var``, ...), so the pytorch-fid weight file loads directly; its ``fc.*`` and
 ``*.num_batches_tracked`` entries are accepted and ignored."""
-import ctypes
 import os
 
 import torch
 import torch.nn as nn
 
 from uspace_amd import _hip
+from uspace_amd._blob import PackedWeights, WorkspaceCache
 
 FID_WEIGHTS_FILE = "pt_inception-2015-12-05-6726825d.pth"
 
@@ -157,8 +157,8 @@ class InceptionV3(nn.Module):
             self.load_state_dict(torch.load(path, map_location="cpu"))
         for p in self.parameters():
             p.requires_grad = requires_grad
-        self._packed = None
-        self._ws = {}
+        self._packed = PackedWeights("uspace_inception_", "Inception", self._canonical_params)
+        self._ws = WorkspaceCache(1)
 
     @torch.no_grad()
     def _seed(self, seed):
@@ -186,44 +186,21 @@ class InceptionV3(nn.Module):
         for k, v in sd.items():
             if tuple(v.shape) != tuple(own[k].shape):
                 raise ValueError(f"FID Inception state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(own[k].shape)}")
-        self._packed = None
         return super().load_state_dict(sd, strict=True, assign=assign)
 
     def invalidate_packed(self):
-        """Forget the packed weight blob; needed only after in-place edits through ``p.data``."""
-        self._packed = None
+        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
+        self._packed.invalidate()
 
     # ------------------------------------------------------------------------------------------------ kernels
+    def _canonical_params(self):
+        return list(self.state_dict().values())
+
     def _blob(self, device):
-        ts = list(self.state_dict().values())
-        versions = tuple((t.data_ptr(), t._version) for t in ts)
-        if self._packed is not None and self._packed[0] == device and self._packed[1] == versions:
-            return self._packed[2]
-        L = _hip.lib()
-        n = L.uspace_inception_num_params()
-        if n != len(ts):
-            raise _hip.UspaceHipError(f"Inception parameter count mismatch: module {len(ts)} vs library {n}")
-        srcs = []
-        for i, t in enumerate(ts):
-            _hip.require_device(t, "Inception parameter")
-            if t.numel() != L.uspace_inception_param_numel(i):
-                raise _hip.UspaceHipError(f"Inception parameter {i}: unexpected size {tuple(t.shape)}")
-            srcs.append(t.detach().to(torch.float32).contiguous())
-        nbytes = L.uspace_inception_weight_bytes()
-        blob = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        arr = (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs])
-        _hip.check(L.uspace_inception_pack_weights(arr, n, _hip.ptr(blob), nbytes, _hip.stream_ptr()),
-                   "uspace_inception_pack_weights")
-        torch.cuda.current_stream().synchronize()
-        self._packed = (device, versions, blob)
-        return blob
+        return self._packed.blob(device)
 
     def _workspace(self, B, H, W, device):
-        key = (B, str(device))
-        if key not in self._ws:
-            nbytes = _hip.lib().uspace_inception_workspace_bytes(B, H, W)
-            self._ws = {key: torch.empty(nbytes, dtype=torch.uint8, device=device)}
-        return self._ws[key]
+        return self._ws.take(B, device, _hip.lib().uspace_inception_workspace_bytes(B, H, W))
 
     def _input(self, inp):
         _hip.require_device(inp, "input")
