@@ -179,21 +179,37 @@ USPACE_API int uspace_layernorm_f32_bf16(const float* x, const float* gamma, con
  * key_scale (optional, [B, L] fp32): the post-softmax map is multiplied column-wise by it
  * before P.V, without renormalisation -- the attention-map edit of
  * tools/utils_t2i.py:196-224 at libs/uvit_t2i.py:101-105, applied as a row scaling of V.
- * L <= 336; which kernel form and grid a call launches: uspace_attention_plan. */
+ * L <= 336 (K and V of a head resident in LDS; longer sequences: uspace_attention_long_bf16); which kernel form and grid a call
+ * launches: uspace_attention_plan. */
 USPACE_API int uspace_attention_bf16(const uint16_t* qkv, const float* key_scale, uint16_t* out,
                           int B, int L, int H, uspace_stream_t stream);
 /* host-side, no GPU work: out[8] = {NT, LC, NW, QS, HPW, grid, block, dynamic LDS bytes} of the launch
- * uspace_attention_bf16 takes for (B, L, H, key_scale != NULL); USPACE_ERR_ARG where that call would refuse.
+ * uspace_attention_bf16 takes for (B, L, H, key_scale != NULL); USPACE_ERR_ARG where that call would refuse (L > 336 among them:
+ * uspace_attention_long_plan).
  * NT 16-key tiles the kernel is compiled for, LC its compile-time length (0 = any length up to 16 NT), NW waves per workgroup,
  * QS workgroups per (batch, head), HPW heads per workgroup. */
 USPACE_API int uspace_attention_plan(int B, int L, int H, int scaled, int* out);
+
+/* The long form of uspace_attention_bf16: same qkv, key_scale and out, same key_scale semantics (bf16(P ks) feeds P.V, bf16(P) the
+ * row sum, no renormalisation; a sample whose scales are all 0 comes out exactly 0), any L >= 1.  K and V stream through LDS in key
+ * tiles under an fp32 online softmax (running row maximum and sum; P rounded to bf16 once per key tile).  A query row's keys are never
+ * split across workgroups and there are no atomics: a row's bits depend on neither B, H nor the grid, and repeat from run to run.
+ * The U-ViT forward takes it for L > 336.  USPACE_ERR_ARG for B, L or H <= 0, NULL qkv / out, or B * L, 3 * H * 64, B * H or the
+ * grid beyond INT_MAX. */
+USPACE_API int uspace_attention_long_bf16(const uint16_t* qkv, const float* key_scale, uint16_t* out,
+                                          int B, int L, int H, uspace_stream_t stream);
+/* host-side, no GPU work: out[6] = {KT, QB, NW, grid, block, dynamic LDS bytes} of the launch uspace_attention_long_bf16 takes for
+ * (B, L, H, key_scale != NULL); USPACE_ERR_ARG where that call would refuse.  KT keys per key tile, QB queries per workgroup
+ * (grid = B * H * ceil(L / QB)), NW waves per workgroup. */
+USPACE_API int uspace_attention_long_plan(int B, int L, int H, int scaled, int* out);
 
 /* Head-mean attention map of the same packed qkv (what tools/utils_t2i.py:141-193 vis_attention_map draws from the reference's
  * [B, H, L, L] softmax, libs/uvit_t2i.py:101-103):
  *     out[b, i, j] = (1/H) * sum_h softmax_k( q[b,h,q0+i] . k[b,h,k] * 64^-0.5 )[k0+j]       fp32, [B, nq, nk]
  * The softmax runs over ALL L keys, not the window.  No key_scale: the reference shows the map before the edit
  * (tools/utils_t2i.py:283 precedes :286).  P stays fp32; the heads are summed in the order 0 .. H-1 by the one workgroup that owns
- * a (sample, 16-query tile): no atomics, bit-equal from run to run and for any B.  head_dim 64, L <= 336, 0 <= q0, nq >= 1,
+ * a (sample, 16-query tile): no atomics, bit-equal from run to run and for any B.  head_dim 64, L <= 336 (there is no long form of the
+ * map), 0 <= q0, nq >= 1,
  * q0 + nq <= L and the same for k0 / nk; anything else returns USPACE_ERR_ARG. */
 USPACE_API int uspace_attention_map_bf16(const uint16_t* qkv, float* out, int B, int L, int H,
                                          int q0, int nq, int k0, int nk, uspace_stream_t stream);
@@ -492,7 +508,8 @@ USPACE_API int uspace_quick_gelu_bf16(uint16_t* x, long n, uspace_stream_t strea
 USPACE_API int uspace_prof_gemm_begin(int epi_flags, int N, int K, int max_launches);
 USPACE_API int uspace_prof_gemm_end(double* total_ms, int* n_launches);
 /* The same around EVERY GEMM and attention launch (bench.py's roofline_all): _end() aggregates the recorded launches by
- * (kind, flags, M, N, K) into keys[6 * i + {0: kind (0 GEMM, 1 attention), 1: epi_flags (attention: 1 = key scales),
+ * (kind, flags, M, N, K) into keys[6 * i + {0: kind (0 GEMM, 1 attention), 1: epi_flags (attention: 1 = key scales, 2 = the streaming form
+ * uspace_attention_long_bf16),
  * 2: M (attention: B * H), 3: N (attention: L), 4: K (attention: head dim), 5: launches}] and total_ms[i], i < *n_records <= max_records. */
 USPACE_API int uspace_prof_all_begin(int max_launches);
 USPACE_API int uspace_prof_all_end(int* keys, double* total_ms, int max_records, int* n_records);

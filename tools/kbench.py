@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Kernel micro-benchmarks at the BASELINE shapes (run on the GPU box): GEMMs, attention, LayerNorm."""
+"""Kernel micro-benchmarks at the BASELINE shapes (run on the GPU box): GEMMs, attention, LayerNorm.
+``--long``: the long-sequence attention kernel alone (profiles/attention_long.md)."""
 import argparse
 import os
 import sys
@@ -23,12 +24,35 @@ def timeit(fn, reps=20, warm=3):
     return s.elapsed_time(e) / reps * 1e-3
 
 
+BF16_NOMINAL = 2.5e15       # dense bf16 MFMA rate of the MI355X, FLOP/s
+
+
+def attention_long_rows():
+    """The streaming attention kernel (uspace_attention_long_bf16) at 64 x 64 latents -- L = 1 025 (unconditional) and 1 102 (T2I) at
+    B * H = 16 and 1 024 -- and at L = 334 beside the resident kernel: time, TFLOP/s (4 L^2 64 per head) and the share of the nominal rate."""
+    H = 16
+    print("| kernel | B x H | L | key_scale | us | TFLOP/s | of 2.5 PF |\n|---|---|---|---|---|---|---|")
+    for L in (1025, 1102, 334):
+        for B in (1, 64):
+            qkv = torch.randn(B * L, 3 * H * 64, device="cuda").to(torch.bfloat16)
+            for scaled in (False, True):
+                ks = torch.exp(torch.rand(B, L, device="cuda") * 2 - 1) if scaled else None
+                forms = [("long", _hip.attention_long)] + ([("resident", _hip.attention)] if L <= 336 else [])
+                for name, fn in forms:
+                    t = timeit(lambda: fn(qkv, B, L, H, key_scale=ks), reps=50, warm=5)
+                    fl = 4.0 * L * L * 64 * B * H
+                    print(f"| {name} | {B} x {H} | {L} | {'yes' if scaled else 'no'} | {t * 1e6:.1f} | {fl / t / 1e12:.1f} | {fl / t / BF16_NOMINAL:.3f} |")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--long", action="store_true", help="only the long-sequence attention rows")
     ap.add_argument("--B", type=int, default=64)
     ap.add_argument("--L", type=int, default=257)
     ap.add_argument("--D", type=int, default=1024)
     a = ap.parse_args()
+    if a.long:
+        return attention_long_rows()
     M, D = a.B * a.L, a.D
     dev = "cuda"
     bf = torch.bfloat16

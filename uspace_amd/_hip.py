@@ -84,6 +84,8 @@ SIGNATURES = {
     "uspace_layernorm_f32_bf16": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "uspace_attention_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "uspace_attention_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "uspace_attention_long_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "uspace_attention_long_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I)]),
     "uspace_attention_map_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "uspace_embed_tokens": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "uspace_output_head": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
@@ -298,6 +300,15 @@ def attention(qkv, B, L, H, key_scale=None):
     out = torch.empty(B * L, H * 64, dtype=torch.bfloat16, device=qkv.device)
     check(lib().uspace_attention_bf16(ptr(qkv), ptr(key_scale), ptr(out), B, L, H, stream_ptr()),
           "uspace_attention_bf16")
+    return out
+
+
+def attention_long(qkv, B, L, H, key_scale=None):
+    """The streaming form of ``attention`` (K and V in key tiles, online softmax): any L; what the forward takes for L > 336."""
+    require_device(qkv, "qkv")
+    out = torch.empty(B * L, H * 64, dtype=torch.bfloat16, device=qkv.device)
+    check(lib().uspace_attention_long_bf16(ptr(qkv), ptr(key_scale), ptr(out), B, L, H, stream_ptr()),
+          "uspace_attention_long_bf16")
     return out
 
 

@@ -19,7 +19,7 @@
 //   row sums: one more MFMA per step against an all-ones tile (see below).
 // The optional key_scale[B,L] multiplies P column-wise after normalisation (attention-map edit
 // of the reference, tools/utils_t2i.py:196-224), i.e. it scales P before P.V but not the row sum.
-#include "common.h"
+#include "attention_tiles.h"
 
 // lab switch (tools/lab/build_variant.sh att_w4 attention.hip "-DUSPACE_ATT_W4=1"; measured in round 4 and not taken: 39.0 -> 43.5 us):
 // L = 257 on 8-wave workgroups, four waves per SIMD at 128 registers
@@ -60,25 +60,6 @@ __device__ unsigned long long g_att_trace[2 * 4 * 64];
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-constexpr int DH = 64;
-constexpr int KROW_BYTES = 128;
-
-__device__ __forceinline__ int k_off(int r, int c) { return r * KROW_BYTES + ((c ^ ((r >> 1) & 7)) << 4); }
-
-// V rows are 128 B like K rows, but the transposing read fetches 32-byte pieces of 8 different rows per 32-lane
-// half: 32-B chunk c of row r lives at chunk c ^ ((r >> 1) & 3), which puts those 8 pieces on 8 distinct
-// 32-byte bank groups (row parity selects the 128-B half of the 256-B bank row, the XOR the piece inside it).
-__device__ __forceinline__ int v_off(int r, int c32) { return r * KROW_BYTES + ((c32 ^ ((r >> 1) & 3)) << 5); }
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ uint2 lds_read_tr16(const char* p) {
-    const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-    union { s16x4 v; uint2 u; } c;
-    c.v = r;
-    return c.u;
-}
 
 // The dynamic LDS of a workgroup, for the kernel's pointers and the host's launch alike: K rows (16 per key tile), V rows (32 per
 // P.V step of two key tiles), 128 B each, then one fp32 key scale per K row (SCALED only).
@@ -143,35 +124,17 @@ __global__ __launch_bounds__(64 * NW, NW == 6 ? 3 : (W4 ? 4 : 2)) void attention
 
     // ---- stage K by LDS-DMA: one instruction = 8 rows x 128 B per wave; rows >= L re-read row L-1
     //      (their scores are masked below).  LDS image is lane-linear, the swizzle is on the source.
-    {
-        const int r8 = lane >> 3, cpos = lane & 7;
 #pragma unroll
-        for (int blk = 0; blk < (KROWS / 8 + NW - 1) / NW; ++blk) {
-            const int rb = (blk * NW + wave) * 8;                   // first row of this wave's 8-row block
-            if (rb < KROWS) {
-                const int r = rb + r8;
-                const int c = cpos ^ ((r >> 1) & 7);
-                const int rr = r < L ? r : L - 1;
-                __builtin_amdgcn_global_load_lds((const US_GLB void*)(gk + (size_t)rr * C3 + c * 8),
-                                                 (US_LDS void*)(sK + rb * KROW_BYTES), 16, 0, 0);
-            }
-        }
+    for (int blk = 0; blk < (KROWS / 8 + NW - 1) / NW; ++blk) {
+        const int rb = (blk * NW + wave) * 8;                       // first row of this wave's 8-row block
+        if (rb < KROWS) att_dma_k8(gk, C3, rb, L, sK + rb * KROW_BYTES, lane);
     }
     // ---- stage V the same way (row-major; physical 16-B position cpos holds logical chunk
     //      (((cpos>>1) ^ ((r>>1)&3)) << 1) | (cpos&1))
-    {
-        const int r8 = lane >> 3, cpos = lane & 7;
 #pragma unroll
-        for (int blk = 0; blk < (VROWS / 8 + NW - 1) / NW; ++blk) {
-            const int rb = (blk * NW + wave) * 8;
-            if (rb < VROWS) {
-                const int r = rb + r8;
-                const int c = (((cpos >> 1) ^ ((r >> 1) & 3)) << 1) | (cpos & 1);
-                const int rr = r < L ? r : L - 1;
-                __builtin_amdgcn_global_load_lds((const US_GLB void*)(gv + (size_t)rr * C3 + c * 8),
-                                                 (US_LDS void*)(sV + rb * KROW_BYTES), 16, 0, 0);
-            }
-        }
+    for (int blk = 0; blk < (VROWS / 8 + NW - 1) / NW; ++blk) {
+        const int rb = (blk * NW + wave) * 8;
+        if (rb < VROWS) att_dma_v8(gv, C3, rb, L, sV + rb * KROW_BYTES, lane);
     }
     if constexpr (SCALED) {
         for (int k = tid; k < KROWS; k += 64 * NW) sKs[k] = k < L ? key_scale[(size_t)b * L + k] : 0.f;
@@ -303,9 +266,7 @@ __global__ __launch_bounds__(64 * NW, NW == 6 ? 3 : (W4 ? 4 : 2)) void attention
                 for (int r = 0; r < 4; ++r) s[t][r] = (t * 16 + fq * 4 + r) <= (q0 + fr) ? s[t][r] : -INFINITY;
         }
         // ---- row max
-        // four independent chains (a single one is NT dependent v_max3_f32), then the 16-lane rows: v_permlane16_swap / v_permlane32_swap
-        // on two copies of the value leave rows (0, 0, 2, 2) | (1, 1, 3, 3) resp. halves (lo, lo) | (hi, hi) -- one VALU instruction where
-        // __shfl_xor is a trip through the LDS crossbar
+        // four independent chains (a single one is NT dependent v_max3_f32), then the 16-lane rows (att_max_over_rows)
         float mq[4] = {s[0][0], s[0][0], s[0][0], s[0][0]};
 #pragma unroll
         for (int t = 0; t < NT; ++t) {   // two v_max3_f32 per tile (nested form the backend fuses)
@@ -313,12 +274,7 @@ __global__ __launch_bounds__(64 * NW, NW == 6 ? 3 : (W4 ? 4 : 2)) void attention
             mq[(2 * t + 1) & 3] = fmaxf(fmaxf(mq[(2 * t + 1) & 3], s[t][2]), s[t][3]);
         }
         float mx = fmaxf(fmaxf(mq[0], mq[1]), fmaxf(mq[2], mq[3]));
-        {
-            const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-            const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-        }
+        mx = att_max_over_rows(mx);
         const float mc = mx * c_exp;
         ATT_STAMP(tr_slot++)   // row maximum known
         // p = 2^(s*c - mx*c), one 32-key step (two key tiles) at a time
@@ -357,16 +313,9 @@ __global__ __launch_bounds__(64 * NW, NW == 6 ? 3 : (W4 ? 4 : 2)) void attention
         VF vb[2][4];
         PF pb[2];
         auto load_v = [&](int u, VF (&dst)[4]) {
-            // group fq of 16 lanes points at V[(2u)*16 + 4fq + 0..3][dt*16 .. +15] (lane a: key row a/4, dims 4(a%4)..+3)
-            // and receives, per lane, dim dt*16+fr of those 4 keys; the second read does tile 2u+1 (16 rows on:
-            // same swizzle key, +2048 B)
-            const int vrow = fq * 4 + (fr >> 2);
+            // (att_read_vt: tiles 2u and 2u + 1)
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const char* pv = sV + v_off(vrow, dt) + ((fr & 3) << 3) + u * (32 * KROW_BYTES);
-                dst[dt].h[0] = lds_read_tr16(pv);
-                dst[dt].h[1] = lds_read_tr16(pv + 16 * KROW_BYTES);
-            }
+            for (int dt = 0; dt < 4; ++dt) att_read_vt(sV, fq, fr, dt, u * (32 * KROW_BYTES), dst[dt].h[0], dst[dt].h[1]);
         };
         auto pack_p = [&](int u, PF& pf) {
             pf.w[0] = pack_bf2(s[2 * u][0], s[2 * u][1]);
