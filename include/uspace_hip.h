@@ -245,6 +245,14 @@ USPACE_API int uspace_add_broadcast(float* x, uint16_t* x_bf16, const float* del
 USPACE_API int uspace_add_broadcast_rows(float* x, uint16_t* x_bf16, const float* delta, float scale,
                                          const float* row_scale, int B, long per_sample, uspace_stream_t stream);
 
+/* Classifier-free guidance, U-ViT's convention (the configs' sample.scale): out[b, i] = c + s_b * (c - u) with c = pair[b, i],
+ * u = pair[B + b, i] and s_b = scale * row_scale[b] (row_scale: device float[B] or NULL = ones), evaluated in fp32 as
+ * fmaf(s_b, c - u, c); s_b == 0 returns c bit for bit.  pair [2B, per_sample] holds the conditional rows first, out is
+ * [B, per_sample] and overlaps neither half of pair.  16-byte accesses where per_sample % 4 == 0 and both pointers are 16-byte
+ * aligned, a scalar form otherwise; no atomics. */
+USPACE_API int uspace_cfg_combine(const float* pair, const float* row_scale, float scale, float* out, int B, long per_sample,
+                                  uspace_stream_t stream);
+
 /* Attribute-direction statistics kept on the device (reference: tools/utils_attr.py:124-145 computes
  * mean(feat[attr==1]) - mean(feat[attr==0]) in numpy from activations the read hook staged through disk):
  *   pos_sum[a, f] += sum_n [attr[n,a] == 1] * feat[n, f];  neg_sum likewise for attr == 0.
@@ -345,6 +353,26 @@ USPACE_API int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* bl
 USPACE_API int uspace_uvit_forward_maps(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
                                         const uspace_uvit_io* io, int B, int q0, int nq, int k0, int nk, float* maps,
                                         uspace_stream_t stream);
+
+/* Classifier-free guidance inside the forward: ONE evaluation over 2B rows -- row b the conditional branch (x[b], t[b], context[b]),
+ * row B + b the unconditional one (x[b], t[b], uncond[b], or uncond itself when uncond_batched == 0) -- and one uspace_cfg_combine
+ * (scale, row_scale as there) of the 2B predictions into io->out [B,C,S,S].
+ *   io       describes the B samples as for uspace_uvit_forward.  key_scale, when given, is [depth+1, 2B, L] (the caller puts ones in
+ *            the rows of the unconditional half); mid_delta / mid_scale act on all 2B rows; mid_row_scale, when given, is float[2B];
+ *            mid_tap must be NULL.
+ *   uncond   the unconditional branch's context in the form of io->context: [n_extra, clip_dim] / [n_extra, D], or B of them.
+ *            A config with n_extra == 0 has no condition to drop: USPACE_ERR_ARG.
+ *   pair_out optional [2B,C,S,S]: receives the 2B predictions (conditional rows first); with NULL they stay in the workspace.
+ *   workspace of uspace_uvit_cfg_workspace_bytes(cfg, B) bytes: a plain forward's at batch 2B, then the predictions.
+ * The launches are those of uspace_uvit_forward at batch 2B -- same GEMM forms, LayerNorm mode and K-split decisions, same attention
+ * launches (and records) -- except that the context cast and the token embedding are issued once per half, each reading x, t and its
+ * context where the caller holds them: neither a doubled x nor a second context batch is staged.  An unbatched uncond is cast into
+ * each sample's rows and embedded with the rest (one GEMM over 2B * n_extra rows).  The 2B predictions are bit-equal to
+ * uspace_uvit_forward at batch 2B on the explicitly concatenated inputs. */
+USPACE_API size_t uspace_uvit_cfg_workspace_bytes(const uspace_uvit_config* cfg, int B);
+USPACE_API int uspace_uvit_forward_cfg(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                       const uspace_uvit_io* io, int B, const float* uncond, int uncond_batched, float scale,
+                                       const float* row_scale, float* pair_out, uspace_stream_t stream);
 
 /* Test aid: run the forward exactly as uspace_uvit_forward does up to the end of stage `stop_after`, then copy the fp32 residual
  * stream x [B,L,D] to `dump` (device) and return.  Stages: 0 the tokens after embed + pos_embed, as block 0 reads them; k = 1 ..

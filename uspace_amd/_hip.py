@@ -92,6 +92,7 @@ SIGNATURES = {
     "uspace_add_broadcast": (_I, [_P, _P, _P, _F, _I, _L, _P]),
     "uspace_add_broadcast_rows": (_I, [_P, _P, _P, _F, _P, _I, _L, _P]),
     "uspace_cast_f32_bf16": (_I, [_P, _P, _L, _P]),
+    "uspace_cfg_combine": (_I, [_P, _P, _F, _P, _I, _L, _P]),
     "uspace_direction_accumulate": (_I, [_P, _P, _P, _P, _I, _L, _I, _P]),
     "uspace_center_cols_f32": (_I, [_P, _P, _I, _L, _P]),
     "uspace_gram_f64": (_I, [_P, _P, _I, _L, _P]),
@@ -106,6 +107,8 @@ SIGNATURES = {
     "uspace_uvit_pack_weights": (_I, [ctypes.POINTER(UvitConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
     "uspace_uvit_forward": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _P]),
     "uspace_uvit_forward_maps": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _I, _I, _I, _I, _P, _P]),
+    "uspace_uvit_cfg_workspace_bytes": (_SZ, [ctypes.POINTER(UvitConfig), _I]),
+    "uspace_uvit_forward_cfg": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _P, _I, _F, _P, _P, _P]),
     "uspace_uvit_forward_tap": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _I, _P, _P]),
     "uspace_uvit_graph_create": (_I, [ctypes.POINTER(UvitConfig), _P, _P, _SZ, ctypes.POINTER(UvitIO), _I, _P,
                                       ctypes.POINTER(_P)]),
@@ -334,6 +337,31 @@ def add_broadcast(x, delta, scale, x_bf16=None, row_scale=None):
     check(lib().uspace_add_broadcast_rows(ptr(x), ptr(x_bf16), ptr(delta), float(scale), ptr(row_scale), B, per,
                                           stream_ptr()), "uspace_add_broadcast_rows")
     return x
+
+
+def cfg_combine(pair, scale, row_scale=None, out=None):
+    """Classifier-free guidance of paired predictions: ``pair`` [2B, ...] fp32 with the conditional rows first ->
+    out[b] = c + s_b (c - u), s_b = scale * (row_scale[b] if given); fp32 [B, ...]."""
+    require_device(pair, "pair")
+    if pair.dtype != torch.float32 or not pair.is_contiguous() or pair.shape[0] < 2 or pair.shape[0] % 2:
+        raise ValueError(f"pair must be a contiguous fp32 tensor of 2B rows, got {pair.dtype} {tuple(pair.shape)}")
+    B = pair.shape[0] // 2
+    per = pair.numel() // (2 * B)
+    if row_scale is not None and not (row_scale.numel() == B and row_scale.dtype == torch.float32 and row_scale.is_cuda
+                                      and row_scale.is_contiguous()):
+        raise ValueError(f"row_scale must be a contiguous fp32 device tensor of {B} entries")
+    if out is None:
+        out = torch.empty((B,) + tuple(pair.shape[1:]), dtype=torch.float32, device=pair.device)
+    check(lib().uspace_cfg_combine(ptr(pair), ptr(row_scale), float(scale), ptr(out), B, per, stream_ptr()), "uspace_cfg_combine")
+    return out
+
+
+def uvit_forward_cfg(cfg, blob, ws, io, B, uncond, uncond_batched, scale, row_scale=None, pair_out=None):
+    """``uspace_uvit_forward_cfg`` on the current stream: ``io`` (a ``UvitIO``) describes the B samples, ``ws`` is a uint8 tensor of
+    ``uspace_uvit_cfg_workspace_bytes(cfg, B)`` bytes at least; the guided prediction lands in ``io.out``."""
+    check(lib().uspace_uvit_forward_cfg(ctypes.byref(cfg), ptr(blob), ptr(ws), ws.numel(), ctypes.byref(io), B, ptr(uncond),
+                                        1 if uncond_batched else 0, float(scale), ptr(row_scale), ptr(pair_out), stream_ptr()),
+          "uspace_uvit_forward_cfg")
 
 
 def cast_bf16(src):

@@ -146,6 +146,14 @@ int us_output_head_packed(const float* tok, int L, int extras, const float* imag
 // out[n] = sum_k float(bf16(W[n * ld + col0 + k])), k < ncols (rowops.hip; pack-time companion of USPACE_EPI_RANK1)
 int us_rowsum_bf16(const float* W, int ld, int col0, int ncols, float* out, int N, hipStream_t s);
 
+// Pieces of the paired (classifier-free guidance) forward of uvit.hip (rowops.hip; not exported): uspace_embed_tokens over B rows whose
+// extra tokens lie extra_bstride floats apart (0: one copy for all), in the kernel form a launch over plan_B rows takes; one fp32
+// context cast to bf16 into `copies` consecutive samples' rows
+int us_embed_tokens_rows(const float* img, const float* t, int t_stride, const float* extra, int n_extra, long extra_bstride,
+                         int time_first, const float* patch_w, const float* patch_b, const float* pos, float* tok, uint16_t* tok_bf16,
+                         int B, int plan_B, int C, int S, int p, int D, hipStream_t s);
+int us_cast_bcast_f32_bf16(const float* src, uint16_t* dst, long n_src, int copies, hipStream_t s);
+
 // The GEMM with the switch of its K-split tail (uspace_gemm_set_sk) passed in rather than read (gemm.hip; used by uvit.hip, not
 // exported): a forward reads the switch once, so the slot counts its consumers are told and the forms its producers launch agree.
 int us_gemm_bf16_ext(const uint16_t* A, int lda, const uint16_t* A2, int lda2, int K1, const uint16_t* W, int ldw, int M, int N, int K,

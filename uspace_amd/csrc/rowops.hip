@@ -175,10 +175,11 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(bf16_t* __restrict__ x,
 // ------------------------------------------------------------------------------------------
 // Token assembly. grid = B*L blocks; each block writes one token row of D floats.
 // ------------------------------------------------------------------------------------------
-// Time / label / context token l of sample b (the tokens in front of the patch tokens): one block per row.
+// Time / label / context token l of sample b (the tokens in front of the patch tokens): one block per row.  extra_bstride: floats
+// from one sample's extra tokens to the next one's (n_extra * D; 0: every sample reads the same tokens).
 __device__ __forceinline__ void embed_special_row(const float* __restrict__ t, int t_stride, const float* __restrict__ extra, int n_extra,
-                                                  int time_first, const float* __restrict__ pos, float* __restrict__ tok,
-                                                  bf16_t* __restrict__ tok_bf16, int b, int l, int L, int D) {
+                                                  long extra_bstride, int time_first, const float* __restrict__ pos,
+                                                  float* __restrict__ tok, bf16_t* __restrict__ tok_bf16, int b, int l, int L, int D) {
     const int time_pos = time_first ? 0 : n_extra;
     const int extra_pos = time_first ? 1 : 0;
     float* out = tok + ((size_t)b * L + l) * D;
@@ -210,13 +211,13 @@ __device__ __forceinline__ void embed_special_row(const float* __restrict__ t, i
             put4(d, v);
         }
     } else {
-        const float* src = extra + ((size_t)b * n_extra + (l - extra_pos)) * D;
+        const float* src = extra + (size_t)b * extra_bstride + (size_t)(l - extra_pos) * D;
         for (int d = threadIdx.x * 4; d < D; d += blockDim.x * 4) put4(d, *(const f32x4*)(src + d));
     }
 }
 
 __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ img, const float* __restrict__ t, int t_stride,
-                                                    const float* __restrict__ extra, int n_extra, int time_first,
+                                                    const float* __restrict__ extra, int n_extra, long extra_bstride, int time_first,
                                                     const float* __restrict__ pw, const float* __restrict__ pb,
                                                     const float* __restrict__ pos, float* __restrict__ tok,
                                                     bf16_t* __restrict__ tok_bf16, int C, int S, int p, int D,
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ im
         }
     };
     if (l == time_pos || (l >= extra_pos && l < extra_pos + n_extra)) {
-        embed_special_row(t, t_stride, extra, n_extra, time_first, pos, tok, tok_bf16, b, l, L, D);
+        embed_special_row(t, t_stride, extra, n_extra, extra_bstride, time_first, pos, tok, tok_bf16, b, l, L, D);
     } else {
         // PatchEmbed conv k = s = p (libs/uvit.py:171-178): pixels consumed in (c, i, j) order
         __shared__ __attribute__((aligned(16))) float px[64];
@@ -294,14 +295,15 @@ __global__ __launch_bounds__(256) void embed_patch16_kernel(const float* __restr
                                                             float* __restrict__ tok, bf16_t* __restrict__ tok_bf16,
                                                             int C, int S, int p, int D, int L, int first_patch,
                                                             const float* __restrict__ t, int t_stride, const float* __restrict__ extra,
-                                                            int time_first, int B) {
+                                                            long extra_bstride, int time_first, int B) {
     __shared__ __attribute__((aligned(16))) float px[TOK][16];
     const int g = S / p;
     const int npatch = g * g;
     const int chunks = npatch / TOK;
     if ((int)blockIdx.x >= B * chunks) {        // the blocks behind the patch blocks: one special token each (one launch for all rows)
         const int idx = blockIdx.x - B * chunks;
-        embed_special_row(t, t_stride, extra, first_patch - 1, time_first, pos, tok, tok_bf16, idx / first_patch, idx % first_patch, L, D);
+        embed_special_row(t, t_stride, extra, first_patch - 1, extra_bstride, time_first, pos, tok, tok_bf16, idx / first_patch,
+                          idx % first_patch, L, D);
         return;
     }
     const int b = blockIdx.x / chunks;
@@ -698,6 +700,44 @@ __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src
     if (blockIdx.x == 0 && threadIdx.x < (n - rem0)) dst[rem0 + threadIdx.x] = f2bf(src[rem0 + threadIdx.x]);
 }
 
+// dst[i] = bf16(src[i % n_src]), in groups of 4 (n_src % 4 == 0): one context cast into every sample's rows
+__global__ __launch_bounds__(256) void cast_bcast_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long n_src4, long total4) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 v = ((const f32x4*)src)[i % n_src4];
+        uint2 p;
+        p.x = pack_bf2(v[0], v[1]);
+        p.y = pack_bf2(v[2], v[3]);
+        ((uint2*)dst)[i] = p;
+    }
+}
+
+// Classifier-free guidance: out[b, i] = c + s_b (c - u), c = pair[b, i], u = pair[B + b, i], s_b = scale * row_scale[b]
+// (row_scale == NULL: scale) -- one fp32 subtraction and one fused multiply-add.  s_b == 0 hands c on as it is (the fma would
+// turn a -0 into +0).
+__device__ __forceinline__ float cfg_guided(float c, float u, float sb) { return sb == 0.f ? c : __builtin_fmaf(sb, c - u, c); }
+
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ pair, const float* __restrict__ row_scale, float scale,
+                                                          float* __restrict__ out, long per_sample4, long total4) {
+    const f32x4* __restrict__ cond = (const f32x4*)pair;
+    const f32x4* __restrict__ unc = cond + total4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
+        const float sb = row_scale ? scale * row_scale[i / per_sample4] : scale;
+        const f32x4 c = cond[i], u = unc[i];
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = cfg_guided(c[e], u[e], sb);
+        ((f32x4*)out)[i] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void cfg_combine_tail_kernel(const float* __restrict__ pair, const float* __restrict__ row_scale,
+                                                               float scale, float* __restrict__ out, long per_sample, long total) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const float sb = row_scale ? scale * row_scale[i / per_sample] : scale;
+        out[i] = cfg_guided(pair[i], pair[total + i], sb);
+    }
+}
+
 // Attribute-direction statistics (reference: tools/utils_attr.py:124-145, done there in numpy over
 // activations staged through disk): pos[a, f] += sum_n [attr[n,a] == 1] feat[n, f], neg likewise for == 0.
 // One thread owns 4 consecutive features for ALL attributes: the batch column is read once into registers
@@ -872,33 +912,42 @@ extern "C" int uspace_quick_gelu_bf16(uint16_t* x, long n, uspace_stream_t strea
     return USPACE_OK;
 }
 
-extern "C" int uspace_embed_tokens(const float* img, const float* t, int t_stride, const float* extra, int n_extra,
-                                   int time_first, const float* patch_w, const float* patch_b, const float* pos,
-                                   float* tok, uint16_t* tok_bf16, int B, int C, int S, int p, int D,
-                                   uspace_stream_t stream) {
+// uspace_embed_tokens over B rows with the extra tokens extra_bstride floats apart, through the kernel form a launch over plan_B rows
+// takes: the two halves of a paired forward (uvit.hip, uspace_uvit_forward_cfg) are two launches of B rows each and run the kernel a
+// single launch over 2B rows would.
+int us_embed_tokens_rows(const float* img, const float* t, int t_stride, const float* extra, int n_extra, long extra_bstride,
+                         int time_first, const float* patch_w, const float* patch_b, const float* pos, float* tok, uint16_t* tok_bf16,
+                         int B, int plan_B, int C, int S, int p, int D, hipStream_t s) {
     if (!img || !t || !patch_w || !patch_b || !pos || !tok) return USPACE_ERR_ARG;
-    if (B <= 0 || C <= 0 || S <= 0 || p <= 0 || D <= 0 || (D & 3) || S % p || C * p * p > 64 || n_extra < 0) return USPACE_ERR_ARG;
-    if (n_extra > 0 && !extra) return USPACE_ERR_ARG;
+    if (B <= 0 || plan_B < B || C <= 0 || S <= 0 || p <= 0 || D <= 0 || (D & 3) || S % p || C * p * p > 64 || n_extra < 0) return USPACE_ERR_ARG;
+    if (n_extra > 0 && (!extra || extra_bstride < 0)) return USPACE_ERR_ARG;
     const int g = S / p;
     const int L = 1 + n_extra + g * g;
-    hipStream_t s = (hipStream_t)stream;
     constexpr int TOK = 16;
     if (C * p * p == 16 && (g * g) % TOK == 0) {
         // patch tokens by the register-weight kernel; its trailing B * (1 + n_extra) blocks write the time / label / context tokens
         // a block walks its tokens one after the other: few blocks (small batches) take 4 tokens each instead of 16
         const int nsp = B * (1 + n_extra);
-        if (B * (g * g / TOK) < 512 && (g * g) % 4 == 0)
+        if (plan_B * (g * g / TOK) < 512 && (g * g) % 4 == 0)
             hipLaunchKernelGGL(embed_patch16_kernel<4>, dim3(B * (g * g / 4) + nsp), dim3(256), 0, s, img, patch_w, patch_b, pos,
-                               tok, tok_bf16, C, S, p, D, L, 1 + n_extra, t, t_stride, extra, time_first, B);
+                               tok, tok_bf16, C, S, p, D, L, 1 + n_extra, t, t_stride, extra, extra_bstride, time_first, B);
         else
             hipLaunchKernelGGL(embed_patch16_kernel<TOK>, dim3(B * (g * g / TOK) + nsp), dim3(256), 0, s, img, patch_w, patch_b, pos,
-                               tok, tok_bf16, C, S, p, D, L, 1 + n_extra, t, t_stride, extra, time_first, B);
+                               tok, tok_bf16, C, S, p, D, L, 1 + n_extra, t, t_stride, extra, extra_bstride, time_first, B);
     } else {
-        hipLaunchKernelGGL(embed_kernel, dim3(B * L), dim3(256), 0, s, img, t, t_stride, extra, n_extra,
+        hipLaunchKernelGGL(embed_kernel, dim3(B * L), dim3(256), 0, s, img, t, t_stride, extra, n_extra, extra_bstride,
                            time_first, patch_w, patch_b, pos, tok, tok_bf16, C, S, p, D, 0);
     }
     US_CHECK_LAUNCH();
     return USPACE_OK;
+}
+
+extern "C" int uspace_embed_tokens(const float* img, const float* t, int t_stride, const float* extra, int n_extra,
+                                   int time_first, const float* patch_w, const float* patch_b, const float* pos,
+                                   float* tok, uint16_t* tok_bf16, int B, int C, int S, int p, int D,
+                                   uspace_stream_t stream) {
+    return us_embed_tokens_rows(img, t, t_stride, extra, n_extra, (long)n_extra * D, time_first, patch_w, patch_b, pos, tok, tok_bf16,
+                                B, B, C, S, p, D, (hipStream_t)stream);
 }
 
 extern "C" int uspace_output_head(const float* tok, int L, int extras, const float* norm_g, const float* norm_b,
@@ -999,6 +1048,32 @@ extern "C" int uspace_cast_f32_bf16(const float* src, uint16_t* dst, long n, usp
     if (!src || !dst || n <= 0) return USPACE_ERR_ARG;
     if (((uintptr_t)src & 15) || ((uintptr_t)dst & 7)) return USPACE_ERR_ARG;
     hipLaunchKernelGGL(cast_kernel, dim3(grid_for((n >> 2) + 1)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+// dst[b, :] = bf16(src[:]) for b < copies (uvit.hip: an unbatched unconditional context into every sample's rows; not exported)
+int us_cast_bcast_f32_bf16(const float* src, uint16_t* dst, long n_src, int copies, hipStream_t s) {
+    if (!src || !dst || n_src <= 0 || (n_src & 3) || copies <= 0) return USPACE_ERR_ARG;
+    if (((uintptr_t)src & 15) || ((uintptr_t)dst & 7)) return USPACE_ERR_ARG;
+    const long total4 = (n_src >> 2) * copies;
+    hipLaunchKernelGGL(cast_bcast_kernel, dim3(grid_for(total4)), dim3(256), 0, s, src, dst, n_src >> 2, total4);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_cfg_combine(const float* pair, const float* row_scale, float scale, float* out, int B, long per_sample,
+                                  uspace_stream_t stream) {
+    if (!pair || !out || B <= 0 || per_sample <= 0) return USPACE_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)B * per_sample;
+    if ((per_sample & 3) == 0 && !(((uintptr_t)pair | (uintptr_t)out) & 15)) {
+        hipLaunchKernelGGL(cfg_combine_kernel, dim3(grid_for(total >> 2)), dim3(256), 0, s, pair, row_scale, scale, out,
+                           per_sample >> 2, total >> 2);
+    } else {
+        hipLaunchKernelGGL(cfg_combine_tail_kernel, dim3(grid_for(total)), dim3(256), 0, s, pair, row_scale, scale, out, per_sample,
+                           total);
+    }
     US_CHECK_LAUNCH();
     return USPACE_OK;
 }

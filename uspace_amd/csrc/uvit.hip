@@ -225,10 +225,17 @@ int attention(const uint16_t* qkv, const float* ks, uint16_t* out, int B, int L,
 // is the same for every stop_after up to the stop.  maps != NULL (uspace_uvit_forward_maps): one more launch per block, the head-mean
 // attention map of the window mw = {q0, nq, k0, nk} right after the block's qkv GEMM; with maps == NULL the launch sequence is
 // the product forward's.
+// pair != NULL (uspace_uvit_forward_cfg): io describes Bs samples and the forward runs over B = 2 Bs rows -- row b is (x[b], t[b],
+// context[b]), row Bs + b is (x[b], t[b], uncond[b or 0]) -- with the launch sequence of a plain forward at batch 2 Bs, except that the
+// context cast and the token embedding are issued per half, each reading its own rows in place; the head writes pair->pred
+// ([2 Bs, C, S, S]) instead of io->out.
 struct MapWindow { int q0, nq, k0, nk; };
+struct PairArgs { const float* uncond; bool batched; float* pred; };
 int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes, const uspace_uvit_io* io,
-                 int B, int stop_after, float* dump, uspace_stream_t stream, float* maps = nullptr, MapWindow mw = MapWindow{0, 0, 0, 0}) {
-    if (!valid_cfg(cfg) || !blob || !workspace || !io || B <= 0) return USPACE_ERR_ARG;
+                 int Bs, int stop_after, float* dump, uspace_stream_t stream, float* maps = nullptr, MapWindow mw = MapWindow{0, 0, 0, 0},
+                 const PairArgs* pair = nullptr) {
+    if (!valid_cfg(cfg) || !blob || !workspace || !io || Bs <= 0) return USPACE_ERR_ARG;
+    const int B = pair ? 2 * Bs : Bs;
     if (stop_after >= 0 && (!dump || stop_after > cfg->depth + 1)) return USPACE_ERR_ARG;
     if (!io->x || !io->t || !io->out) return USPACE_ERR_ARG;
     if (cfg->n_extra > 0 && !io->context) return USPACE_ERR_ARG;
@@ -292,8 +299,10 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
         if (c.clip_dim > 0) {
             uint16_t* cbf = (uint16_t*)(ws + w.ctx_bf);
             float* cf = (float*)(ws + w.ctx_f32);
-            const long n = (long)B * c.n_extra * c.clip_dim;
+            const long n = (long)Bs * c.n_extra * c.clip_dim;
             US_TRY(uspace_cast_f32_bf16(io->context, cbf, n, stream));
+            if (pair && pair->batched) US_TRY(uspace_cast_f32_bf16(pair->uncond, cbf + n, n, stream));
+            else if (pair) US_TRY(us_cast_bcast_f32_bf16(pair->uncond, cbf + n, (long)c.n_extra * c.clip_dim, Bs, (hipStream_t)stream));
             US_TRY(us_gemm_bf16_ext(cbf, c.clip_dim, nullptr, 0, c.clip_dim, PH(m.cw), c.clip_dim, B * c.n_extra, D,
                                     c.clip_dim, B_ | F_, PF(m.cb), nullptr, 0, cf, D, nullptr, 0, nullptr, sk_on, stream));
             extra = cf;
@@ -301,8 +310,20 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
             extra = io->context;
         }
     }
-    US_TRY(uspace_embed_tokens(io->x, io->t, io->t_stride, extra, c.n_extra, c.time_first, PF(m.pw), PF(m.pb),
-                               PF(m.pos), x, nullptr, B, c.in_chans, c.img_size, c.patch_size, D, stream));
+    if (!pair) {
+        US_TRY(uspace_embed_tokens(io->x, io->t, io->t_stride, extra, c.n_extra, c.time_first, PF(m.pw), PF(m.pb),
+                                   PF(m.pos), x, nullptr, B, c.in_chans, c.img_size, c.patch_size, D, stream));
+    } else {
+        // both halves read the same x and t; the unconditional half takes the second half of the embedded context (clip_dim > 0) or
+        // the caller's unconditional tokens where they lie (one copy: stride 0)
+        const long es = (long)c.n_extra * D;
+        const float* extra_u = c.clip_dim > 0 ? extra + (size_t)Bs * es : pair->uncond;
+        const long es_u = (c.clip_dim > 0 || pair->batched) ? es : 0;
+        for (int half_i = 0; half_i < 2; ++half_i)
+            US_TRY(us_embed_tokens_rows(io->x, io->t, io->t_stride, half_i ? extra_u : extra, c.n_extra, half_i ? es_u : es, c.time_first,
+                                        PF(m.pw), PF(m.pb), PF(m.pos), x + (size_t)half_i * Bs * L * D, nullptr, Bs, B, c.in_chans,
+                                        c.img_size, c.patch_size, D, (hipStream_t)stream));
+    }
     auto tap = [&]() {
         return hipMemcpyAsync(dump, x, MD * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? USPACE_OK : USPACE_ERR_LAUNCH;
     };
@@ -429,12 +450,13 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
         if (i + 1 == stop_after && !is_last) return tap();
     }
     }
+    float* const pred = pair ? pair->pred : io->out;
     if (m.head_img >= 0)     // decoder weights with the last LayerNorm folded in, prepared by uspace_uvit_pack_weights
-        US_TRY(us_output_head_packed(x, L, m.extras, PF(m.head_img), PF(m.convw), PF(m.convb), (float*)(ws + w.head), io->out, B,
+        US_TRY(us_output_head_packed(x, L, m.extras, PF(m.head_img), PF(m.convw), PF(m.convb), (float*)(ws + w.head), pred, B,
                                      c.in_chans, c.img_size, c.patch_size, D, 1e-5f, (hipStream_t)stream));
     else
         US_TRY(uspace_output_head(x, L, m.extras, PF(m.ng), PF(m.nb), PF(m.dw), PF(m.db), PF(m.convw), PF(m.convb),
-                                  (float*)(ws + w.head), io->out, B, c.in_chans, c.img_size, c.patch_size, D, 1e-5f, stream));
+                                  (float*)(ws + w.head), pred, B, c.in_chans, c.img_size, c.patch_size, D, 1e-5f, stream));
     if (stop_after == m.nblocks) return tap();
     return USPACE_OK;
 }
@@ -456,6 +478,37 @@ extern "C" int uspace_uvit_forward_maps(const uspace_uvit_config* cfg, const voi
                                         uspace_stream_t stream) {
     if (!maps) return USPACE_ERR_ARG;
     return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, -1, nullptr, stream, maps, MapWindow{q0, nq, k0, nk});
+}
+
+// ------------------------------------------------------------------------------------------
+// Classifier-free guidance: conditional and unconditional branch of every sample in ONE forward over 2B rows, combined on the device.
+// Workspace = that of a plain forward at batch 2B, then the 2B predictions.
+// ------------------------------------------------------------------------------------------
+namespace {
+inline size_t pair_pred_bytes(const uspace_uvit_config& c, int B) {
+    return ((size_t)2 * B * c.in_chans * c.img_size * c.img_size * 4 + 255) & ~(size_t)255;
+}
+constexpr int kMaxPairB = 1 << 29;
+}  // namespace
+
+extern "C" size_t uspace_uvit_cfg_workspace_bytes(const uspace_uvit_config* cfg, int B) {
+    if (!valid_cfg(cfg) || B <= 0 || B > kMaxPairB) return 0;
+    const size_t base = uspace_uvit_workspace_bytes(cfg, 2 * B);
+    return base ? base + pair_pred_bytes(*cfg, B) : 0;
+}
+
+extern "C" int uspace_uvit_forward_cfg(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                       const uspace_uvit_io* io, int B, const float* uncond, int uncond_batched, float scale,
+                                       const float* row_scale, float* pair_out, uspace_stream_t stream) {
+    if (!valid_cfg(cfg) || !blob || !workspace || !io || B <= 0 || B > kMaxPairB) return USPACE_ERR_ARG;
+    if (cfg->n_extra == 0 || !uncond) return USPACE_ERR_ARG;          // nothing to drop
+    if (!io->x || !io->t || !io->out || !io->context || io->mid_tap) return USPACE_ERR_ARG;
+    const size_t base = uspace_uvit_workspace_bytes(cfg, 2 * B);
+    if (!base || workspace_bytes < base + pair_pred_bytes(*cfg, B)) return USPACE_ERR_WORKSPACE;
+    float* pred = pair_out ? pair_out : (float*)((char*)workspace + base);
+    const PairArgs pair{uncond, uncond_batched != 0, pred};
+    US_TRY(forward_impl(cfg, blob, workspace, base, io, B, -1, nullptr, stream, nullptr, MapWindow{0, 0, 0, 0}, &pair));
+    return uspace_cfg_combine(pred, row_scale, scale, io->out, B, (long)cfg->in_chans * cfg->img_size * cfg->img_size, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -4,6 +4,10 @@
 ``encode`` (data -> noise, t: 1 -> 0), ``decode_fixadp`` (fixed steps up to t_edit, adaptive after)
 -- over this package's own integrators (uspace_amd/odeint.py), because the reference's solver is
 the external torchdiffeq.  ``sample_ode`` (the name BASELINE.json uses) aliases ``decode``.
+
+Every keyword reaches the network at each evaluation, classifier-free guidance among them:
+``decode(z, y, cfg_scale=s)`` (optionally ``empty_label=K``) integrates v_c + s (v_c - v_u), with
+``cfg_scale`` a number or B per-sample values (libs/uvit.py of this package).
 """
 import torch
 import torch.nn as nn

@@ -3,6 +3,10 @@
 Differences from the unconditional driver, as in the reference: the condition is passed by
 keyword (``context=``), ``fm_direction`` is recorded in the kwargs ("encode" / "decode") for the
 attention-map edit, and ``encode`` follows ``get_ode_kwargs`` instead of forcing the fixed solver.
+
+Classifier-free guidance: ``decode(z, context=ctx, cfg_scale=config.sample.scale,
+empty_context=dataset.empty_context, ...)`` -- the keywords reach the network at each evaluation
+(libs/uvit_t2i.py of this package), which runs both branches of every sample in one forward.
 """
 from .flow_matching import CNFBase, Stats
 

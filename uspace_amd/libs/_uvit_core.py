@@ -74,6 +74,10 @@ class UViTBase(nn.Module):
         # B x n_scales solve with plain B solves (tools/utils_vis.py:189-198), and one slot would reallocate hundreds of MB at
         # every switch.
         self._workspace = WorkspaceCache(2)
+        # Guided (classifier-free guidance) evaluations run at 2B rows in a workspace of their own, so that guided and plain evaluations
+        # of the same B do not evict each other; empty until the first guided call.
+        self._cfg_workspace = WorkspaceCache(1)
+        self._cfg_rows = None        # (key, device tensor): the per-sample guidance scales of a sweep, uploaded once
         self._delta_cache = {}
         # Replay a captured hipGraph for plain (un-hooked) evaluations.  Off by default since round 3: one C call enqueues a whole
         # evaluation and the kernels take longer to run than to launch at every batch size, so the replay only adds its three small
@@ -248,13 +252,21 @@ class UViTBase(nn.Module):
 
     # ------------------------------------------------------------------ the single HIP call
     def _run(self, x, timesteps, context=None, mid_delta=None, mid_scale=0.0, mid_tap=None, key_scale=None,
-             mid_row_scale=None, keep_f32=False, attn_maps=None):
+             mid_row_scale=None, keep_f32=False, attn_maps=None, cfg=None):
         """``keep_f32``: return the fp32 result even for a half-precision ``x`` (the caller still has fp32 work to do).
         ``attn_maps``: a ``(q0, nq, k0, nk)`` token window; the call then goes through ``uspace_uvit_forward_maps`` and returns
         ``(out, maps)`` with maps [depth + 1, B, nq, nk] fp32, the head-mean attention map of every block (before any ``key_scale``
         edit of that block).  A maps evaluation always runs eagerly, never through the captured hipGraph: the graph holds the plain
-        launch sequence and its own static buffers, which a maps evaluation neither replays nor touches."""
+        launch sequence and its own static buffers, which a maps evaluation neither replays nor touches.
+        ``cfg``: ``(uncond, batched, scale, row_scales, want_pair)`` -- classifier-free guidance through ``uspace_uvit_forward_cfg``:
+        one evaluation over 2B rows (row b with ``context[b]``, row B + b with ``uncond`` -- the unconditional context in the form of
+        ``context``, one copy or, with ``batched``, B of them) combined on the device as c + s_b (c - u), s_b = ``scale`` *
+        ``row_scales[b]`` (a device fp32 [B] or None).  ``key_scale`` is then [depth + 1, 2B, L] and ``mid_row_scale`` [2B]; ``mid_tap``
+        and ``attn_maps`` are not available.  ``want_pair``: return ``(out, pair)`` with the 2B fp32 predictions, conditional rows
+        first.  Always eager, like a maps evaluation, and in a workspace of its own."""
         _hip.require_device(x, "x")
+        if cfg is not None and (attn_maps is not None or mid_tap is not None):
+            raise ValueError("a guided evaluation has neither attention maps nor a mid tap")
         if x.dim() != 4 or x.shape[1] != self.in_chans or x.shape[2] != self.img_size or x.shape[3] != self.img_size:
             raise ValueError(f"x must be [B,{self.in_chans},{self.img_size},{self.img_size}], got {tuple(x.shape)}")
         B = x.shape[0]
@@ -268,6 +280,8 @@ class UViTBase(nn.Module):
                                 dtype=torch.float32 if keep_f32 else x.dtype, device=dev)
             if attn_maps is not None:
                 return empty, torch.empty(self.depth + 1, 0, nq, nk, dtype=torch.float32, device=dev)
+            if cfg is not None and cfg[4]:
+                return empty, torch.empty(0, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev)
             return empty
         xin = x.detach().to(torch.float32).contiguous()
         t = timesteps
@@ -283,10 +297,19 @@ class UViTBase(nn.Module):
             if t_stride not in (0, 1):
                 t = t.contiguous(); t_stride = 1
         plain = mid_delta is None and mid_tap is None and key_scale is None
-        if self.use_graph and plain and t_stride == 0 and attn_maps is None:
+        if self.use_graph and plain and t_stride == 0 and attn_maps is None and cfg is None:
             return self._run_graph(xin, t, context, B, dev, torch.float32 if keep_f32 else x.dtype)
         out = torch.empty(B, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev)
         blob = self._packed_blob(dev)
+        if cfg is not None:
+            uncond, batched, scale, row_scales, want_pair = cfg
+            ws = self._cfg_workspace.take(B, dev, _hip.lib().uspace_uvit_cfg_workspace_bytes(ctypes.byref(self._cfg), B))
+            io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta), float(mid_scale), None,
+                             _hip.ptr(key_scale), _hip.ptr(out), _hip.ptr(mid_row_scale))
+            pair = torch.empty(2 * B, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev) if want_pair else None
+            _hip.uvit_forward_cfg(self._cfg, blob, ws, io, B, uncond, batched, scale, row_scale=row_scales, pair_out=pair)
+            out = out if (keep_f32 or x.dtype == torch.float32) else out.to(x.dtype)
+            return (out, pair) if want_pair else out
         ws = self._workspace_for(B, dev)
         io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta),
                          float(mid_scale), _hip.ptr(mid_tap), _hip.ptr(key_scale), _hip.ptr(out),
@@ -300,6 +323,17 @@ class UViTBase(nn.Module):
         _hip.check(_hip.lib().uspace_uvit_forward(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
                                                   ctypes.byref(io), B, _hip.stream_ptr()), "uspace_uvit_forward")
         return out if (keep_f32 or x.dtype == torch.float32) else out.to(x.dtype)
+
+    def _guidance_rows(self, rows, dev):
+        """The per-sample guidance scales of ``guidance_scales`` on the device (a host array is uploaded once per distinct sweep)."""
+        if rows is None:
+            return None
+        if torch.is_tensor(rows):
+            return rows.detach().to(device=dev, dtype=torch.float32).contiguous()
+        key = (rows.tobytes(), str(dev))
+        if self._cfg_rows is None or self._cfg_rows[0] != key:
+            self._cfg_rows = (key, torch.from_numpy(rows).to(dev))
+        return self._cfg_rows[1]
 
     def _tap(self, stage, x, timesteps, context=None, mid_delta=None, mid_scale=0.0, mid_tap=None, key_scale=None,
              mid_row_scale=None, out=None, workspace=None):
@@ -343,6 +377,29 @@ class _GraphEntry:
             self.destroy()
         except Exception:
             pass
+
+
+def guidance_scales(cfg_scale, B):
+    """``cfg_scale`` of ``forward`` -> ``(scale, rows)``: a number gives ``(s, None)``; B per-sample values (list, ndarray or tensor: a
+    guidance sweep in one solve) give ``(1.0, rows)`` with rows a float32 ndarray or the tensor itself.  U-ViT's convention, the
+    configs' ``sample.scale``: v = v_c + s (v_c - v_u), s = 0 the conditional prediction."""
+    import numpy as np
+    if torch.is_tensor(cfg_scale):
+        if cfg_scale.dim() == 0:
+            return float(cfg_scale), None
+        rows = cfg_scale.reshape(-1)
+        n = rows.numel()
+    elif isinstance(cfg_scale, (list, tuple, np.ndarray)) and np.ndim(cfg_scale) > 0:
+        rows = np.ascontiguousarray(np.asarray(cfg_scale, dtype=np.float32).reshape(-1))
+        n = rows.size
+    else:
+        try:
+            return float(cfg_scale), None
+        except (TypeError, ValueError):
+            raise ValueError(f"cfg_scale must be a number or {B} per-sample values, got {type(cfg_scale).__name__}") from None
+    if n != B:
+        raise ValueError(f"cfg_scale has {n} entries for a batch of {B}")
+    return 1.0, rows
 
 
 def host_timestep(timesteps, kwargs):

@@ -5,13 +5,20 @@
 Same constructor keywords (dummies accepted), same state_dict keys, same kwargs contract
 (``edit_loc`` + the u-space hook keys).  The velocity field is computed by one call into
 libuspace_hip.so; the u-space hook's add runs on the GPU as well.
+
+Classifier-free guidance of a class-conditional network: ``cfg_scale=s`` (a number, or B per-sample
+values) gives v_c + s (v_c - v_u) with the unconditional branch fed ``label_emb.weight[empty_label]``
+(``empty_label`` defaults to num_classes - 1, the label the reference's CFGDataset reserves), both
+branches in one evaluation over 2B rows.  Hooks under guidance: a ``head`` write edits x before it is
+paired, a ``mid`` write reaches both branches, ``tail`` reads and writes the guided result; a ``mid``
+read has two candidates to save and raises ValueError.
 """
 import torch
 import torch.nn as nn
 
 from .. import _hip
 from . import dissection
-from ._uvit_core import ParamGroup, UViTBase, host_timestep, timestep_digit
+from ._uvit_core import ParamGroup, UViTBase, guidance_scales, host_timestep, timestep_digit
 
 
 class UViT(UViTBase):
@@ -53,8 +60,19 @@ class UViT(UViTBase):
         if edit_loc in ("head", "mid", "tail"):
             digit = timestep_digit(host_timestep(timesteps, kwargs))
             plan = dissection.plan_uspace_hook(digit, kwargs)
-        _hip.require_device(x, "x")
         B = x.shape[0]
+        guide = None
+        if kwargs.get("cfg_scale") is not None:
+            if self.num_classes <= 0:
+                raise ValueError("cfg_scale given but the model has no label embedding (num_classes <= 0): there is no condition to drop")
+            empty_label = kwargs.get("empty_label")
+            empty_label = self.num_classes - 1 if empty_label is None else int(empty_label)
+            if not 0 <= empty_label < self.num_classes:
+                raise ValueError(f"empty_label {empty_label} is not one of the {self.num_classes} labels")
+            if plan is not None and edit_loc == "mid" and plan.kind == "read":
+                raise ValueError("a mid read hook under cfg_scale is ambiguous (conditional or unconditional branch?): read in an unguided solve")
+            guide = guidance_scales(kwargs["cfg_scale"], B) + (empty_label,)
+        _hip.require_device(x, "x")
         dev = x.device
         label_tok = None
         if y is not None:
@@ -84,8 +102,15 @@ class UViT(UViTBase):
                 mid_delta = self._deltas().get(plan.path, plan.ith, dev, self.seq_len * self.embed_dim)
                 mid_scale = plan.scale
         tail_write = plan is not None and edit_loc == "tail" and plan.kind == "write"
-        out = self._run(x, timesteps, context=label_tok, mid_delta=mid_delta, mid_scale=mid_scale, mid_tap=mid_tap,
-                        mid_row_scale=rows if mid_delta is not None else None, keep_f32=tail_write)
+        if guide is not None:
+            scale, srows, empty_label = guide
+            uncond = self.label_emb.weight.detach()[empty_label].to(torch.float32).contiguous()
+            mid_rows = torch.cat([rows, rows]) if (mid_delta is not None and rows is not None) else None    # both branches of a sample
+            out = self._run(x, timesteps, context=label_tok, mid_delta=mid_delta, mid_scale=mid_scale, mid_row_scale=mid_rows,
+                            keep_f32=tail_write, cfg=(uncond, False, scale, self._guidance_rows(srows, dev), False))
+        else:
+            out = self._run(x, timesteps, context=label_tok, mid_delta=mid_delta, mid_scale=mid_scale, mid_tap=mid_tap,
+                            mid_row_scale=rows if mid_delta is not None else None, keep_f32=tail_write)
         if mid_tap is not None:
             dissection.save_activation(plan.path, mid_tap, kwargs)
         if plan is not None and edit_loc == "tail":

@@ -3,6 +3,8 @@
     nnet(x, timesteps, context=ctx, **kwargs) -> (pred, None)
 
 77 CLIP context tokens are embedded by the HIP GEMM and prepended after the time token.
+Classifier-free guidance (``cfg_scale=s, empty_context=...``: v_c + s (v_c - v_u), the configs'
+``sample.scale``) runs both branches of every sample in one evaluation over 2B rows.
 The prompt-to-prompt attention-map edit (dissect_name in {p2p, local_prompt,
 sampled_image_editing}) is applied inside the fused attention kernel as a per-key factor.
 The map itself -- the reference's ``vis_am_path`` pictures (tools/utils_t2i.py:141-193) and
@@ -15,7 +17,7 @@ import torch.nn as nn
 
 from .. import _hip
 from ..tools import utils_t2i
-from ._uvit_core import ParamGroup, UViTBase, host_timestep, timestep_digit
+from ._uvit_core import ParamGroup, UViTBase, guidance_scales, host_timestep, timestep_digit
 
 
 class UViT(UViTBase):
@@ -48,9 +50,11 @@ class UViT(UViTBase):
     def _extra_canonical(self):
         return [self.context_embed.weight, self.context_embed.bias]
 
-    def _prepare(self, x, timesteps, context, kwargs):
+    def _prepare(self, x, timesteps, context, kwargs, paired=False):
         """What ``forward`` and ``attention_maps`` share: the checked fp32 context, this step's key_scale table (or None) and the
-        timestep digit (None off the attention-edit path).  One place, so that a map always sees the edit ``forward`` applies."""
+        timestep digit (None off the attention-edit path).  One place, so that a map always sees the edit ``forward`` applies.
+        ``paired``: the table of a guided evaluation, [depth + 1, 2B, L] -- the edit on the conditional rows, ones on the
+        unconditional ones (as in prompt-to-prompt, the edit acts on the conditional branch only)."""
         _hip.require_device(x, "x")
         B = x.shape[0]
         dev = x.device
@@ -63,13 +67,40 @@ class UViT(UViTBase):
             digit = timestep_digit(host_timestep(timesteps, kwargs))
             table = utils_t2i.key_scale_table(self.depth + 1, B, self.seq_len, digit, kwargs)
             if table is not None:
+                if paired:
+                    table = np.concatenate([table, np.ones_like(table)], axis=1)
                 key_scale = self._device_table(table, dev)
         return ctx, key_scale, digit
 
+    def _guidance(self, B, cfg_scale, empty_context):
+        """The checked guidance arguments of ``forward``: (scale, per-sample scales or None, empty context, batched flag).  Host work
+        only."""
+        scale, rows = guidance_scales(cfg_scale, B)
+        if empty_context is None:
+            raise ValueError("cfg_scale needs empty_context: the context of the empty prompt (the feature datasets' empty_context.npy)")
+        empty = torch.as_tensor(empty_context)
+        want = (self.num_clip_token, self.clip_dim)
+        if tuple(empty.shape) != want and tuple(empty.shape) != (B,) + want:
+            raise ValueError(f"empty_context must be {list(want)} or {[B] + list(want)}, got {list(empty.shape)}")
+        return scale, rows, empty, empty.dim() == 3
+
     def forward(self, x, timesteps, context, **kwargs):
-        ctx, key_scale, digit = self._prepare(x, timesteps, context, kwargs)
+        """kwargs: the reference's, and ``cfg_scale`` (None: no guidance; a number; or B per-sample values -- a guidance sweep in one
+        solve) with ``empty_context`` ([77, clip_dim] or [B, 77, clip_dim])."""
+        guide = None
+        if kwargs.get("cfg_scale") is not None:
+            guide = self._guidance(x.shape[0], kwargs["cfg_scale"], kwargs.get("empty_context"))
+        ctx, key_scale, digit = self._prepare(x, timesteps, context, kwargs, paired=guide is not None)
         # tools/utils_t2i.py:279-283: on the edit path the decode direction shows the map (before the edit) when vis_am_path is set
-        if not (digit in utils_t2i.VIS_DIGITS and kwargs.get("fm_direction") == "decode" and kwargs.get("vis_am_path") is not None):
+        vis = digit in utils_t2i.VIS_DIGITS and kwargs.get("fm_direction") == "decode" and kwargs.get("vis_am_path") is not None
+        if guide is not None:
+            if vis:
+                raise ValueError("vis_am_path pictures under cfg_scale are not supported: draw the maps in an unguided solve")
+            scale, rows, empty, batched = guide
+            empty = empty.detach().to(device=x.device, dtype=torch.float32).contiguous()
+            cfg = (empty, batched, scale, self._guidance_rows(rows, x.device), False)
+            return self._run(x, timesteps, context=ctx, key_scale=key_scale, cfg=cfg), None
+        if not vis:
             return self._run(x, timesteps, context=ctx, key_scale=key_scale), None
         window = self.token_range("image") + self.token_range("context")
         out, maps = self._run(x, timesteps, context=ctx, key_scale=key_scale, attn_maps=window)
@@ -88,7 +119,10 @@ class UViT(UViTBase):
         ``"time"``, ``"all"`` or an explicit ``(first, count)``.  The softmax runs over all L keys.  ``kwargs`` are those of
         ``forward``: a live p2p edit acts on the prediction and on the later blocks, the map of a block is always the one before its
         edit.  With ``queries="image", keys="image"`` this is the input of the reference's tools/attention_vis.py:54
-        show_self_attention_comp.  Nothing is written, whatever ``vis_am_path`` says."""
+        show_self_attention_comp.  Nothing is written, whatever ``vis_am_path`` says.  Maps under guidance (``cfg_scale``) are not
+        available: ValueError."""
+        if kwargs.get("cfg_scale") is not None:
+            raise ValueError("attention_maps under cfg_scale is not supported: the maps of a guided evaluation are out of scope")
         ctx, key_scale, _ = self._prepare(x, timesteps, context, kwargs)
         window = self.token_range(queries) + self.token_range(keys)
         return self._run(x, timesteps, context=ctx, key_scale=key_scale, attn_maps=window)[1]
