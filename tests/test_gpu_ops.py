@@ -578,14 +578,20 @@ def test_gemm_tile_configurations_at_full_row_counts(hip, M, N, K, expect):
     (2 * 257, 512, 4096, False),   # 20 tiles: K split in 8
 ])
 def test_gemm_small_launches_k_split(hip, M, N, K, two_slabs):
-    """Small launches (128x128 tiles on a fraction of the CUs) given a workspace split a long K over gridDim.y; a second
-    kernel adds the partial sums in split order and applies the epilogue (bias + residual in place + bf16 copy: proj / fc2 /
-    skip_linear, libs/uvit.py:159-161).  Against the oracle, against the unsplit launch, and repeatedly over the same
-    workspace (bit-identical results)."""
+    """Small launches with a long K.  Non-producers run as 64x64 tiles whatever workspace they are given (`refine_small`): bias +
+    residual in place + bf16 copy (proj / fc2 / skip_linear, libs/uvit.py:159-161) against the oracle, with and without a split
+    workspace, which must stay untouched.  Producers of LayerNorm partial sums with N > 512 keep 128x128 tiles and, given a workspace,
+    split a long K over gridDim.y; a second kernel adds the partial sums in split order and applies the epilogue: against the oracle,
+    against the unsplit launch, and repeatedly over the same NaN-poisoned workspace (bit-identical results), the workspace itself
+    being the witness that the split ran."""
     import ctypes
     lib = hip.lib()
     split = ctypes.c_int(0)
-    assert lib.uspace_gemm_tile_choice(M, N, ctypes.byref(split)) == 2
+    assert lib.uspace_gemm_tile_choice(M, N, ctypes.byref(split)) == 2          # the base plan ...
+    plan, pplan = (ctypes.c_int * 8)(), (ctypes.c_int * 8)()
+    assert lib.uspace_gemm_plan_k(M, N, K, 0, plan) == 0 and lib.uspace_gemm_plan_k(M, N, K, 1, pplan) == 0
+    assert plan[0] == 5 and plan[7] == 512                                      # ... and what is launched: 64x64 tiles, ring form
+    assert pplan[0] == (2 if N > 512 else 5), list(pplan)                       # a producer keeps 128x128 tiles beyond 8 slots of 64
     rng = np.random.default_rng(M + N + K)
     K1 = K // 2 if two_slabs else K
     A = bf16_round(_rand(rng, M, K))
@@ -612,6 +618,7 @@ def test_gemm_small_launches_k_split(hip, M, N, K, two_slabs):
             runs.append(x.clone())
         if ws_bytes:
             assert all(torch.equal(runs[0], r) for r in runs[1:])
+            assert bool(torch.isnan(ws).all())                                  # the 64x64 form has no use for it
         got = x.cpu().numpy()
         np.testing.assert_allclose(got, ref, rtol=1e-3, atol=1e-3 * np.abs(ref).max())
         assert rel_l2(got, ref) < 1e-5
@@ -623,6 +630,62 @@ def test_gemm_small_launches_k_split(hip, M, N, K, two_slabs):
         x = dR.clone()
         hip.gemm(dA, dW, A2=dA2, bias=db, resid=x, out_f32=x, split_ws=torch.zeros(need // 4 - 64, device="cuda"))
         assert np.array_equal(x.cpu().numpy(), outs[0])
+
+    # ---- the same launch as a producer (proj / fc2 / skip_linear feeding a norm): the one role that still takes the K split
+    S = need // (4 * M * N)
+    splits = pplan[0] == 2 and need > 0
+    assert splits == (N > 512 and K >= 2048) and (not splits or S == 2)
+    slots = lib.uspace_gemm_part_slots_k(M, N, K)
+    assert slots == pplan[5]
+    c = R.mean(axis=1).astype(np.float32)
+    dc = to_dev(c)
+    other_A = to_dev(bf16_round(_rand(rng, M, K1)), torch.bfloat16)
+    flags = hip.EPI_BIAS | hip.EPI_RESIDUAL | hip.EPI_OUT_F32 | hip.EPI_OUT_BF16 | hip.EPI_CEN_OUT
+
+    def producer(a, ws, ws_bytes):
+        x = dR.clone()
+        xb = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
+        xc = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
+        part = torch.full((M, slots, 2), float("nan"), device="cuda")
+        ext = hip.GemmExt(hip.ptr(dc).value, hip.ptr(xc).value, N, hip.ptr(part).value, None, 0, None, None, N, 1e-5)
+        if ws is not None:
+            ext.split_ws, ext.split_ws_bytes = hip.ptr(ws).value, ws_bytes
+        rc = lib.uspace_gemm_bf16_ext(hip.ptr(a), K1, hip.ptr(dA2), K1 if two_slabs else 0, K1, hip.ptr(dW), K, M, N, K, flags, hip.ptr(db),
+                                      hip.ptr(x), N, hip.ptr(x), N, hip.ptr(xb), N, ctypes.byref(ext), hip.stream_ptr())
+        assert rc == 0
+        return x, xb, xc, part
+
+    def verify(x, xb, xc, part, finish):
+        got = x.cpu().numpy()
+        np.testing.assert_allclose(got, ref, rtol=1e-3, atol=1e-3 * np.abs(ref).max())
+        assert rel_l2(got, ref) < 1e-5
+        assert torch.equal(xb, x.to(torch.bfloat16)) and torch.equal(xc, (x - dc[:, None]).to(torch.bfloat16))
+        pg = part.cpu().numpy().astype(np.float64)
+        assert np.isfinite(pg).all()
+        cen = got.astype(np.float64) - c[:, None]
+        np.testing.assert_allclose(pg[:, :, 0].sum(1), cen.sum(1), rtol=1e-4, atol=2e-2)
+        np.testing.assert_allclose(pg[:, :, 1].sum(1), (cen ** 2).sum(1), rtol=1e-4)
+        if finish:                     # the finish kernel: the row's sums in slot 0, zeros behind
+            assert not pg[:, 1:].any()
+        return got
+
+    p0 = producer(dA, None, 0)
+    got0 = verify(*p0, False)
+    if not splits:
+        return
+    ws = torch.full((need // 4,), float("nan"), device="cuda")
+    runs = []
+    for _ in range(3):
+        runs.append(producer(dA, ws, need))
+        assert not bool(torch.isnan(ws).any())                                  # the witness: every partial sum went through it
+        producer(other_A, ws, need)                                             # the same workspace with other operands in between
+    assert all(torch.equal(a, b_) for r in runs[1:] for a, b_ in zip(runs[0], r))
+    got1 = verify(*runs[0], True)
+    assert rel_l2(got1, got0) < 1e-6
+    # a workspace that is too small is ignored (unsplit launch), not an error: bit-equal to the launch without one, nothing written
+    small = torch.full((need // 4 - 64,), float("nan"), device="cuda")
+    ps = producer(dA, small, need - 256)
+    assert all(torch.equal(a, b_) for a, b_ in zip(p0, ps)) and bool(torch.isnan(small).all())
 
 
 @pytest.mark.parametrize("M,D,Kp,N2", [
