@@ -528,6 +528,68 @@ USPACE_API int uspace_table_embed(const int* ids, const float* tok_table, const 
 /* x <- x * sigmoid(1.702 x) in place, bf16 (HF QuickGELUActivation); n % 4 == 0 */
 USPACE_API int uspace_quick_gelu_bf16(uint16_t* x, long n, uspace_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CLIP score: the image side of CLIP (Hugging Face CLIPVisionModelWithProjection: patch embedding, class token + position
+ * table, pre_layrnorm, pre-LN blocks with NON-causal attention and a quick-GELU MLP, post_layernorm of the class token,
+ * visual_projection), the image preprocessing in front of it and the fp32 pieces of the metric.  Added under ABI 11: new
+ * symbols only.
+ * ---------------------------------------------------------------------------------------------- */
+/* (declared struct-then-typedef: the generated ctypes stub of INTEGRATION.md lists the `typedef struct {` configs of the
+ * sampling path; the binding of this one is uspace_amd/_hip.py ClipVisionConfig) */
+struct uspace_clipv_config {
+    int image;     /* 224: side of pixel_values; image % patch == 0 */
+    int patch;     /* 14 */
+    int dim;       /* 1024 = heads * 64 */
+    int heads;     /* 16 */
+    int layers;    /* 24 */
+    int ffn;       /* 4096; % 64 == 0 */
+    int proj_dim;  /* 768; % 4 == 0 */
+    float eps;     /* 1e-5 */
+};
+typedef struct uspace_clipv_config uspace_clipv_config;
+
+/* parameter tensors in the HF state_dict order: embeddings.class_embedding [dim], embeddings.patch_embedding.weight
+ * [dim, 3, patch, patch] (no bias), embeddings.position_embedding.weight [(image / patch)^2 + 1, dim], pre_layrnorm.{weight,bias}
+ * (HF's spelling), per layer self_attn.{k,v,q,out}_proj.{weight,bias}, layer_norm1.*, mlp.fc1.*, mlp.fc2.*, layer_norm2.*, then
+ * post_layernorm.{weight,bias} and visual_projection.weight [proj_dim, dim].  The patch weight is stored bf16 as [dim, Kp],
+ * Kp = 3 patch^2 rounded up to 64 with zero columns (the GEMM's K % 64 == 0; ViT-L/14: 588 -> 640); visual_projection stays fp32.
+ * An invalid config gives USPACE_ERR_ARG / 0 bytes. */
+USPACE_API int uspace_clipv_num_params(const uspace_clipv_config* cfg);
+USPACE_API long uspace_clipv_param_numel(const uspace_clipv_config* cfg, int index);
+USPACE_API size_t uspace_clipv_weight_bytes(const uspace_clipv_config* cfg);
+USPACE_API size_t uspace_clipv_workspace_bytes(const uspace_clipv_config* cfg, int B);
+USPACE_API int uspace_clipv_pack_weights(const uspace_clipv_config* cfg, const float* const* params, int n_params, void* blob,
+                                         size_t blob_bytes, uspace_stream_t stream);
+/* pixel_values: fp32 [B, 3, image, image] (uspace_clip_preprocess's output) -> image_embeds fp32 [B, proj_dim] and, where
+ * pooler_output != NULL, post_layernorm(class token) fp32 [B, dim].  Patch rows in (c, py, px) order as bf16 -> uspace_gemm_bf16;
+ * the attention is uspace_attention_bf16 where uspace_attention_plan accepts the token count, uspace_attention_long_bf16 beyond.
+ * stop_after_layer = -1: the whole model.  Test aid, written to tap_out fp32 [B, tokens, dim] instead (image_embeds may be
+ * NULL): k >= 0 the hidden state after k layers (k = 0: after pre_layrnorm; HF hidden_states[k]), -2 the embeddings before
+ * pre_layrnorm. */
+USPACE_API int uspace_clipv_forward(const uspace_clipv_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                    const float* pixel_values, float* image_embeds, float* pooler_output, int B, int stop_after_layer,
+                                    float* tap_out, uspace_stream_t stream);
+
+/* images fp32 [B, 3, H, W] in [0, 1] (H == W; anything else: USPACE_ERR_ARG) -> pixel_values fp32 [B, 3, S, S]:
+ *   v = 255 x, with quantize != 0 v = clamp(floor(255 x + 0.5), 0, 255), each step rounded to fp32
+ *   (save_image's rounding, ties included);
+ *   separable antialiased bicubic resize to S: Keys filter a = -0.5 of support 2 max(H / S, 1) around the centre (o + 0.5) H / S,
+ *   the window clipped to the image and its weights renormalised per output pixel (torch interpolate(mode="bicubic",
+ *   antialias=True, align_corners=False)); the result is NOT rounded back to uint8;
+ *   out = (clamp(v, 0, 255) / 255 - mean[c]) / std[c].   mean, std: HOST float[3].  H <= 4096, H / S <= 63. */
+USPACE_API int uspace_clip_preprocess(const float* images, float* pixel_values, int B, int H, int W, int S, int quantize,
+                                      const float* mean, const float* std, uspace_stream_t stream);
+/* out[B, N] = x[B, K] . w[N, K]^T in fp32 (weights, products and sums), no bias: the two CLIP projections.  K % 4 == 0. */
+USPACE_API int uspace_linear_f32(const float* x, const float* w, float* out, int B, int N, int K, uspace_stream_t stream);
+/* out[b, :] = x[b, idx[b], :] of x fp32 [B, L, D]; idx: device int32 [B] in [0, L) (the text pooling position) */
+USPACE_API int uspace_gather_rows_f32(const float* x, const int* idx, float* out, int B, int L, int D, uspace_stream_t stream);
+/* out[b] = scale <a_b, b_b> / (|a_b| |b_b|), with relu != 0 max(., 0); a, b fp32 [B, D].  One wave per row, fixed summation
+ * order, no atomics.  A zero row gives NaN, as the division does. */
+USPACE_API int uspace_cosine_f32(const float* a, const float* b, float* out, int B, int D, float scale, int relu,
+                                 uspace_stream_t stream);
+/* out[b, :] = a_b / |a_b| - b_b / |b_b|: the step between two embeddings on the unit sphere (directional similarity) */
+USPACE_API int uspace_normalized_diff_f32(const float* a, const float* b, float* out, int B, int D, uspace_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for

@@ -50,6 +50,11 @@ class ClipConfig(ctypes.Structure):
                 ("ffn", ctypes.c_int), ("max_pos", ctypes.c_int), ("eps", ctypes.c_float)]
 
 
+class ClipVisionConfig(ctypes.Structure):
+    _fields_ = [("image", ctypes.c_int), ("patch", ctypes.c_int), ("dim", ctypes.c_int), ("heads", ctypes.c_int),
+                ("layers", ctypes.c_int), ("ffn", ctypes.c_int), ("proj_dim", ctypes.c_int), ("eps", ctypes.c_float)]
+
+
 class GemmExt(ctypes.Structure):
     _fields_ = [("row_c", ctypes.c_void_p), ("out_cen", ctypes.c_void_p), ("ld_cen", ctypes.c_int),
                 ("part_out", ctypes.c_void_p), ("part_in", ctypes.c_void_p), ("np_in", ctypes.c_int),
@@ -148,6 +153,17 @@ SIGNATURES = {
     "uspace_layernorm_f32": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "uspace_table_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "uspace_quick_gelu_bf16": (_I, [_P, _L, _P]),
+    "uspace_clipv_num_params": (_I, [ctypes.POINTER(ClipVisionConfig)]),
+    "uspace_clipv_param_numel": (_L, [ctypes.POINTER(ClipVisionConfig), _I]),
+    "uspace_clipv_weight_bytes": (_SZ, [ctypes.POINTER(ClipVisionConfig)]),
+    "uspace_clipv_workspace_bytes": (_SZ, [ctypes.POINTER(ClipVisionConfig), _I]),
+    "uspace_clipv_pack_weights": (_I, [ctypes.POINTER(ClipVisionConfig), _P, _I, _P, _SZ, _P]),
+    "uspace_clipv_forward": (_I, [ctypes.POINTER(ClipVisionConfig), _P, _P, _SZ, _P, _P, _P, _I, _I, _P, _P]),
+    "uspace_clip_preprocess": (_I, [_P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _P]),
+    "uspace_linear_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "uspace_gather_rows_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "uspace_cosine_f32": (_I, [_P, _P, _P, _I, _I, _F, _I, _P]),
+    "uspace_normalized_diff_f32": (_I, [_P, _P, _P, _I, _I, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),

@@ -1,0 +1,439 @@
+// CLIP's image side and the CLIP score (HF CLIPVisionModelWithProjection + the cosine of CLIPModel): image preprocessing
+// (save_image quantisation, antialiased bicubic resize, mean / std), the vision tower on the kernels of this library -- patch rows ->
+// uspace_gemm_bf16, class token + position table, pre_layrnorm, the pre-LN blocks of clip.hip with NON-causal attention, post_layernorm
+// of token 0, visual_projection -- and the small fp32 pieces of the metric: a no-bias fp32 linear for the two projections, a row gather
+// for the text pooling, the cosine and the normalised difference of the directional (editing) similarity.
+// Every reduction runs in a fixed order inside one wave or one block: no atomics, run-to-run bit-equal.
+#include <vector>
+
+#include "blob.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------------------- preprocessing
+// Keys cubic convolution kernel, a = -0.5 (the filter of torch's antialiased bicubic and of PIL's BICUBIC)
+__device__ __forceinline__ float keys_cubic(float x) {
+    x = fabsf(x);
+    if (x < 1.0f) return (1.5f * x - 2.5f) * x * x + 1.0f;
+    if (x < 2.0f) return ((-0.5f * x + 2.5f) * x - 4.0f) * x + 2.0f;
+    return 0.0f;
+}
+
+// the window of output index o: input pixels lo .. lo + n - 1 (clipped to the image), centre (o + 0.5) scale, support 2 max(scale, 1)
+__device__ __forceinline__ void resize_window(int o, float scale, float support, int H, float* center, int* lo, int* n) {
+    const float c = scale * ((float)o + 0.5f);
+    int a = (int)(c - support + 0.5f);
+    a = a < 0 ? 0 : a;
+    int b = (int)(c + support + 0.5f);
+    b = b > H ? H : b;
+    *center = c;
+    *lo = a;
+    *n = b - a;
+}
+
+constexpr int RS_MAX_H = 4096;    // input side the row buffer holds
+constexpr int RS_MAX_TAPS = 256;  // window length: 4 max(H / S, 1) + 2 at most
+
+// One block per output row (b, c, oy): the vertical pass over every input column into LDS, then the horizontal pass of each
+// output pixel; both with the window weights renormalised to sum 1.  out = (clamp(v, 0, 255) / 255 - mean[c]) / std[c].
+__global__ __launch_bounds__(256) void clip_preprocess_kernel(const float* __restrict__ img, float* __restrict__ out, int H, int S,
+                                                              int quantize, float m0, float m1, float m2, float s0, float s1,
+                                                              float s2) {
+    __shared__ float col[RS_MAX_H];
+    __shared__ float wy[RS_MAX_TAPS];
+    __shared__ float wy_sum[1];
+    const int oy = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const float scale = (float)H / (float)S;
+    const float support = 2.0f * fmaxf(scale, 1.0f), inv = 1.0f / fmaxf(scale, 1.0f);
+    float cy;
+    int y0, ny;
+    resize_window(oy, scale, support, H, &cy, &y0, &ny);
+    const int tid = threadIdx.x;
+    // vertical weights: one wave computes them and their sum in lane order
+    if (tid < 64) {
+        float part = 0.0f;
+        for (int j = tid; j < ny; j += 64) {
+            const float w = keys_cubic(((float)(j + y0) - cy + 0.5f) * inv);
+            wy[j] = w;
+            part += w;
+        }
+        part = wave_sum(part);
+        if (tid == 0) wy_sum[0] = part;
+    }
+    __syncthreads();
+    const float ry = 1.0f / wy_sum[0];
+    const float* src = img + ((size_t)(b * 3 + c) * H + y0) * H;
+    for (int ix = tid; ix < H; ix += 256) {
+        float acc = 0.0f;
+        for (int j = 0; j < ny; ++j) {
+            // two fp32 roundings, never one fused multiply-add: save_image's x.mul(255).add_(0.5) decides the ties this way
+            float v = __fmul_rn(255.0f, src[(size_t)j * H + ix]);
+            if (quantize) v = fminf(fmaxf(floorf(__fadd_rn(v, 0.5f)), 0.0f), 255.0f);
+            acc = fmaf(wy[j], v, acc);
+        }
+        col[ix] = acc * ry;
+    }
+    __syncthreads();
+    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+    float* dst = out + ((size_t)(b * 3 + c) * S + oy) * S;
+    for (int ox = tid; ox < S; ox += 256) {
+        float cx;
+        int x0, nx;
+        resize_window(ox, scale, support, H, &cx, &x0, &nx);
+        float acc = 0.0f, tot = 0.0f;
+        for (int j = 0; j < nx; ++j) {
+            const float w = keys_cubic(((float)(j + x0) - cx + 0.5f) * inv);
+            acc = fmaf(w, col[x0 + j], acc);
+            tot += w;
+        }
+        const float v = fminf(fmaxf(acc / tot, 0.0f), 255.0f) / 255.0f;
+        dst[ox] = (v - mean) / sd;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- tower pieces
+// rows[b * N + gy * G + gx][k], k = (c, py, px) -> pixel_values[b, c, gy p + py, gx p + px] as bf16; columns K .. Kp - 1 are zero.
+// One block per patch row.
+__global__ __launch_bounds__(256) void patch_rows_kernel(const float* __restrict__ pv, bf16_t* __restrict__ rows, int S, int p, int G,
+                                                         int K, int Kp) {
+    const int row = blockIdx.x;
+    const int N = G * G, b = row / N, i = row - b * N, gy = i / G, gx = i - gy * G;
+    const int pp = p * p;
+    bf16_t* dst = rows + (size_t)row * Kp;
+    for (int k = threadIdx.x; k < Kp; k += 256) {
+        float v = 0.0f;
+        if (k < K) {
+            const int c = k / pp, r = k - c * pp, py = r / p, px = r - py * p;
+            v = pv[((size_t)(b * 3 + c) * S + gy * p + py) * S + gx * p + px];
+        }
+        dst[k] = f2bf(v);
+    }
+}
+
+// x[b, 0] = cls + pos[0];  x[b, 1 + i] = patch[b, i] + pos[1 + i]  (HF CLIPVisionEmbeddings); one block per token row, fp32
+__global__ __launch_bounds__(256) void assemble_tokens_kernel(const float* __restrict__ patch, const float* __restrict__ cls,
+                                                              const float* __restrict__ pos, float* __restrict__ x, int T, int D) {
+    const int row = blockIdx.x, b = row / T, t = row - b * T;
+    const float* a = t == 0 ? cls : patch + ((size_t)b * (T - 1) + (t - 1)) * D;
+    const float* pr = pos + (size_t)t * D;
+    for (int d = threadIdx.x * 4; d < D; d += 1024) *(f32x4*)(x + (size_t)row * D + d) = *(const f32x4*)(a + d) + *(const f32x4*)(pr + d);
+}
+
+// out[b, :] = x[b, idx[b], :] of x [B, L, D]; idx == NULL: row 0 (the class token).  One block per sample; an index outside
+// [0, L) is clamped (validated on the host).
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, const int* __restrict__ idx, float* __restrict__ out,
+                                                          int L, int D) {
+    const int b = blockIdx.x;
+    int r = idx ? idx[b] : 0;
+    r = r < 0 ? 0 : (r >= L ? L - 1 : r);
+    const float* src = x + ((size_t)b * L + r) * D;
+    for (int d = threadIdx.x; d < D; d += 256) out[(size_t)b * D + d] = src[d];
+}
+
+// ------------------------------------------------------------------------------------------------------------- fp32 linear
+// out[b, n] = sum_k x[b, k] w[n, k]: one wave per output column n and group of LIN_ROWS batch rows; the lanes stride K in float4,
+// the wave reduction has a fixed order.  K % 4 == 0.
+constexpr int LIN_ROWS = 8;
+__global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ out,
+                                                         int B, int N, int K) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b0 = blockIdx.y * LIN_ROWS;
+    if (n >= N) return;
+    float acc[LIN_ROWS];
+#pragma unroll
+    for (int r = 0; r < LIN_ROWS; ++r) acc[r] = 0.0f;
+    const float* wr = w + (size_t)n * K;
+    for (int k = lane * 4; k < K; k += 256) {
+        const f32x4 wv = *(const f32x4*)(wr + k);
+#pragma unroll
+        for (int r = 0; r < LIN_ROWS; ++r) {
+            const int b = b0 + r < B ? b0 + r : B - 1;      // rows past the batch repeat the last one and are not stored
+            const f32x4 xv = *(const f32x4*)(x + (size_t)b * K + k);
+            acc[r] = fmaf(wv[0], xv[0], acc[r]);
+            acc[r] = fmaf(wv[1], xv[1], acc[r]);
+            acc[r] = fmaf(wv[2], xv[2], acc[r]);
+            acc[r] = fmaf(wv[3], xv[3], acc[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < LIN_ROWS; ++r) {
+        const float v = wave_sum(acc[r]);
+        if (lane == 0 && b0 + r < B) out[(size_t)(b0 + r) * N + n] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- the score
+// one wave per row: out[b] = scale <a_b, c_b> / (|a_b| |c_b|), optionally max(., 0)
+__global__ __launch_bounds__(256) void cosine_kernel(const float* __restrict__ a, const float* __restrict__ c, float* __restrict__ out,
+                                                     int B, int D, float scale, int relu) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float* ar = a + (size_t)b * D;
+    const float* cr = c + (size_t)b * D;
+    float dot = 0.0f, na = 0.0f, nc = 0.0f;
+    for (int d = lane; d < D; d += 64) {
+        const float u = ar[d], v = cr[d];
+        dot = fmaf(u, v, dot);
+        na = fmaf(u, u, na);
+        nc = fmaf(v, v, nc);
+    }
+    dot = wave_sum(dot);
+    na = wave_sum(na);
+    nc = wave_sum(nc);
+    float v = scale * (dot / (sqrtf(na) * sqrtf(nc)));
+    if (relu) v = fmaxf(v, 0.0f);
+    if (lane == 0) out[b] = v;
+}
+
+// one wave per row: out[b] = a_b / |a_b| - c_b / |c_b|  (the step of an embedding under an edit, on the unit sphere)
+__global__ __launch_bounds__(256) void normalized_diff_kernel(const float* __restrict__ a, const float* __restrict__ c,
+                                                              float* __restrict__ out, int B, int D) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float* ar = a + (size_t)b * D;
+    const float* cr = c + (size_t)b * D;
+    float na = 0.0f, nc = 0.0f;
+    for (int d = lane; d < D; d += 64) {
+        na = fmaf(ar[d], ar[d], na);
+        nc = fmaf(cr[d], cr[d], nc);
+    }
+    const float ia = 1.0f / sqrtf(wave_sum(na)), ic = 1.0f / sqrtf(wave_sum(nc));
+    for (int d = lane; d < D; d += 64) out[(size_t)b * D + d] = ar[d] * ia - cr[d] * ic;
+}
+
+// ------------------------------------------------------------------------------------------------------------- the model
+struct VLayer {
+    size_t wqkv, bqkv, wo, bo, ln1g, ln1b, w1, b1, w2, b2, ln2g, ln2b;
+};
+struct VModel {
+    ParamTable t;
+    size_t cls, patch, pos, preg, preb, postg, postb, proj;
+    std::vector<VLayer> layers;
+};
+
+int patch_k(const uspace_clipv_config& c) { return 3 * c.patch * c.patch; }
+int patch_kp(const uspace_clipv_config& c) { return (patch_k(c) + 63) / 64 * 64; }
+int n_patches(const uspace_clipv_config& c) { return (c.image / c.patch) * (c.image / c.patch); }
+
+bool valid_clipv(const uspace_clipv_config* c) {
+    if (!c || c->image <= 0 || c->patch <= 0 || c->dim <= 0 || c->heads <= 0 || c->layers < 0 || c->ffn <= 0 || c->proj_dim <= 0) return false;
+    if (c->dim != c->heads * 64 || (c->dim & 63) || (c->ffn & 63) || c->dim > 4096 || (c->proj_dim & 3)) return false;
+    if (c->image % c->patch || c->image > 4096 || c->patch > 256) return false;
+    return true;
+}
+
+// HF CLIPVisionModelWithProjection.state_dict() order (see the header)
+VModel build_clipv(const uspace_clipv_config& c) {
+    VModel m;
+    ParamTable& t = m.t;
+    auto put = [&t](long numel, PKind k) { return t.at(t.add(numel, k)); };
+    const long D = c.dim, F = c.ffn, K = patch_k(c), Kp = patch_kp(c);
+    m.cls = put(D, P_F32);
+    // patch weight [D, K] fp32 -> bf16 [D, Kp]: the region is Kp wide, the cast fills K of every row (the forward's pack step)
+    m.patch = t.arena.take((size_t)D * Kp * 2);
+    t.add_at(m.patch, D * K, P_BF16);
+    m.pos = put((long)(n_patches(c) + 1) * D, P_F32);
+    m.preg = put(D, P_F32);
+    m.preb = put(D, P_F32);
+    for (int i = 0; i < c.layers; ++i) {
+        VLayer l;
+        l.wqkv = t.arena.take(3 * D * D * 2);      // q | k | v rows, as clip.hip packs them; HF lists k, v, q
+        l.bqkv = t.arena.take(3 * D * 4);
+        for (const int slot : {1, 2, 0}) {
+            t.add_at(l.wqkv + slot * D * D * 2, D * D, P_BF16);
+            t.add_at(l.bqkv + slot * D * 4, D, P_F32);
+        }
+        l.wo = put(D * D, P_BF16);
+        l.bo = put(D, P_F32);
+        l.ln1g = put(D, P_F32);
+        l.ln1b = put(D, P_F32);
+        l.w1 = put(F * D, P_BF16);
+        l.b1 = put(F, P_F32);
+        l.w2 = put(D * F, P_BF16);
+        l.b2 = put(D, P_F32);
+        l.ln2g = put(D, P_F32);
+        l.ln2b = put(D, P_F32);
+        m.layers.push_back(l);
+    }
+    m.postg = put(D, P_F32);
+    m.postb = put(D, P_F32);
+    m.proj = put((long)c.proj_dim * D, P_F32);
+    return m;
+}
+
+// bf16 [D, K] dense (the staging area behind the table) -> [D, Kp] with zero pad columns (the table's region); one block per row
+__global__ __launch_bounds__(256) void pad_patch_rows_kernel(const bf16_t* __restrict__ dense, bf16_t* __restrict__ padded, int K, int Kp) {
+    const int d = blockIdx.x;
+    for (int k = threadIdx.x; k < Kp; k += 256) padded[(size_t)d * Kp + k] = k < K ? dense[(size_t)d * K + k] : (bf16_t)0;
+}
+
+struct VWs {
+    size_t x, e, pe, rows, h, qkv, att, f, tok0, pool, total;
+};
+VWs plan_clipv_ws(const uspace_clipv_config& c, int B) {
+    VWs w;
+    Arena a;
+    const size_t N = n_patches(c), M = (size_t)B * (N + 1), D = c.dim;
+    w.x = a.take(M * D * 4);
+    w.e = a.take(M * D * 4);
+    w.pe = a.take((size_t)B * N * D * 4);
+    w.rows = a.take((size_t)B * N * patch_kp(c) * 2);
+    w.h = a.take(M * D * 2);
+    w.qkv = a.take(M * 3 * D * 2);
+    w.att = a.take(M * D * 2);
+    w.f = a.take(M * (size_t)c.ffn * 2);
+    w.tok0 = a.take((size_t)B * D * 4);
+    w.pool = a.take((size_t)B * D * 4);
+    w.total = a.off;
+    return w;
+}
+
+// the resident kernel where its plan accepts the shape, the streaming one beyond (as uvit.hip's attention())
+int attention_any(const uint16_t* qkv, uint16_t* out, int B, int L, int H, uspace_stream_t stream) {
+    int plan[8];
+    if (uspace_attention_plan(B, L, H, 0, plan) == USPACE_OK) return uspace_attention_bf16(qkv, nullptr, out, B, L, H, stream);
+    return uspace_attention_long_bf16(qkv, nullptr, out, B, L, H, stream);
+}
+
+}  // namespace
+
+extern "C" int uspace_clipv_num_params(const uspace_clipv_config* cfg) {
+    return valid_clipv(cfg) ? build_clipv(*cfg).t.n_params : USPACE_ERR_ARG;
+}
+
+extern "C" long uspace_clipv_param_numel(const uspace_clipv_config* cfg, int index) {
+    return valid_clipv(cfg) ? build_clipv(*cfg).t.numel(index) : (long)USPACE_ERR_ARG;
+}
+
+extern "C" size_t uspace_clipv_weight_bytes(const uspace_clipv_config* cfg) {
+    // + one dense bf16 copy of the patch weight behind the table: the staging area of the pad step
+    return valid_clipv(cfg) ? build_clipv(*cfg).t.bytes() + us_align_up((size_t)cfg->dim * patch_k(*cfg) * 2) : 0;
+}
+
+extern "C" size_t uspace_clipv_workspace_bytes(const uspace_clipv_config* cfg, int B) {
+    return (valid_clipv(cfg) && B > 0) ? plan_clipv_ws(*cfg, B).total : 0;
+}
+
+extern "C" int uspace_clipv_pack_weights(const uspace_clipv_config* cfg, const float* const* params, int n_params, void* blob,
+                                         size_t blob_bytes, uspace_stream_t stream) {
+    if (!valid_clipv(cfg)) return USPACE_ERR_ARG;
+    if (blob && blob_bytes < uspace_clipv_weight_bytes(cfg)) return USPACE_ERR_WORKSPACE;
+    VModel m = build_clipv(*cfg);
+    // the shared loop casts the patch weight densely ([D, K]); it goes to the staging area behind the table and is then
+    // spread to rows of Kp with zero pad columns
+    const int K = patch_k(*cfg), Kp = patch_kp(*cfg);
+    const size_t stage = m.t.bytes();
+    m.t.p[1].offset = stage;
+    US_TRY(us_pack_table(m.t, params, n_params, blob, blob_bytes, stream));
+    hipLaunchKernelGGL(pad_patch_rows_kernel, dim3(cfg->dim), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)((char*)blob + stage),
+                       (bf16_t*)((char*)blob + m.patch), K, Kp);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_clipv_forward(const uspace_clipv_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                    const float* pixel_values, float* image_embeds, float* pooler_output, int B, int stop_after_layer,
+                                    float* tap_out, uspace_stream_t stream) {
+    if (!valid_clipv(cfg) || !blob || !workspace || !pixel_values || B <= 0) return USPACE_ERR_ARG;
+    const bool tap = stop_after_layer != -1;
+    if (stop_after_layer < -2 || (tap && !tap_out) || (!tap && !image_embeds)) return USPACE_ERR_ARG;
+    const VModel m = build_clipv(*cfg);
+    const VWs w = plan_clipv_ws(*cfg, B);
+    if (workspace_bytes < w.total) return USPACE_ERR_WORKSPACE;
+    const char* wb = (const char*)blob;
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = cfg->dim, F = cfg->ffn, H = cfg->heads, G = cfg->image / cfg->patch, N = G * G, T = N + 1, M = B * T;
+    const int K = patch_k(*cfg), Kp = patch_kp(*cfg);
+    float* x = (float*)(ws + w.x);
+    float* e = (float*)(ws + w.e);
+    float* pe = (float*)(ws + w.pe);
+    uint16_t* rows = (uint16_t*)(ws + w.rows);
+    uint16_t* h = (uint16_t*)(ws + w.h);
+    uint16_t* qkv = (uint16_t*)(ws + w.qkv);
+    uint16_t* att = (uint16_t*)(ws + w.att);
+    uint16_t* f = (uint16_t*)(ws + w.f);
+    float* tok0 = (float*)(ws + w.tok0);
+    float* pool = pooler_output ? pooler_output : (float*)(ws + w.pool);
+    auto PF = [&](size_t off) { return (const float*)(wb + off); };
+    auto PH = [&](size_t off) { return (const uint16_t*)(wb + off); };
+    constexpr int B_ = USPACE_EPI_BIAS, R_ = USPACE_EPI_RESIDUAL, F_ = USPACE_EPI_OUT_F32, H_ = USPACE_EPI_OUT_BF16;
+    auto dump = [&](const float* src) {
+        return hipMemcpyAsync(tap_out, src, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s) == hipSuccess ? USPACE_OK : USPACE_ERR_LAUNCH;
+    };
+
+    hipLaunchKernelGGL(patch_rows_kernel, dim3(B * N), dim3(256), 0, s, pixel_values, rows, cfg->image, cfg->patch, G, K, Kp);
+    US_CHECK_LAUNCH();
+    US_TRY(uspace_gemm_bf16(rows, Kp, nullptr, 0, Kp, PH(m.patch), Kp, B * N, D, Kp, F_, nullptr, nullptr, 0, pe, D, nullptr, 0, stream));
+    hipLaunchKernelGGL(assemble_tokens_kernel, dim3(M), dim3(256), 0, s, pe, PF(m.cls), PF(m.pos), e, T, D);
+    US_CHECK_LAUNCH();
+    // stop_after_layer: -1 = the whole model; -2 = the embeddings before pre_layrnorm; k >= 0 = the hidden state after k layers
+    if (stop_after_layer == -2) return dump(e);
+    US_TRY(uspace_layernorm_f32(e, PF(m.preg), PF(m.preb), x, M, D, cfg->eps, stream));
+    const int n_layers = stop_after_layer < 0 ? cfg->layers : (stop_after_layer < cfg->layers ? stop_after_layer : cfg->layers);
+    for (int i = 0; i < n_layers; ++i) {
+        const VLayer& l = m.layers[i];
+        US_TRY(uspace_layernorm_f32_bf16(x, PF(l.ln1g), PF(l.ln1b), h, M, D, cfg->eps, stream));
+        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(l.wqkv), D, M, 3 * D, D, B_ | H_, PF(l.bqkv), nullptr, 0, nullptr, 0, qkv,
+                                3 * D, stream));
+        US_TRY(attention_any(qkv, att, B, T, H, stream));
+        US_TRY(uspace_gemm_bf16(att, D, nullptr, 0, D, PH(l.wo), D, M, D, D, B_ | R_ | F_, PF(l.bo), x, D, x, D, nullptr, 0, stream));
+        US_TRY(uspace_layernorm_f32_bf16(x, PF(l.ln2g), PF(l.ln2b), h, M, D, cfg->eps, stream));
+        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(l.w1), D, M, F, D, B_ | H_, PF(l.b1), nullptr, 0, nullptr, 0, f, F, stream));
+        US_TRY(uspace_quick_gelu_bf16(f, (long)M * F, stream));
+        US_TRY(uspace_gemm_bf16(f, F, nullptr, 0, F, PH(l.w2), F, M, D, F, B_ | R_ | F_, PF(l.b2), x, D, x, D, nullptr, 0, stream));
+    }
+    if (tap) return dump(x);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, s, x, (const int*)nullptr, tok0, T, D);
+    US_CHECK_LAUNCH();
+    US_TRY(uspace_layernorm_f32(tok0, PF(m.postg), PF(m.postb), pool, B, D, cfg->eps, stream));
+    return uspace_linear_f32(pool, PF(m.proj), image_embeds, B, cfg->proj_dim, D, stream);
+}
+
+extern "C" int uspace_clip_preprocess(const float* images, float* pixel_values, int B, int H, int W, int S, int quantize,
+                                      const float* mean, const float* std, uspace_stream_t stream) {
+    if (!images || !pixel_values || !mean || !std || B <= 0 || H <= 0 || S <= 0 || H != W) return USPACE_ERR_ARG;
+    if (H > RS_MAX_H || S > 65535 || B > 65535) return USPACE_ERR_ARG;
+    const double scale = (double)H / S;
+    if (4.0 * (scale > 1.0 ? scale : 1.0) + 2.0 > RS_MAX_TAPS) return USPACE_ERR_ARG;
+    for (int c = 0; c < 3; ++c)
+        if (!(std[c] > 0.0f)) return USPACE_ERR_ARG;
+    hipLaunchKernelGGL(clip_preprocess_kernel, dim3(S, 3, B), dim3(256), 0, (hipStream_t)stream, images, pixel_values, H, S, quantize,
+                       mean[0], mean[1], mean[2], std[0], std[1], std[2]);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_linear_f32(const float* x, const float* w, float* out, int B, int N, int K, uspace_stream_t stream) {
+    if (!x || !w || !out || B <= 0 || N <= 0 || K <= 0 || (K & 3)) return USPACE_ERR_ARG;
+    const int gy = us_cdiv(B, LIN_ROWS);
+    if (gy > 65535) return USPACE_ERR_ARG;
+    hipLaunchKernelGGL(linear_f32_kernel, dim3(us_cdiv(N, 4), gy), dim3(256), 0, (hipStream_t)stream, x, w, out, B, N, K);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_gather_rows_f32(const float* x, const int* idx, float* out, int B, int L, int D, uspace_stream_t stream) {
+    if (!x || !idx || !out || B <= 0 || L <= 0 || D <= 0) return USPACE_ERR_ARG;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, idx, out, L, D);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_cosine_f32(const float* a, const float* b, float* out, int B, int D, float scale, int relu,
+                                 uspace_stream_t stream) {
+    if (!a || !b || !out || B <= 0 || D <= 0) return USPACE_ERR_ARG;
+    hipLaunchKernelGGL(cosine_kernel, dim3(us_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, a, b, out, B, D, scale, relu);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_normalized_diff_f32(const float* a, const float* b, float* out, int B, int D, uspace_stream_t stream) {
+    if (!a || !b || !out || B <= 0 || D <= 0) return USPACE_ERR_ARG;
+    hipLaunchKernelGGL(normalized_diff_kernel, dim3(us_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, a, b, out, B, D);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}

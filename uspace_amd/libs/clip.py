@@ -166,6 +166,190 @@ class CLIPTextTransformer(nn.Module):
         return out
 
 
+CLIP_L_VISION = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224,
+                     patch_size=14, projection_dim=768, layer_norm_eps=1e-5)                  # openai/clip-vit-large-patch14
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)                                               # HF OPENAI_CLIP_MEAN / _STD
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+class CLIPVisionTransformer(nn.Module):
+    """HF CLIPVisionModelWithProjection's computation (``image_embeds``) in libuspace_hip.so (``uspace_clipv_forward``), with the
+    image preprocessing of ``uspace_clip_preprocess`` in front of it; parameters in the HF state_dict order and naming
+    (``vision_model.*``, ``visual_projection.weight``)."""
+
+    def __init__(self, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224,
+                 patch_size=14, projection_dim=768, layer_norm_eps=1e-5, hidden_act="quick_gelu", num_channels=3, **_ignored):
+        super().__init__()
+        if hidden_act != "quick_gelu":
+            raise NotImplementedError(f"hidden_act={hidden_act!r}: the CLIP vision tower of openai/clip-vit-large-patch14 uses quick_gelu")
+        if hidden_size != 64 * num_attention_heads or hidden_size % 64 or intermediate_size % 64:
+            raise NotImplementedError("head_dim must be 64 and the widths multiples of 64")
+        if num_channels != 3 or image_size % patch_size or projection_dim % 4:
+            raise NotImplementedError("3 channels, image_size a multiple of patch_size and projection_dim a multiple of 4")
+        self.cfg = dict(image=image_size, patch=patch_size, dim=hidden_size, heads=num_attention_heads, layers=num_hidden_layers,
+                        ffn=intermediate_size, proj_dim=projection_dim, eps=layer_norm_eps)
+        self.tokens = (image_size // patch_size) ** 2 + 1
+        vm = ParamGroup()
+        emb = vm.child("embeddings")
+        emb.add("class_embedding", hidden_size)
+        emb.child("patch_embedding").add("weight", hidden_size, 3, patch_size, patch_size)
+        emb.child("position_embedding").add("weight", self.tokens, hidden_size)
+        _norm(vm, "pre_layrnorm", hidden_size)                 # HF's spelling
+        enc = vm.child("encoder")
+        layers = []
+        for _ in range(num_hidden_layers):
+            lyr = ParamGroup()
+            att = lyr.child("self_attn")
+            for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+                _linear(att, n, hidden_size, hidden_size)
+            _norm(lyr, "layer_norm1", hidden_size)
+            mlp = lyr.child("mlp")
+            _linear(mlp, "fc1", intermediate_size, hidden_size)
+            _linear(mlp, "fc2", hidden_size, intermediate_size)
+            _norm(lyr, "layer_norm2", hidden_size)
+            layers.append(lyr)
+        enc.add_module("layers", nn.ModuleList(layers))
+        _norm(vm, "post_layernorm", hidden_size)
+        self.vision_model = vm
+        self.visual_projection = ParamGroup()
+        self.visual_projection.add("weight", projection_dim, hidden_size)
+        with torch.no_grad():
+            for name, prm in self.named_parameters():
+                if ("norm" in name) and name.endswith("weight"):
+                    prm.fill_(1.0)
+                elif name.endswith("bias"):
+                    prm.zero_()
+                else:
+                    prm.normal_(0.0, 0.02)
+        self._packed = PackedWeights("uspace_clipv_", "CLIP vision", self._canonical_params, self._c_cfg())
+        self._ws = WorkspaceCache(1)
+        self.eval()
+        self.requires_grad_(False)
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Accepts HF CLIPModel / CLIPVisionModel / CLIPVisionModelWithProjection checkpoints, with or without the
+        ``vision_model.`` prefix; ``position_ids`` buffers and text entries are dropped."""
+        sd = {}
+        for k, v in state_dict.items():
+            if k.startswith(("text_model.", "text_projection", "logit_scale")) or k.endswith("position_ids"):
+                continue
+            if not k.startswith(("vision_model.", "visual_projection")):
+                k = "vision_model." + k
+            sd[k] = v
+        return super().load_state_dict(sd, strict=strict)
+
+    def _c_cfg(self):
+        c = self.cfg
+        return _hip.ClipVisionConfig(c["image"], c["patch"], c["dim"], c["heads"], c["layers"], c["ffn"], c["proj_dim"], c["eps"])
+
+    def invalidate_packed(self):
+        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
+        self._packed.invalidate()
+
+    def _canonical_params(self):
+        return list(self.parameters())
+
+    def _packed_blob(self, device):
+        return self._packed.blob(device)
+
+    def preprocess(self, images, quantize=True, mean=CLIP_MEAN, std=CLIP_STD):
+        """images [B, 3, H, H] fp32 in [0, 1] on the device -> pixel_values [B, 3, image_size, image_size]: ``save_image``'s
+        rounding (``quantize``), antialiased bicubic resize (``uspace_clip_preprocess``), CLIP's mean and std."""
+        _hip.require_device(images, "images")
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+            raise ValueError(f"images must be [B, 3, H, H] (square), got {tuple(images.shape)}")
+        S = self.cfg["image"]
+        x = images.detach().to(torch.float32).contiguous()
+        B, _, H, W = x.shape
+        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=x.device)
+        if B == 0:
+            return out
+        m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+        _hip.check(_hip.lib().uspace_clip_preprocess(_hip.ptr(x), _hip.ptr(out), B, H, W, S, 1 if quantize else 0, m3, s3,
+                                                     _hip.stream_ptr()), "uspace_clip_preprocess")
+        return out
+
+    def forward(self, pixel_values, hidden_state=None, return_pooled=False):
+        """pixel_values [B, 3, S, S] -> image_embeds [B, projection_dim] fp32 (``return_pooled``: also HF's ``pooler_output``
+        [B, D]).  ``hidden_state=k``: the state [B, tokens, D] after k layers instead (k = 0: after pre_layrnorm, HF
+        ``hidden_states[k]``; "embeddings": before pre_layrnorm)."""
+        _hip.require_device(pixel_values, "pixel_values")
+        S, D, P = self.cfg["image"], self.cfg["dim"], self.cfg["proj_dim"]
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
+            raise ValueError(f"pixel_values must be [B, 3, {S}, {S}], got {tuple(pixel_values.shape)}")
+        dev = pixel_values.device
+        B = pixel_values.shape[0]
+        stop = -1 if hidden_state is None else (-2 if hidden_state == "embeddings" else int(hidden_state))
+        if stop < -2:
+            raise ValueError("hidden_state must be None, 'embeddings' or a layer count >= 0")
+        tap = torch.empty(B, self.tokens, D, dtype=torch.float32, device=dev) if stop != -1 else None
+        emb = torch.empty(B, P, dtype=torch.float32, device=dev) if stop == -1 else None
+        pooled = torch.empty(B, D, dtype=torch.float32, device=dev) if (return_pooled and stop == -1) else None
+        if B:
+            blob = self._packed_blob(dev)
+            L = _hip.lib()
+            cfg = self._c_cfg()
+            ws = self._ws.take(B, dev, L.uspace_clipv_workspace_bytes(ctypes.byref(cfg), B))
+            pv = pixel_values.detach().to(torch.float32).contiguous()
+            _hip.check(L.uspace_clipv_forward(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(pv), _hip.ptr(emb),
+                                              _hip.ptr(pooled), B, stop, _hip.ptr(tap), _hip.stream_ptr()), "uspace_clipv_forward")
+        if stop != -1:
+            return tap
+        return (emb, pooled) if return_pooled else emb
+
+
+class CLIPTextProjection(nn.Module):
+    """HF CLIPModel's text head: the pooled row of ``last_hidden_state`` through ``text_projection`` (no bias), in fp32
+    (``uspace_gather_rows_f32``, ``uspace_linear_f32``)."""
+
+    def __init__(self, hidden_size=768, projection_dim=768):
+        super().__init__()
+        if hidden_size % 4:
+            raise NotImplementedError("hidden_size must be a multiple of 4")
+        self.text_projection = ParamGroup()
+        self.text_projection.add("weight", projection_dim, hidden_size)
+        with torch.no_grad():
+            self.text_projection.weight.normal_(0.0, hidden_size ** -0.5)
+        self.eval()
+        self.requires_grad_(False)
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Accepts a CLIPModel / CLIPTextModelWithProjection checkpoint: only ``text_projection.weight`` is taken."""
+        return super().load_state_dict({k: v for k, v in state_dict.items() if k == "text_projection.weight"}, strict=strict)
+
+    @staticmethod
+    def pooled_index(input_ids, eos_token_id=None):
+        """HF's rule: ``eos_token_id`` 2 or None (the legacy config of this checkpoint family) -> ``argmax`` of the ids (the
+        end-of-text token has the largest id); otherwise the first position that holds ``eos_token_id``."""
+        if eos_token_id is None or eos_token_id == 2:
+            return input_ids.argmax(-1)
+        return (input_ids == eos_token_id).int().argmax(-1)
+
+    def forward(self, last_hidden_state, input_ids, eos_token_id=None):
+        """last_hidden_state [B, L, D] fp32 (device), input_ids [B, L] -> text_embeds [B, projection_dim] fp32."""
+        _hip.require_device(last_hidden_state, "last_hidden_state")
+        h = last_hidden_state.detach().to(torch.float32).contiguous()
+        if h.dim() != 3 or tuple(input_ids.shape) != tuple(h.shape[:2]):
+            raise ValueError(f"last_hidden_state [B, L, D] and input_ids [B, L] expected, got {tuple(h.shape)} and {tuple(input_ids.shape)}")
+        B, T, D = h.shape
+        w = self.text_projection.weight
+        _hip.require_device(w, "text_projection.weight")
+        if D != w.shape[1]:
+            raise ValueError(f"hidden size {D} does not match text_projection {tuple(w.shape)}")
+        out = torch.empty(B, w.shape[0], dtype=torch.float32, device=h.device)
+        if B == 0:
+            return out
+        idx = self.pooled_index(input_ids, eos_token_id).to(device=h.device, dtype=torch.int32).contiguous()
+        pooled = torch.empty(B, D, dtype=torch.float32, device=h.device)
+        L = _hip.lib()
+        _hip.check(L.uspace_gather_rows_f32(_hip.ptr(h), _hip.ptr(idx), _hip.ptr(pooled), B, T, D, _hip.stream_ptr()),
+                   "uspace_gather_rows_f32")
+        wf = w.detach().to(torch.float32).contiguous()
+        _hip.check(L.uspace_linear_f32(_hip.ptr(pooled), _hip.ptr(wf), _hip.ptr(out), B, w.shape[0], D, _hip.stream_ptr()),
+                   "uspace_linear_f32")
+        return out
+
+
 class AbstractEncoder(nn.Module):
     def encode(self, *args, **kwargs):
         raise NotImplementedError
