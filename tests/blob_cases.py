@@ -1,4 +1,4 @@
-"""The packed-weight blobs of the five models as the library lays them out: which configurations are pinned, how a size
+"""The packed-weight blobs of the six models as the library lays them out: which configurations are pinned, how a size
 record and a blob digest are taken.  Shared by tests/golden/make_blob_golden.py (which records them) and by
 tests/test_blob_layout.py / tests/test_gpu_blob_pack.py (which compare).  Nothing here goes through the Python wrappers'
 own pack path: the size queries and ``uspace_*_pack_weights`` are called through ctypes."""
@@ -48,12 +48,20 @@ def clip_cfg(vocab_size, hidden_size, intermediate_size, num_hidden_layers, num_
                            max_position_embeddings, layer_norm_eps)
 
 
+def clipv_cfg(hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, image_size, patch_size, projection_dim,
+              layer_norm_eps, **_):
+    from uspace_amd import _hip
+    return _hip.ClipVisionConfig(image_size, patch_size, hidden_size, num_attention_heads, num_hidden_layers, intermediate_size,
+                                 projection_dim, layer_norm_eps)
+
+
 def size_cases(golden_dir):
     """{case name: (symbol prefix, config or None, [(label, extra workspace arguments)])}.  The U-ViT cases are every model of
     tools/bench_configs.py and the two tiny fixtures; they are recorded once per setting of uspace_gemm_set_sk (size_table)."""
     from bench import COMMON, MODELS
     from tools.bench_configs import CONFIGS
-    from uspace_amd.libs.clip import CLIP_L_TEXT
+    from tests.clip_vision_cases import TINY_VISION
+    from uspace_amd.libs.clip import CLIP_L_TEXT, CLIP_L_VISION
     plain = [("", ())]
     cases = {}
     for model in sorted({c["model"] for c in CONFIGS}):
@@ -68,6 +76,8 @@ def size_cases(golden_dir):
         cases[f"vae_enc/{tag}"] = ("uspace_vae_enc_", vae_cfg(enc), plain)
     cases["clip/L"] = ("uspace_clip_", clip_cfg(**CLIP_L_TEXT), plain)
     cases["clip/tiny"] = ("uspace_clip_", clip_cfg(**_meta(golden_dir, "clip_text_tiny.npz")[1]), plain)
+    cases["clipv/L"] = ("uspace_clipv_", clipv_cfg(**CLIP_L_VISION), plain)
+    cases["clipv/tiny"] = ("uspace_clipv_", clipv_cfg(**TINY_VISION), plain)
     cases["inception"] = ("uspace_inception_", None, [("299/", (299, 299)), ("64/", (64, 64))])
     return cases
 
@@ -126,13 +136,21 @@ def tiny_model(kind, golden_dir):
         m.load_state_dict({"text_model." + k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd/")})
         m = m.cuda()
         return m, "uspace_clip_", clip_cfg(**meta), list(m.parameters())
+    if kind == "clipv":
+        from tests import clip_vision_cases as V
+        from uspace_amd.libs.clip import CLIPVisionTransformer
+        cfg = V.TOWER_CASES["tiny"][0]
+        m = CLIPVisionTransformer(**cfg)
+        m.load_state_dict(V.case_params("tiny"))
+        m = m.cuda()
+        return m, "uspace_clipv_", clipv_cfg(**cfg), list(m.parameters())
     assert kind == "inception"
     from uspace_amd.tools.inception import InceptionV3
     m = InceptionV3([3], seed=0).cuda()
     return m, "uspace_inception_", None, list(m.state_dict().values())
 
 
-TINY_KINDS = ("tiny_u", "tiny_t2i", "vae", "vae_enc", "clip", "inception")
+TINY_KINDS = ("tiny_u", "tiny_t2i", "vae", "vae_enc", "clip", "clipv", "inception")
 
 
 def blob_digest(prefix, cfg, tensors):

@@ -1,4 +1,4 @@
-"""Every size the library reports for the packed weight blobs and the workspaces of the five models, against
+"""Every size the library reports for the packed weight blobs and the workspaces of the six models, against
 tests/golden/blob_sizes.json (recorded by tests/golden/make_blob_golden.py at the commit named in the file): exact integers, no
 margin.  Host queries only; the library loads without a GPU."""
 import ctypes
@@ -46,7 +46,8 @@ def test_invalid_configs_report_no_parameters_and_no_bytes():
            ("uspace_uvit_", _hip.UvitConfig(32, 2, 4, 1024, 19, 16, 4096, 0, 0, 0)),       # odd depth
            ("uspace_vae_", _hip.VaeConfig(100, mult, 4, 2, 256)),                           # ch not a multiple of 64
            ("uspace_vae_enc_", _hip.VaeConfig(192, mult, 4, 2, 256)),                       # encoder: ch not a power of two
-           ("uspace_clip_", _hip.ClipConfig(49408, 768, 8, 12, 3072, 77, 1e-5))]           # head_dim != 64
+           ("uspace_clip_", _hip.ClipConfig(49408, 768, 8, 12, 3072, 77, 1e-5)),           # head_dim != 64
+           ("uspace_clipv_", _hip.ClipVisionConfig(224, 14, 1024, 12, 24, 4096, 768, 1e-5))]   # heads * 64 != dim
     for prefix, cfg in bad:
         ref = ctypes.byref(cfg)
         assert getattr(L, prefix + "num_params")(ref) < 0 and getattr(L, prefix + "param_numel")(ref, 0) < 0, prefix

@@ -37,6 +37,7 @@ WRAPPERS = {
     "vae_enc": ("_packed_enc_blob", "_ws_enc", 1,
                 lambda m, B: m.encode_moments(torch.zeros(B, 3, m.resolution, m.resolution, device="cuda"))),
     "clip": ("_packed_blob", "_ws", 1, lambda m, B: m(torch.zeros(B, 77, dtype=torch.long, device="cuda"))),
+    "clipv": ("_packed_blob", "_ws", 1, lambda m, B: m(torch.zeros(B, 3, m.cfg["image"], m.cfg["image"], device="cuda"))),
     "inception": ("_blob", "_ws", 1, lambda m, B: m.features(torch.rand(B, 3, 64, 64, device="cuda"))),
 }
 

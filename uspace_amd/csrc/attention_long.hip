@@ -265,3 +265,12 @@ extern "C" int uspace_attention_long_bf16(const uint16_t* qkv, const float* key_
     if (key_scale) return p.QB == 128 ? long_launch<true, 2>(p, a) : long_launch<true, 1>(p, a);
     return p.QB == 128 ? long_launch<false, 2>(p, a) : long_launch<false, 1>(p, a);
 }
+
+// The attention of a block: the resident kernel wherever its plan takes the length (att_plan of attention.hip is the one place that
+// knows the limit), the streaming kernel beyond
+int us_attention_any(const uint16_t* qkv, const float* key_scale, uint16_t* out, int B, int L, int H, uspace_stream_t stream) {
+    int plan[8];
+    if (uspace_attention_plan(B, L, H, key_scale != nullptr, plan) == USPACE_OK)
+        return uspace_attention_bf16(qkv, key_scale, out, B, L, H, stream);
+    return uspace_attention_long_bf16(qkv, key_scale, out, B, L, H, stream);
+}

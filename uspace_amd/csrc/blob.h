@@ -1,6 +1,6 @@
 // One layout for every model's packed weights and workspaces (host side only): the aligned arena, the parameter table and
-// the loop that packs fp32 checkpoint tensors into a device blob.  uvit.hip, vae.hip (both halves) and clip.hip describe their
-// parameters with a ParamTable and serve num_params / param_numel / weight_bytes / pack_weights from it; inception.hip keeps its
+// the loop that packs fp32 checkpoint tensors into a device blob.  uvit.hip, vae.hip (both halves), clip.hip and clip_vision.hip
+// (the two towers' layers through clip_encoder.h) describe their parameters with a ParamTable and serve num_params / param_numel / weight_bytes / pack_weights from it; inception.hip keeps its
 // own layout (64-byte pieces, batch norm folded in fp64 at pack time).
 #pragma once
 #include <vector>

@@ -1,12 +1,12 @@
 // CLIP's image side and the CLIP score (HF CLIPVisionModelWithProjection + the cosine of CLIPModel): image preprocessing
 // (save_image quantisation, antialiased bicubic resize, mean / std), the vision tower on the kernels of this library -- patch rows ->
-// uspace_gemm_bf16, class token + position table, pre_layrnorm, the pre-LN blocks of clip.hip with NON-causal attention, post_layernorm
-// of token 0, visual_projection -- and the small fp32 pieces of the metric: a no-bias fp32 linear for the two projections, a row gather
-// for the text pooling, the cosine and the normalised difference of the directional (editing) similarity.
+// uspace_gemm_bf16, class token + position table, pre_layrnorm, the pre-LN blocks of clip_encoder.h (shared with clip.hip) with NON-causal
+// attention, post_layernorm of token 0, visual_projection -- and the small fp32 pieces of the metric: a no-bias fp32 linear for the two
+// projections, a row gather for the text pooling, the cosine and the normalised difference of the directional (editing) similarity.
 // Every reduction runs in a fixed order inside one wave or one block: no atomics, run-to-run bit-equal.
 #include <vector>
 
-#include "blob.h"
+#include "clip_encoder.h"
 
 namespace {
 
@@ -205,13 +205,10 @@ __global__ __launch_bounds__(256) void normalized_diff_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------------------- the model
-struct VLayer {
-    size_t wqkv, bqkv, wo, bo, ln1g, ln1b, w1, b1, w2, b2, ln2g, ln2b;
-};
 struct VModel {
     ParamTable t;
     size_t cls, patch, pos, preg, preb, postg, postb, proj;
-    std::vector<VLayer> layers;
+    std::vector<ClipEncLayer> layers;
 };
 
 int patch_k(const uspace_clipv_config& c) { return 3 * c.patch * c.patch; }
@@ -230,7 +227,7 @@ VModel build_clipv(const uspace_clipv_config& c) {
     VModel m;
     ParamTable& t = m.t;
     auto put = [&t](long numel, PKind k) { return t.at(t.add(numel, k)); };
-    const long D = c.dim, F = c.ffn, K = patch_k(c), Kp = patch_kp(c);
+    const long D = c.dim, K = patch_k(c), Kp = patch_kp(c);
     m.cls = put(D, P_F32);
     // patch weight [D, K] fp32 -> bf16 [D, Kp]: the region is Kp wide, the cast fills K of every row (the forward's pack step)
     m.patch = t.arena.take((size_t)D * Kp * 2);
@@ -238,26 +235,7 @@ VModel build_clipv(const uspace_clipv_config& c) {
     m.pos = put((long)(n_patches(c) + 1) * D, P_F32);
     m.preg = put(D, P_F32);
     m.preb = put(D, P_F32);
-    for (int i = 0; i < c.layers; ++i) {
-        VLayer l;
-        l.wqkv = t.arena.take(3 * D * D * 2);      // q | k | v rows, as clip.hip packs them; HF lists k, v, q
-        l.bqkv = t.arena.take(3 * D * 4);
-        for (const int slot : {1, 2, 0}) {
-            t.add_at(l.wqkv + slot * D * D * 2, D * D, P_BF16);
-            t.add_at(l.bqkv + slot * D * 4, D, P_F32);
-        }
-        l.wo = put(D * D, P_BF16);
-        l.bo = put(D, P_F32);
-        l.ln1g = put(D, P_F32);
-        l.ln1b = put(D, P_F32);
-        l.w1 = put(F * D, P_BF16);
-        l.b1 = put(F, P_F32);
-        l.w2 = put(D * F, P_BF16);
-        l.b2 = put(D, P_F32);
-        l.ln2g = put(D, P_F32);
-        l.ln2b = put(D, P_F32);
-        m.layers.push_back(l);
-    }
+    for (int i = 0; i < c.layers; ++i) m.layers.push_back(clip_enc_add_layer(t, D, c.ffn));
     m.postg = put(D, P_F32);
     m.postb = put(D, P_F32);
     m.proj = put((long)c.proj_dim * D, P_F32);
@@ -271,7 +249,9 @@ __global__ __launch_bounds__(256) void pad_patch_rows_kernel(const bf16_t* __res
 }
 
 struct VWs {
-    size_t x, e, pe, rows, h, qkv, att, f, tok0, pool, total;
+    size_t x, e, pe, rows;
+    ClipEncWs enc;
+    size_t tok0, pool, total;
 };
 VWs plan_clipv_ws(const uspace_clipv_config& c, int B) {
     VWs w;
@@ -281,21 +261,11 @@ VWs plan_clipv_ws(const uspace_clipv_config& c, int B) {
     w.e = a.take(M * D * 4);
     w.pe = a.take((size_t)B * N * D * 4);
     w.rows = a.take((size_t)B * N * patch_kp(c) * 2);
-    w.h = a.take(M * D * 2);
-    w.qkv = a.take(M * 3 * D * 2);
-    w.att = a.take(M * D * 2);
-    w.f = a.take(M * (size_t)c.ffn * 2);
+    w.enc = clip_enc_take_ws(a, M, D, (size_t)c.ffn);
     w.tok0 = a.take((size_t)B * D * 4);
     w.pool = a.take((size_t)B * D * 4);
     w.total = a.off;
     return w;
-}
-
-// the resident kernel where its plan accepts the shape, the streaming one beyond (as uvit.hip's attention())
-int attention_any(const uint16_t* qkv, uint16_t* out, int B, int L, int H, uspace_stream_t stream) {
-    int plan[8];
-    if (uspace_attention_plan(B, L, H, 0, plan) == USPACE_OK) return uspace_attention_bf16(qkv, nullptr, out, B, L, H, stream);
-    return uspace_attention_long_bf16(qkv, nullptr, out, B, L, H, stream);
 }
 
 }  // namespace
@@ -346,46 +316,31 @@ extern "C" int uspace_clipv_forward(const uspace_clipv_config* cfg, const void* 
     const char* wb = (const char*)blob;
     char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
-    const int D = cfg->dim, F = cfg->ffn, H = cfg->heads, G = cfg->image / cfg->patch, N = G * G, T = N + 1, M = B * T;
+    const int D = cfg->dim, G = cfg->image / cfg->patch, N = G * G, T = N + 1, M = B * T;
     const int K = patch_k(*cfg), Kp = patch_kp(*cfg);
     float* x = (float*)(ws + w.x);
     float* e = (float*)(ws + w.e);
     float* pe = (float*)(ws + w.pe);
     uint16_t* rows = (uint16_t*)(ws + w.rows);
-    uint16_t* h = (uint16_t*)(ws + w.h);
-    uint16_t* qkv = (uint16_t*)(ws + w.qkv);
-    uint16_t* att = (uint16_t*)(ws + w.att);
-    uint16_t* f = (uint16_t*)(ws + w.f);
     float* tok0 = (float*)(ws + w.tok0);
     float* pool = pooler_output ? pooler_output : (float*)(ws + w.pool);
     auto PF = [&](size_t off) { return (const float*)(wb + off); };
     auto PH = [&](size_t off) { return (const uint16_t*)(wb + off); };
-    constexpr int B_ = USPACE_EPI_BIAS, R_ = USPACE_EPI_RESIDUAL, F_ = USPACE_EPI_OUT_F32, H_ = USPACE_EPI_OUT_BF16;
     auto dump = [&](const float* src) {
         return hipMemcpyAsync(tap_out, src, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s) == hipSuccess ? USPACE_OK : USPACE_ERR_LAUNCH;
     };
 
     hipLaunchKernelGGL(patch_rows_kernel, dim3(B * N), dim3(256), 0, s, pixel_values, rows, cfg->image, cfg->patch, G, K, Kp);
     US_CHECK_LAUNCH();
-    US_TRY(uspace_gemm_bf16(rows, Kp, nullptr, 0, Kp, PH(m.patch), Kp, B * N, D, Kp, F_, nullptr, nullptr, 0, pe, D, nullptr, 0, stream));
+    US_TRY(uspace_gemm_bf16(rows, Kp, nullptr, 0, Kp, PH(m.patch), Kp, B * N, D, Kp, USPACE_EPI_OUT_F32, nullptr, nullptr, 0, pe, D,
+                            nullptr, 0, stream));
     hipLaunchKernelGGL(assemble_tokens_kernel, dim3(M), dim3(256), 0, s, pe, PF(m.cls), PF(m.pos), e, T, D);
     US_CHECK_LAUNCH();
     // stop_after_layer: -1 = the whole model; -2 = the embeddings before pre_layrnorm; k >= 0 = the hidden state after k layers
     if (stop_after_layer == -2) return dump(e);
     US_TRY(uspace_layernorm_f32(e, PF(m.preg), PF(m.preb), x, M, D, cfg->eps, stream));
-    const int n_layers = stop_after_layer < 0 ? cfg->layers : (stop_after_layer < cfg->layers ? stop_after_layer : cfg->layers);
-    for (int i = 0; i < n_layers; ++i) {
-        const VLayer& l = m.layers[i];
-        US_TRY(uspace_layernorm_f32_bf16(x, PF(l.ln1g), PF(l.ln1b), h, M, D, cfg->eps, stream));
-        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(l.wqkv), D, M, 3 * D, D, B_ | H_, PF(l.bqkv), nullptr, 0, nullptr, 0, qkv,
-                                3 * D, stream));
-        US_TRY(attention_any(qkv, att, B, T, H, stream));
-        US_TRY(uspace_gemm_bf16(att, D, nullptr, 0, D, PH(l.wo), D, M, D, D, B_ | R_ | F_, PF(l.bo), x, D, x, D, nullptr, 0, stream));
-        US_TRY(uspace_layernorm_f32_bf16(x, PF(l.ln2g), PF(l.ln2b), h, M, D, cfg->eps, stream));
-        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(l.w1), D, M, F, D, B_ | H_, PF(l.b1), nullptr, 0, nullptr, 0, f, F, stream));
-        US_TRY(uspace_quick_gelu_bf16(f, (long)M * F, stream));
-        US_TRY(uspace_gemm_bf16(f, F, nullptr, 0, F, PH(l.w2), F, M, D, F, B_ | R_ | F_, PF(l.b2), x, D, x, D, nullptr, 0, stream));
-    }
+    US_TRY(clip_enc_layers(m.layers, stop_after_layer, blob, workspace, w.enc, x, B, T, D, cfg->ffn, cfg->heads, cfg->eps, false,
+                           stream));
     if (tap) return dump(x);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, s, x, (const int*)nullptr, tok0, T, D);
     US_CHECK_LAUNCH();

@@ -212,14 +212,6 @@ extern "C" int uspace_uvit_set_ln_fold(int mode) {
 extern "C" int uspace_uvit_get_ln_fold(void) { return g_ln_fold.load(); }
 
 namespace {
-// The attention of a block: the resident kernel wherever its plan takes the length (att_plan of attention.hip is the one place that
-// knows the limit), the streaming kernel of attention_long.hip beyond
-int attention(const uint16_t* qkv, const float* ks, uint16_t* out, int B, int L, int H, uspace_stream_t stream) {
-    int plan[8];
-    if (uspace_attention_plan(B, L, H, ks != nullptr, plan) == USPACE_OK) return uspace_attention_bf16(qkv, ks, out, B, L, H, stream);
-    return uspace_attention_long_bf16(qkv, ks, out, B, L, H, stream);
-}
-
 // The forward; stop_after >= 0 (uspace_uvit_forward_tap) copies the residual stream x to `dump` after stage stop_after and
 // returns there (the last stage, depth + 1, runs the head first).  stop_after = -1 is the product forward: the launch sequence
 // is the same for every stop_after up to the stop.  maps != NULL (uspace_uvit_forward_maps): one more launch per block, the head-mean
@@ -376,7 +368,7 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
                                     nullptr, 0, qkv, 3 * D, &cons, sk_on, stream));
             if (maps) US_TRY(uspace_attention_map_bf16(qkv, maps + (size_t)i * map_stride, B, L, H, mw.q0, mw.nq, mw.k0, mw.nk, stream));
             const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
-            US_TRY(attention(qkv, ks, h, B, L, H, stream));
+            US_TRY(us_attention_any(qkv, ks, h, B, L, H, stream));
             US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, C_ | B_ | R_ | F_, PF(b.projb), x, D, x, D,
                                     nullptr, 0, sk_ptr(prod), sk_on, stream));
             np = slots_proj;
@@ -428,7 +420,7 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
                                 qkv, 3 * D, nullptr, sk_on, stream));
         if (maps) US_TRY(uspace_attention_map_bf16(qkv, maps + (size_t)i * map_stride, B, L, H, mw.q0, mw.nq, mw.k0, mw.nk, stream));
         const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
-        US_TRY(attention(qkv, ks, h, B, L, H, stream));
+        US_TRY(us_attention_any(qkv, ks, h, B, L, H, stream));
         US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, B_ | R_ | F_, PF(b.projb), x, D, x, D,
                                 nullptr, 0, sk_ptr(plain), sk_on, stream));
         // x += fc2(gelu(fc1(norm2(x))))

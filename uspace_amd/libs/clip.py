@@ -69,16 +69,68 @@ def _norm(group, name, n):
     c.add("bias", n)
 
 
-class CLIPTextTransformer(nn.Module):
+def _encoder_layers(n, hidden_size, intermediate_size):
+    """The ``ModuleList`` of ``n`` HF CLIPEncoderLayer parameter groups (the same in both towers), in state_dict order."""
+    layers = []
+    for _ in range(n):
+        lyr = ParamGroup()
+        att = lyr.child("self_attn")
+        for name in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            _linear(att, name, hidden_size, hidden_size)
+        _norm(lyr, "layer_norm1", hidden_size)
+        mlp = lyr.child("mlp")
+        _linear(mlp, "fc1", intermediate_size, hidden_size)
+        _linear(mlp, "fc2", hidden_size, intermediate_size)
+        _norm(lyr, "layer_norm2", hidden_size)
+        layers.append(lyr)
+    return nn.ModuleList(layers)
+
+
+class _CLIPTower(nn.Module):
+    """What the two towers share on the host: the checks of the encoder's shape, HF's initialisation, the packed blob and the
+    workspace cache.  A subclass names its library symbols (``_SYMBOLS``), itself (``_DISPLAY``, ``_WHICH``) and supplies
+    ``_c_cfg()``; its constructor builds the parameters between ``super().__init__(...)`` and ``self._finish_init()``."""
+    _SYMBOLS = _DISPLAY = _WHICH = None
+
+    def __init__(self, hidden_act, hidden_size, num_attention_heads, intermediate_size):
+        super().__init__()
+        if hidden_act != "quick_gelu":
+            raise NotImplementedError(f"hidden_act={hidden_act!r}: {self._WHICH} uses quick_gelu")
+        if hidden_size != 64 * num_attention_heads or hidden_size % 64 or intermediate_size % 64:
+            raise NotImplementedError("head_dim must be 64 and the widths multiples of 64")
+
+    def _finish_init(self):
+        with torch.no_grad():                                  # HF _init_weights: normal tables / projections, unit norms
+            for name, prm in self.named_parameters():
+                if "norm" in name and name.endswith("weight"):
+                    prm.fill_(1.0)
+                elif name.endswith("bias"):
+                    prm.zero_()
+                else:
+                    prm.normal_(0.0, 0.02)
+        self._packed = PackedWeights(self._SYMBOLS, self._DISPLAY, self._canonical_params, self._c_cfg())
+        self._ws = WorkspaceCache(1)
+        self.eval()
+        self.requires_grad_(False)
+
+    def invalidate_packed(self):
+        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
+        self._packed.invalidate()
+
+    def _canonical_params(self):
+        return list(self.parameters())
+
+    def _packed_blob(self, device):
+        return self._packed.blob(device)
+
+
+class CLIPTextTransformer(_CLIPTower):
     """HF CLIPTextModel's computation given token ids; parameters in the HF state_dict order and naming."""
+    _SYMBOLS, _DISPLAY, _WHICH = "uspace_clip_", "CLIP", "the CLIP text encoder the reference loads"
 
     def __init__(self, vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
                  num_attention_heads=12, max_position_embeddings=77, layer_norm_eps=1e-5, hidden_act="quick_gelu", **_ignored):
-        super().__init__()
-        if hidden_act != "quick_gelu":
-            raise NotImplementedError(f"hidden_act={hidden_act!r}: the CLIP text encoder the reference loads uses quick_gelu")
-        if hidden_size != 64 * num_attention_heads or hidden_size % 64 or intermediate_size % 64:
-            raise NotImplementedError("head_dim must be 64 and the widths multiples of 64")
+        super().__init__(hidden_act, hidden_size, num_attention_heads, intermediate_size)
         self.cfg = dict(vocab=vocab_size, dim=hidden_size, heads=num_attention_heads, layers=num_hidden_layers,
                         ffn=intermediate_size, max_pos=max_position_embeddings, eps=layer_norm_eps)
         emb = ParamGroup()
@@ -86,35 +138,12 @@ class CLIPTextTransformer(nn.Module):
         emb.child("position_embedding").add("weight", max_position_embeddings, hidden_size)
         self.embeddings = emb
         enc = ParamGroup()
-        layers = []
-        for _ in range(num_hidden_layers):
-            lyr = ParamGroup()
-            att = lyr.child("self_attn")
-            for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-                _linear(att, n, hidden_size, hidden_size)
-            _norm(lyr, "layer_norm1", hidden_size)
-            mlp = lyr.child("mlp")
-            _linear(mlp, "fc1", intermediate_size, hidden_size)
-            _linear(mlp, "fc2", hidden_size, intermediate_size)
-            _norm(lyr, "layer_norm2", hidden_size)
-            layers.append(lyr)
-        enc.add_module("layers", nn.ModuleList(layers))
+        enc.add_module("layers", _encoder_layers(num_hidden_layers, hidden_size, intermediate_size))
         self.encoder = enc
         self.final_layer_norm = ParamGroup()
         self.final_layer_norm.add("weight", hidden_size)
         self.final_layer_norm.add("bias", hidden_size)
-        with torch.no_grad():                                  # HF _init_weights: normal tables / projections, unit norms
-            for name, prm in self.named_parameters():
-                if name.endswith("norm.weight") or "layer_norm" in name and name.endswith("weight"):
-                    prm.fill_(1.0)
-                elif name.endswith("bias"):
-                    prm.zero_()
-                else:
-                    prm.normal_(0.0, 0.02)
-        self._packed = PackedWeights("uspace_clip_", "CLIP", self._canonical_params, self._c_cfg())
-        self._ws = WorkspaceCache(1)
-        self.eval()
-        self.requires_grad_(False)
+        self._finish_init()
 
     def load_state_dict(self, state_dict, strict=True):
         """Accepts HF CLIPTextModel / CLIPModel checkpoints: an optional ``text_model.`` prefix is stripped,
@@ -131,16 +160,6 @@ class CLIPTextTransformer(nn.Module):
     def _c_cfg(self):
         c = self.cfg
         return _hip.ClipConfig(c["vocab"], c["dim"], c["heads"], c["layers"], c["ffn"], c["max_pos"], c["eps"])
-
-    def invalidate_packed(self):
-        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
-        self._packed.invalidate()
-
-    def _canonical_params(self):
-        return list(self.parameters())
-
-    def _packed_blob(self, device):
-        return self._packed.blob(device)
 
     def forward(self, input_ids, hidden_state=None):
         """input_ids [B, L<=max_pos] integer tensor -> last_hidden_state [B, L, D] fp32 (``hidden_state=k``: the state
@@ -172,18 +191,15 @@ CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)                                 
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
-class CLIPVisionTransformer(nn.Module):
+class CLIPVisionTransformer(_CLIPTower):
     """HF CLIPVisionModelWithProjection's computation (``image_embeds``) in libuspace_hip.so (``uspace_clipv_forward``), with the
     image preprocessing of ``uspace_clip_preprocess`` in front of it; parameters in the HF state_dict order and naming
     (``vision_model.*``, ``visual_projection.weight``)."""
+    _SYMBOLS, _DISPLAY, _WHICH = "uspace_clipv_", "CLIP vision", "the CLIP vision tower of openai/clip-vit-large-patch14"
 
     def __init__(self, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224,
                  patch_size=14, projection_dim=768, layer_norm_eps=1e-5, hidden_act="quick_gelu", num_channels=3, **_ignored):
-        super().__init__()
-        if hidden_act != "quick_gelu":
-            raise NotImplementedError(f"hidden_act={hidden_act!r}: the CLIP vision tower of openai/clip-vit-large-patch14 uses quick_gelu")
-        if hidden_size != 64 * num_attention_heads or hidden_size % 64 or intermediate_size % 64:
-            raise NotImplementedError("head_dim must be 64 and the widths multiples of 64")
+        super().__init__(hidden_act, hidden_size, num_attention_heads, intermediate_size)
         if num_channels != 3 or image_size % patch_size or projection_dim % 4:
             raise NotImplementedError("3 channels, image_size a multiple of patch_size and projection_dim a multiple of 4")
         self.cfg = dict(image=image_size, patch=patch_size, dim=hidden_size, heads=num_attention_heads, layers=num_hidden_layers,
@@ -195,36 +211,12 @@ class CLIPVisionTransformer(nn.Module):
         emb.child("patch_embedding").add("weight", hidden_size, 3, patch_size, patch_size)
         emb.child("position_embedding").add("weight", self.tokens, hidden_size)
         _norm(vm, "pre_layrnorm", hidden_size)                 # HF's spelling
-        enc = vm.child("encoder")
-        layers = []
-        for _ in range(num_hidden_layers):
-            lyr = ParamGroup()
-            att = lyr.child("self_attn")
-            for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-                _linear(att, n, hidden_size, hidden_size)
-            _norm(lyr, "layer_norm1", hidden_size)
-            mlp = lyr.child("mlp")
-            _linear(mlp, "fc1", intermediate_size, hidden_size)
-            _linear(mlp, "fc2", hidden_size, intermediate_size)
-            _norm(lyr, "layer_norm2", hidden_size)
-            layers.append(lyr)
-        enc.add_module("layers", nn.ModuleList(layers))
+        vm.child("encoder").add_module("layers", _encoder_layers(num_hidden_layers, hidden_size, intermediate_size))
         _norm(vm, "post_layernorm", hidden_size)
         self.vision_model = vm
         self.visual_projection = ParamGroup()
         self.visual_projection.add("weight", projection_dim, hidden_size)
-        with torch.no_grad():
-            for name, prm in self.named_parameters():
-                if ("norm" in name) and name.endswith("weight"):
-                    prm.fill_(1.0)
-                elif name.endswith("bias"):
-                    prm.zero_()
-                else:
-                    prm.normal_(0.0, 0.02)
-        self._packed = PackedWeights("uspace_clipv_", "CLIP vision", self._canonical_params, self._c_cfg())
-        self._ws = WorkspaceCache(1)
-        self.eval()
-        self.requires_grad_(False)
+        self._finish_init()
 
     def load_state_dict(self, state_dict, strict=True):
         """Accepts HF CLIPModel / CLIPVisionModel / CLIPVisionModelWithProjection checkpoints, with or without the
@@ -241,16 +233,6 @@ class CLIPVisionTransformer(nn.Module):
     def _c_cfg(self):
         c = self.cfg
         return _hip.ClipVisionConfig(c["image"], c["patch"], c["dim"], c["heads"], c["layers"], c["ffn"], c["proj_dim"], c["eps"])
-
-    def invalidate_packed(self):
-        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
-        self._packed.invalidate()
-
-    def _canonical_params(self):
-        return list(self.parameters())
-
-    def _packed_blob(self, device):
-        return self._packed.blob(device)
 
     def preprocess(self, images, quantize=True, mean=CLIP_MEAN, std=CLIP_STD):
         """images [B, 3, H, H] fp32 in [0, 1] on the device -> pixel_values [B, 3, image_size, image_size]: ``save_image``'s
