@@ -591,6 +591,38 @@ USPACE_API int uspace_cosine_f32(const float* a, const float* b, float* out, int
 USPACE_API int uspace_normalized_diff_f32(const float* a, const float* b, float* out, int B, int D, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Feature-set metrics (KID, precision / recall / density / coverage; uspace_amd/tools/feature_metrics.py): reductions over
+ * the pairwise quantities of two fp32 row-major feature sets x [nx, F] and y [ny, F] on the device, F >= 1, n, nx, ny <= 2^24.
+ * Everything is fp64: the dot product x_i . y_j by v_mfma_f64_16x16x4_f64 over the fp32 values widened to fp64, and
+ *   D2(i, j) = max(0, |x_i|^2 + |y_j|^2 - 2 x_i . y_j),
+ * the squared norms computed once per call and set by one fixed-order kernel.  The nx x ny matrix is never stored: a workgroup
+ * owns 64 rows and walks the column tiles, the reductions fused.  No floating-point atomics: every output is bit-equal from
+ * run to run.  workspace: uspace_metric_workspace_bytes(nx, ny, n_subsets, m) bytes (norms of both sets + the partial sums of
+ * uspace_metric_poly_sums; pass ny = 0 for uspace_metric_knn_radius2, n_subsets = m = 0 where no sums are asked for); 0 on
+ * invalid arguments.  The layout is one formula for all three consumers, norms first: uspace_metric_poly_sums computes no norms and
+ * leaves those (nx + ny) doubles untouched ahead of its partial sums (128 MiB per 2^24-row set, allocated and unused).
+ * Nothing of the workspace is read before it is written.  These functions were added without a change
+ * of USPACE_ABI_VERSION: they only add symbols.
+ * ------------------------------------------------------------------------------------- */
+USPACE_API size_t uspace_metric_workspace_bytes(int nx, int ny, int n_subsets, int m);
+/* radius2[i] = the k-th smallest D2(i, j) over j != i (excluded by index) within one set x [n, F]; 1 <= k <= 16, k <= n - 1,
+ * otherwise USPACE_ERR_ARG.  A sorted list of the k smallest per row is merged tile by tile. */
+USPACE_API int uspace_metric_knn_radius2(const float* x, int n, int F, int k, double* radius2, void* workspace,
+                                         size_t workspace_bytes, uspace_stream_t stream);
+/* count[i] = #{j : D2(i, j) <= radius2_y[j]} (int32 [nx]; needs radius2_y fp64 [ny]) and min_d2[i] = min_j D2(i, j) (fp64 [nx]).
+ * Either output may be NULL, not both. */
+USPACE_API int uspace_metric_manifold(const float* x, int nx, const float* y, int ny, int F, const double* radius2_y, int* count,
+                                      double* min_d2, void* workspace, size_t workspace_bytes, uspace_stream_t stream);
+/* With K(a, b) = (gamma a . b + coef0)^degree, degree an integer in 1 .. 8 applied by multiplication, and idx_x, idx_y device
+ * int32 [n_subsets, m] row indices into x and y (the caller validates them; 1 <= m <= min(nx, ny), n_subsets <= 65535):
+ *   sums[s, 0] = sum_{p != q} K(x[idx_x[s, p]], x[idx_x[s, q]]),   sums[s, 1] = the same for y and idx_y,
+ *   sums[s, 2] = sum_{p, q} K(x[idx_x[s, p]], y[idx_y[s, q]]);     sums: fp64 [n_subsets, 3].
+ * The diagonal is excluded by position p == q.  Per-workgroup partial sums are finished in a fixed order. */
+USPACE_API int uspace_metric_poly_sums(const float* x, int nx, const float* y, int ny, int F, const int* idx_x, const int* idx_y,
+                                       int n_subsets, int m, int degree, double gamma, double coef0, double* sums, void* workspace,
+                                       size_t workspace_bytes, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

@@ -65,6 +65,7 @@ class GemmExt(ctypes.Structure):
 
 
 _P, _I, _L, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_size_t
+_D = ctypes.c_double
 
 # name -> (restype, argtypes); must list every symbol include/uspace_hip.h declares
 SIGNATURES = {
@@ -164,6 +165,10 @@ SIGNATURES = {
     "uspace_gather_rows_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "uspace_cosine_f32": (_I, [_P, _P, _P, _I, _I, _F, _I, _P]),
     "uspace_normalized_diff_f32": (_I, [_P, _P, _P, _I, _I, _P]),
+    "uspace_metric_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "uspace_metric_knn_radius2": (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "uspace_metric_manifold": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "uspace_metric_poly_sums": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _D, _D, _P, _P, _SZ, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),
@@ -416,6 +421,79 @@ def ode_error_norm(y0, y1, ks, coefs, rtol, atol, scratch, result):
     check(lib().uspace_ode_error_norm(ptr(y0), ptr(y1), karr, carr, n, float(rtol), float(atol), y0.numel(),
                                       ptr(scratch), ptr(result), stream_ptr()), "uspace_ode_error_norm")
     return result
+
+
+def _metric_features(t, name):
+    require_device(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape[0] < 1 or t.shape[1] < 1:
+        raise UspaceHipError(f"{name} must be a contiguous fp32 [n, F] tensor with n, F >= 1, got {t.dtype} {tuple(t.shape)}")
+
+
+def metric_workspace(nx, ny=0, n_subsets=0, m=0, device=None, fill=None):
+    """A uint8 workspace tensor of ``uspace_metric_workspace_bytes(nx, ny, n_subsets, m)`` bytes (``fill``: a byte value to set it
+    to; the kernels read nothing of it that they have not written)."""
+    nbytes = lib().uspace_metric_workspace_bytes(int(nx), int(ny), int(n_subsets), int(m))
+    if nbytes == 0:
+        raise UspaceHipError(f"uspace_metric_workspace_bytes({nx}, {ny}, {n_subsets}, {m}): invalid sizes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if fill is not None:
+        ws.fill_(fill)
+    return ws
+
+
+def metric_knn_radius2(x, k, ws=None):
+    """fp64 [n]: the k-th smallest squared distance of every row of ``x`` (fp32 [n, F]) to the other rows, self excluded by index."""
+    _metric_features(x, "x")
+    n, F = x.shape
+    if ws is None:
+        ws = metric_workspace(n, device=x.device)
+    out = torch.empty(n, dtype=torch.float64, device=x.device)
+    check(lib().uspace_metric_knn_radius2(ptr(x), n, F, int(k), ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+          "uspace_metric_knn_radius2")
+    return out
+
+
+def metric_manifold(x, y, radius2_y=None, *, want_count=True, want_min=True, ws=None):
+    """(count int32 [nx] or None, min_d2 fp64 [nx] or None) of the rows of ``x`` against the set ``y``: count[i] = the number of j
+    with D2(i, j) <= radius2_y[j], min_d2[i] = min_j D2(i, j)."""
+    _metric_features(x, "x")
+    _metric_features(y, "y")
+    if x.shape[1] != y.shape[1]:
+        raise UspaceHipError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    nx, F = x.shape
+    ny = y.shape[0]
+    if radius2_y is not None:
+        require_device(radius2_y, "radius2_y")
+        if radius2_y.dtype != torch.float64 or radius2_y.numel() != ny or not radius2_y.is_contiguous():
+            raise UspaceHipError(f"radius2_y must be a contiguous fp64 tensor of {ny} entries")
+    if ws is None:
+        ws = metric_workspace(nx, ny, device=x.device)
+    count = torch.empty(nx, dtype=torch.int32, device=x.device) if want_count else None
+    min_d2 = torch.empty(nx, dtype=torch.float64, device=x.device) if want_min else None
+    check(lib().uspace_metric_manifold(ptr(x), nx, ptr(y), ny, F, ptr(radius2_y), ptr(count), ptr(min_d2), ptr(ws), ws.numel(),
+                                       stream_ptr()), "uspace_metric_manifold")
+    return count, min_d2
+
+
+def metric_poly_sums(x, y, idx_x, idx_y, degree, gamma, coef0, ws=None):
+    """fp64 [n_subsets, 3]: the sums of (gamma a.b + coef0)^degree over the pairs of every subset -- x with x and y with y without
+    the positions p == q, x with y over all.  idx_x, idx_y: device int32 [n_subsets, m], validated by the caller."""
+    _metric_features(x, "x")
+    _metric_features(y, "y")
+    if x.shape[1] != y.shape[1]:
+        raise UspaceHipError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    for t, name in ((idx_x, "idx_x"), (idx_y, "idx_y")):
+        require_device(t, name)
+        if t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous() or t.shape != idx_x.shape:
+            raise UspaceHipError(f"{name} must be a contiguous int32 [n_subsets, m] tensor, got {t.dtype} {tuple(t.shape)}")
+    n_subsets, m = idx_x.shape
+    if ws is None:
+        ws = metric_workspace(x.shape[0], y.shape[0], n_subsets, m, device=x.device)
+    sums = torch.empty(n_subsets, 3, dtype=torch.float64, device=x.device)
+    check(lib().uspace_metric_poly_sums(ptr(x), x.shape[0], ptr(y), y.shape[0], x.shape[1], ptr(idx_x), ptr(idx_y), n_subsets, m,
+                                        int(degree), float(gamma), float(coef0), ptr(sums), ptr(ws), ws.numel(), stream_ptr()),
+          "uspace_metric_poly_sums")
+    return sums
 
 
 def prof_gemm_begin(epi_flags, N, K, max_launches=8192):
