@@ -623,6 +623,35 @@ USPACE_API int uspace_metric_poly_sums(const float* x, int nx, const float* y, i
                                        size_t workspace_bytes, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Inception Score and sFID (uspace_amd/tools/inception_score.py, sfid_score.py, eval_suite.py): the pool features, the
+ * spatial features and the logits from ONE walk of the network, and the fp64 statistics of the score.  These are the numbers
+ * of the pytorch-fid port of the network, not of the TF graph.  Added without a change of USPACE_ABI_VERSION: symbols only.
+ * ------------------------------------------------------------------------------------- */
+/* uspace_inception_forward(last_block = 3) with one addition: right after tap stage `spatial_stage` (1 .. 18, numbered as in
+ * uspace_inception_tap) is complete, channels [0, spatial_channels) of every pixel are gathered to
+ * spatial [B, h * w * spatial_channels] in (h, w, c) order.  sFID's features are stage 14 (Mixed_6d), 7 channels: the first 7
+ * of Mixed_6d.branch1x1 after BN and ReLU, 17 * 17 * 7 = 2023 values per image.  pool [B, 2048] and the workspace
+ * (uspace_inception_workspace_bytes) are those of uspace_inception_forward, bit for bit; spatial == NULL skips the gather.
+ * spatial_stage outside 1 .. 18 or spatial_channels outside 1 .. the stage's channels: USPACE_ERR_ARG, checked either way. */
+USPACE_API int uspace_inception_forward_suite(const void* blob, void* workspace, size_t workspace_bytes, const float* x, int B,
+                                              int H, int W, float* pool, float* spatial, int spatial_stage, int spatial_channels,
+                                              uspace_stream_t stream);
+/* logits [B, C] = pool [B, K] . weight [C, K]^T (+ bias [C] unless NULL), no activation: torchvision's fc.  fp32 operands on
+ * v_mfma_f32_32x32x2_f32: each logit is the k-ordered fp32 fma chain over K, so a row's logits are bit-identical whatever B it
+ * sits in.  Any B >= 1 and C >= 1; K % 16 == 0 and 16-byte aligned pool and weight, anything else USPACE_ERR_ARG.  Plain fp32
+ * device tensors, no blob. */
+USPACE_API int uspace_inception_logits(const float* pool, const float* weight, const float* bias, float* logits, int B, int K,
+                                       int C, uspace_stream_t stream);
+/* scores[k] (fp64 [splits], device) = exp(mean_i sum_c p_ic (log p_ic - log pbar_c)) over the rows i of split k =
+ * [k N / splits, (k + 1) N / splits) (integer division), p_i = softmax(logits_i), pbar = the split's mean of p_i; terms with
+ * p_ic == 0 contribute 0.  logits fp32 [N, C]; all arithmetic fp64; every sum in a fixed order, no atomics: bit-equal from run to
+ * run.  1 <= splits <= N <= 2^24, C <= 65536, splits * ceil(ceil(N / splits) / 256) <= 65535; otherwise USPACE_ERR_ARG / 0 bytes.
+ * Nothing of the workspace is read before it is written. */
+USPACE_API size_t uspace_inception_score_workspace_bytes(int N, int C, int splits);
+USPACE_API int uspace_inception_score_f64(const float* logits, int N, int C, int splits, void* workspace, size_t workspace_bytes,
+                                          double* scores, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

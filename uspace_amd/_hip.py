@@ -169,6 +169,10 @@ SIGNATURES = {
     "uspace_metric_knn_radius2": (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
     "uspace_metric_manifold": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "uspace_metric_poly_sums": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _D, _D, _P, _P, _SZ, _P]),
+    "uspace_inception_forward_suite": (_I, [_P, _P, _SZ, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
+    "uspace_inception_logits": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "uspace_inception_score_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "uspace_inception_score_f64": (_I, [_P, _I, _I, _I, _P, _SZ, _P, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),
@@ -494,6 +498,41 @@ def metric_poly_sums(x, y, idx_x, idx_y, degree, gamma, coef0, ws=None):
                                         int(degree), float(gamma), float(coef0), ptr(sums), ptr(ws), ws.numel(), stream_ptr()),
           "uspace_metric_poly_sums")
     return sums
+
+
+def inception_logits(pool, weight, bias=None):
+    """fp32 [B, C] = pool [B, K] @ weight [C, K]^T (+ bias [C]): the k-ordered fp32 fma chain per logit, no activation."""
+    for t, name in ((pool, "pool"), (weight, "weight")) + (((bias, "bias"),) if bias is not None else ()):
+        require_device(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise UspaceHipError(f"{name} must be a contiguous fp32 tensor, got {t.dtype} {tuple(t.shape)}")
+    if pool.dim() != 2 or weight.dim() != 2 or pool.shape[1] != weight.shape[1] or pool.shape[0] < 1:
+        raise UspaceHipError(f"expected pool [B, K] and weight [C, K], got {tuple(pool.shape)} and {tuple(weight.shape)}")
+    B, K = pool.shape
+    C = weight.shape[0]
+    if bias is not None and tuple(bias.shape) != (C,):
+        raise UspaceHipError(f"bias must have {C} entries, got {tuple(bias.shape)}")
+    out = torch.empty(B, C, dtype=torch.float32, device=pool.device)
+    check(lib().uspace_inception_logits(ptr(pool), ptr(weight), ptr(bias), ptr(out), B, K, C, stream_ptr()),
+          "uspace_inception_logits")
+    return out
+
+
+def inception_score_splits(logits, splits, ws=None):
+    """fp64 [splits] on the device: the per-split scores of ``uspace_inception_score_f64`` for fp32 logits [N, C]."""
+    require_device(logits, "logits")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous():
+        raise UspaceHipError(f"logits must be a contiguous fp32 [N, C] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    N, C = logits.shape
+    if ws is None:
+        nbytes = lib().uspace_inception_score_workspace_bytes(N, C, int(splits))
+        if nbytes == 0:
+            raise UspaceHipError(f"uspace_inception_score_workspace_bytes({N}, {C}, {splits}): invalid sizes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+    scores = torch.empty(int(splits), dtype=torch.float64, device=logits.device)
+    check(lib().uspace_inception_score_f64(ptr(logits), N, C, int(splits), ptr(ws), ws.numel(), ptr(scores), stream_ptr()),
+          "uspace_inception_score_f64")
+    return scores
 
 
 def prof_gemm_begin(epi_flags, N, K, max_launches=8192):

@@ -212,6 +212,17 @@ __global__ __launch_bounds__(256) void spatial_mean_kernel(const float* __restri
     feat[idx] = (float)(s / HW);
 }
 
+// ---- channel gather: out[pix, c] = x[pix, c], c < nc, of an NHWC map with C channels (the spatial features of sFID: the
+// first channels of every pixel, flattened in (h, w, c) order per image)
+__global__ __launch_bounds__(256) void gather_channels_kernel(const float* __restrict__ x, float* __restrict__ out, long npix,
+                                                              int C, int nc) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npix * nc) return;
+    const long pix = idx / nc;
+    const int c = (int)(idx - pix * nc);
+    out[idx] = x[pix * C + c];
+}
+
 // ---- implicit-GEMM convolution, fp32 MFMA.  GEMM view: M = B*Ho*Wo output pixels, N = Cout, K = kh*kw*Cin ordered
 // (tap, channel).  Workgroup = 128 x 64 output tile, 4 waves of 64 x 32 (two 32 x 32 accumulators sharing the B
 // operand); K advances 16 at a time through LDS (A as [k][m], B as [k][n]: both MFMA operand reads are 32 consecutive
@@ -575,11 +586,20 @@ int spatial_mean(const Act& a, float* feat, int B, hipStream_t st) {
     return USPACE_OK;
 }
 
+// Channels of every tap stage 0 .. 18, what the walk below produces (tests/test_eval_suite_host.py holds it against the
+// Python side's STAGE_SHAPES): the gather's arguments are checked against it before anything is launched.
+constexpr int kStageChannels[19] = {3, 32, 32, 64, 64, 80, 192, 192, 256, 288, 288, 768, 768, 768, 768, 768, 1280, 2048, 2048};
+
+bool spatial_args_ok(int stage, int channels) { return stage >= 1 && stage <= 18 && channels >= 1 && channels <= kStageChannels[stage]; }
+
 // Runs stages 0 .. last.  With tap_out, copies stage `last` (NHWC, or [B, 2048] for stage 19) there; with feat, writes
-// the spatial mean of stage `last` (4, 7, 15 or 18) to feat [B, C].
+// the spatial mean of stage `last` (4, 7, 15 or 18) to feat [B, C].  With spatial, channels [0, sp_channels) of every pixel
+// of stage sp_stage (1 .. min(last, 18)) are gathered to spatial [B, h * w * sp_channels] as soon as that stage is complete:
+// its buffer is written again two stages later.
 int run(const void* blob, void* ws, size_t ws_bytes, const float* x, int B, int H, int W, int last, float* tap_out,
-        float* feat, hipStream_t st) {
+        float* feat, hipStream_t st, float* spatial = nullptr, int sp_stage = 0, int sp_channels = 0) {
     if (!blob || !ws || !x || B <= 0 || H <= 0 || W <= 0 || last < 0 || last >= kNumStages) return USPACE_ERR_ARG;
+    if (spatial && (!spatial_args_ok(sp_stage, sp_channels) || sp_stage > last)) return USPACE_ERR_ARG;
     // every NHWC tensor (and the input) stays below 2^31 elements
     if ((long)B * kBigPer >= (1L << 31) || (long)B * 3 * H * W >= (1L << 31)) return USPACE_ERR_ARG;
     if (ws_bytes < workspace_bytes_for(B)) return USPACE_ERR_WORKSPACE;
@@ -614,6 +634,12 @@ int run(const void* blob, void* ws, size_t ws_bytes, const float* x, int B, int 
         }
         o.p = y;
         cur = o;
+        if (spatial && stage == sp_stage) {
+            const long npix = (long)B * cur.H * cur.W;
+            hipLaunchKernelGGL(gather_channels_kernel, dim3((unsigned)((npix * sp_channels + 255) / 256)), dim3(256), 0, st, cur.p,
+                               spatial, npix, cur.C, sp_channels);
+            US_CHECK_LAUNCH();
+        }
     }
     if (tap_out) {
         if (last == 19) return spatial_mean(cur, tap_out, B, st);
@@ -672,6 +698,15 @@ extern "C" int uspace_inception_tap(const void* blob, void* workspace, size_t wo
                                     int W, int stage, float* out, uspace_stream_t stream) {
     if (!out) return USPACE_ERR_ARG;
     return run(blob, workspace, workspace_bytes, x, B, H, W, stage, out, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int uspace_inception_forward_suite(const void* blob, void* workspace, size_t workspace_bytes, const float* x, int B,
+                                              int H, int W, float* pool, float* spatial, int spatial_stage, int spatial_channels,
+                                              uspace_stream_t stream) {
+    if (!pool) return USPACE_ERR_ARG;
+    if (!spatial_args_ok(spatial_stage, spatial_channels)) return USPACE_ERR_ARG;      // whether or not the gather is asked for
+    return run(blob, workspace, workspace_bytes, x, B, H, W, 18, nullptr, pool, (hipStream_t)stream, spatial, spatial_stage,
+               spatial_channels);
 }
 
 extern "C" int uspace_fid_stats_accumulate(const float* feat, int B, int F, const double* shift, double* s1, double* s2,

@@ -162,9 +162,12 @@ class FIDStatistics:
     def __init__(self, dims=2048, device=None, model=None):
         if dims not in InceptionV3.BLOCK_INDEX_BY_DIM:
             raise ValueError(f"dims must be one of {sorted(InceptionV3.BLOCK_INDEX_BY_DIM)}")
+        self._setup(dims, _device(device), model, InceptionV3.BLOCK_INDEX_BY_DIM[dims])
+
+    def _setup(self, dims, device, model, block):
         self.dims = dims
-        self.device = _device(device)
-        self.block = InceptionV3.BLOCK_INDEX_BY_DIM[dims]
+        self.device = device
+        self.block = block
         self._model = model
         self.reset()
 

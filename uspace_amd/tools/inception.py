@@ -81,6 +81,10 @@ STAGE_SHAPES = ([(299, 299, 3), (149, 149, 32), (147, 147, 32), (147, 147, 64), 
 # 2 * MACs of the 94 convolutions at 299 x 299 (the FLOP count of one image)
 GFLOP_PER_IMAGE = 11.42
 MAX_CHUNK = 256     # images per launch sequence: every NHWC tensor stays far below 2^31 elements
+# sFID's spatial features: the first SPATIAL_CHANNELS channels of tap stage SPATIAL_STAGE (Mixed_6d), 17 * 17 * 7 = 2023 values
+SPATIAL_STAGE = 14
+SPATIAL_CHANNELS = 7
+NUM_CLASSES = 1008  # rows of fc.weight in the pytorch-fid weight file
 
 
 def state_dict_layout():
@@ -248,6 +252,36 @@ class InceptionV3(nn.Module):
                                               int(stage), _hip.ptr(out[lo:lo + n]), _hip.stream_ptr()), "uspace_inception_tap")
         return out
 
+    @torch.no_grad()
+    def suite(self, inp, spatial=True, spatial_stage=SPATIAL_STAGE, spatial_channels=SPATIAL_CHANNELS, chunk=None):
+        """(pool [B, 2048], spatial [B, h * w * spatial_channels] or None) from ONE walk of the network.
+
+        pool is ``features(inp, 3)`` bit for bit.  spatial is, for image b, ``tap(inp, spatial_stage)[b, :, :, :spatial_channels]``
+        flattened in (h, w, c) order, bit for bit.  With the defaults these are sFID's spatial features: stage 14 is Mixed_6d,
+        whose concatenated output starts with branch1x1, so they are the first 7 channels of Mixed_6d.branch1x1 after BN and
+        ReLU over the 17 x 17 map, 2023 values per image.  That is a reading of ADM's ``mixed_6/conv:0[..., :7]`` (TF's
+        mixed_6 taken to be torchvision's Mixed_6d); it has not been checked against the TF graph, which is why both are
+        parameters.  ``spatial=False`` skips the gather and returns None in its place."""
+        stage, nch = int(spatial_stage), int(spatial_channels)
+        x = self._input(inp)
+        B, _, H, W = x.shape
+        dev = x.device
+        blob = self._blob(dev)
+        pool = torch.empty(B, BLOCK_DIMS[3], dtype=torch.float32, device=dev)
+        if not 1 <= stage <= 18 or not 1 <= nch <= STAGE_SHAPES[stage][2]:      # checked whether or not the gather is asked for
+            raise _hip.UspaceHipError(f"spatial_stage must be in 1 .. 18 and spatial_channels in 1 .. the stage's channels, got "
+                                      f"{spatial_stage} and {spatial_channels}")
+        h, w, _c = STAGE_SHAPES[stage]
+        sp = torch.empty(B, h * w * nch, dtype=torch.float32, device=dev) if spatial else None
+        chunk, parts = self._chunks(B, chunk)
+        ws = self._workspace(chunk, H, W, dev)
+        L = _hip.lib()
+        for lo, n in parts:
+            _hip.check(L.uspace_inception_forward_suite(_hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(x[lo:lo + n]), n, H, W,
+                                                        _hip.ptr(pool[lo:lo + n]), _hip.ptr(sp[lo:lo + n]) if sp is not None else None,
+                                                        stage, nch, _hip.stream_ptr()), "uspace_inception_forward_suite")
+        return pool, sp
+
     def forward(self, inp):
         """List of the selected output blocks, ascending (reference InceptionV3.forward): blocks 0-2 as feature maps
         [B, C, H, W], block 3 as the pooled [B, 2048, 1, 1]."""
@@ -258,6 +292,80 @@ class InceptionV3(nn.Module):
             else:
                 outp.append(self.tap(inp, BLOCK_STAGE[idx]).permute(0, 3, 1, 2))
         return outp
+
+
+class _FC(nn.Module):
+    def __init__(self, k, c):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(c, k))
+        self.bias = nn.Parameter(torch.zeros(c))
+
+
+class InceptionHead(nn.Module):
+    """The classification layer of Inception-v3 (torchvision's ``fc``, 2048 -> 1008 in the pytorch-fid weight file), which
+    ``InceptionV3`` drops: ``logits = pool @ fc.weight.T + fc.bias`` over the 2048-d pool features of block 3, on
+    uspace_inception_logits (fp32 MFMA, a k-ordered fma chain per logit, no activation).
+
+    ``InceptionHead(weights=path_or_None)`` reads ``fc.*`` from the same file as ``InceptionV3`` (``weights=`` or pytorch-fid's
+    cache; never downloaded); ``InceptionHead(num_classes=..., seed=..., std=...)`` makes seeded weights for tests.  The number
+    of classes is taken from the weight.  These are the logits of the pytorch-fid port of the network, not of the TF graph."""
+
+    def __init__(self, weights=None, num_classes=NUM_CLASSES, seed=None, std=None, in_features=BLOCK_DIMS[3]):
+        super().__init__()
+        if seed is not None:
+            g = torch.Generator().manual_seed(int(seed))
+            std = 2.0 / in_features ** 0.5 if std is None else float(std)
+            self.fc = _FC(in_features, int(num_classes))
+            with torch.no_grad():
+                self.fc.weight.copy_(torch.randn(int(num_classes), in_features, generator=g) * std)
+                self.fc.bias.copy_(torch.randn(int(num_classes), generator=g) * 0.5)
+        else:
+            path = weights if weights is not None else default_weights_path()
+            if not os.path.exists(path):
+                raise FileNotFoundError(
+                    f"FID Inception weights not found at {path}: place pytorch-fid's {FID_WEIGHTS_FILE} there (or pass "
+                    "weights=); uspace_amd never downloads")
+            self.fc = _FC(1, 1)
+            self.load_state_dict(torch.load(path, map_location="cpu"))
+        for p in self.parameters():
+            p.requires_grad = False
+
+    @property
+    def num_classes(self):
+        return self.fc.weight.shape[0]
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        """Keeps ``fc.weight`` [C, K] and ``fc.bias`` [C] of a full torchvision / pytorch-fid state dict and ignores every other
+        key.  A dict without ``fc.weight`` or ``fc.bias`` raises KeyError and names the key; a wrong shape raises ValueError."""
+        for k in ("fc.weight", "fc.bias"):
+            if k not in state_dict:
+                raise KeyError(f"Inception head state_dict: missing key {k!r}")
+        w, b = torch.as_tensor(state_dict["fc.weight"]), torch.as_tensor(state_dict["fc.bias"])
+        if w.dim() != 2 or b.dim() != 1 or b.shape[0] != w.shape[0]:
+            raise ValueError(f"Inception head state_dict: fc.weight {tuple(w.shape)} and fc.bias {tuple(b.shape)} do not fit")
+        dev = self.fc.weight.device
+        self.fc = _FC(w.shape[1], w.shape[0]).to(dev)
+        for p in self.fc.parameters():
+            p.requires_grad = False
+        return super().load_state_dict({"fc.weight": w.detach().float(), "fc.bias": b.detach().float()}, strict=True, assign=assign)
+
+    @torch.no_grad()
+    def logits(self, pool, bias=True):
+        """fp32 [B, C] = pool @ fc.weight.T + fc.bias for device pool features [B, 2048].  ``bias=False`` drops the bias
+        (believed to be torch-fidelity's "unbiased logits" convention; unverified, an option and not a parity claim)."""
+        _hip.require_device(pool, "pool features")
+        pool = pool.detach().to(torch.float32).contiguous()
+        if pool.dim() != 2 or pool.shape[1] != self.fc.weight.shape[1]:
+            raise ValueError(f"expected pool features [B, {self.fc.weight.shape[1]}], got {tuple(pool.shape)}")
+        w = self.fc.weight.detach()
+        if w.device != pool.device:
+            raise _hip.UspaceHipError(f"the head lives on {w.device}, the features on {pool.device}: move the head with .to()")
+        if pool.shape[0] == 0:
+            return torch.empty(0, w.shape[0], dtype=torch.float32, device=pool.device)
+        return _hip.inception_logits(pool, w.contiguous(), self.fc.bias.detach().contiguous() if bias else None)
+
+    def forward(self, pool):
+        return self.logits(pool)
 
 
 def fid_inception_v3(weights=None):
