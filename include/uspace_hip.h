@@ -652,6 +652,56 @@ USPACE_API int uspace_inception_score_f64(const float* logits, int N, int C, int
                                           double* scores, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Paired edit-fidelity metrics (uspace_amd/tools/lpips.py, pair_metrics.py; csrc/lpips.hip): LPIPS, SSIM and PSNR of image
+ * pairs, one fp64 value per pair.  Every sum over pixels is fp64 in one fixed order (per-workgroup partial sums over a constant
+ * number of pixels, then one wave per image; no atomics), so a pair's value is bit-identical whatever B it sits in and wherever
+ * it sits in the batch.  Nothing of a workspace is read before it is written.  Added without a change of USPACE_ABI_VERSION:
+ * symbols only.
+ *
+ * LPIPS (Zhang et al. 2018).  net: 0 = AlexNet, 1 = VGG-16 (torchvision's `features`, convolutions with bias, no batch norm);
+ * anything else is USPACE_ERR_ARG (-1 / 0 from the queries).  Parameters, in order: per convolution weight [Cout, Cin, k, k]
+ * then bias [Cout]; then lin0 .. lin4, the per-channel weights [C_l] of the five taps (alex: 64, 192, 384, 256, 256 after the
+ * five ReLUs; vgg: 64, 128, 256, 512, 512 after relu1_2, 2_2, 3_3, 4_3, 5_3).  The pair runs as one batch of 2B images through
+ * the fp32-MFMA convolution the Inception network uses (a k-ordered fp32 fma chain per output); after each tap
+ *   d_l[b] = (1 / HW) sum_pixels sum_c w_c (a_c / (sqrt(sum a^2) + 1e-10) - b_c / (sqrt(sum b^2) + 1e-10))^2
+ * is computed in this direct form, fp32 per pixel, fp64 over pixels.  x0, x1: fp32 NCHW [B, 3, H, W]; the input is
+ * (v - shift_c) / scale_c with v = x (normalize = 0: images in [-1, 1]) or 2 x - 1 (normalize = 1: images in [0, 1]).
+ * An input too small for the stack (alex below 31 x 31, vgg below 16 x 16), B > 32767 or a tensor of 2^31 elements or more:
+ * USPACE_ERR_ARG / 0 bytes.
+ * ------------------------------------------------------------------------------------- */
+USPACE_API int uspace_lpips_num_params(int net);
+USPACE_API long uspace_lpips_param_numel(int net, int index);
+USPACE_API size_t uspace_lpips_weight_bytes(int net);
+USPACE_API size_t uspace_lpips_workspace_bytes(int net, int B, int H, int W);
+USPACE_API int uspace_lpips_pack_weights(int net, const float* const* params, int n_params, void* blob, size_t blob_bytes,
+                                         uspace_stream_t stream);
+/* out fp64 [B] = d_0 + .. + d_4 (summed in this order); per_layer fp64 [5, B] (d_l[b] at l * B + b) or NULL. */
+USPACE_API int uspace_lpips_forward(int net, const void* blob, void* workspace, size_t workspace_bytes, const float* x0,
+                                    const float* x1, int B, int H, int W, int normalize, double* out, double* per_layer,
+                                    uspace_stream_t stream);
+/* Test aid: the NHWC fp32 activations [2B, h, w, c] of tap stage `stage` (x0's images first): 0 = the scaled input,
+ * 1 .. 5 = the five taps.  No head runs. */
+USPACE_API int uspace_lpips_tap(int net, const void* blob, void* workspace, size_t workspace_bytes, const float* x0, const float* x1,
+                                int B, int H, int W, int normalize, int stage, float* dump, uspace_stream_t stream);
+/* The distance head alone: f0, f1 fp32 [B, HW, C] (NHWC), w fp32 [C], out fp64 [B] = d[b] above.  C a multiple of 64 up to 512,
+ * B <= 65535; otherwise USPACE_ERR_ARG / 0 bytes. */
+USPACE_API size_t uspace_lpips_distance_workspace_bytes(int B, int HW, int C);
+USPACE_API int uspace_lpips_distance_f64(const float* f0, const float* f1, const float* w, int B, int HW, int C, void* workspace,
+                                         size_t workspace_bytes, double* out, uspace_stream_t stream);
+/* SSIM (Wang et al. 2004): x, y fp32 NCHW [B, C, H, W]; Gaussian window of 11 taps, sigma 1.5, normalised to sum 1, applied
+ * separably over the "valid" region (H - 10) x (W - 10); population moments per channel; C1 = (0.01 L)^2, C2 = (0.03 L)^2 with
+ * L = data_range; out fp64 [B] = the mean of the SSIM map over positions and channels.  The moments and the map are fp32, the
+ * mean is fp64.  H or W below 11, B or C above 65535, data_range <= 0: USPACE_ERR_ARG / 0 bytes. */
+USPACE_API size_t uspace_ssim_workspace_bytes(int B, int C, int H, int W);
+USPACE_API int uspace_ssim_f64(const float* x, const float* y, int B, int C, int H, int W, double data_range, void* workspace,
+                               size_t workspace_bytes, double* out, uspace_stream_t stream);
+/* PSNR: out fp64 [B] = 10 log10(L^2 / mse), mse = the mean over the n_per_image fp32 values of (x - y)^2, all in fp64;
+ * identical images give +inf. */
+USPACE_API size_t uspace_psnr_workspace_bytes(int B, long n_per_image);
+USPACE_API int uspace_psnr_f64(const float* x, const float* y, int B, long n_per_image, double data_range, void* workspace,
+                               size_t workspace_bytes, double* out, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

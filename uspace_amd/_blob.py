@@ -10,7 +10,8 @@ from . import _hip
 class PackedWeights:
     """The blob of one model (or one half of it), repacked when a tensor changed.  ``prefix``: the library's symbol prefix
     (``"uspace_uvit_"``); ``name``: the model's name in error messages; ``tensors``: callable returning the tensors in the
-    library's canonical order; ``cfg``: the config struct every entry point of the family takes first (None: it takes none)."""
+    library's canonical order; ``cfg``: the config struct every entry point of the family takes first (None: it takes none; an
+    int: the family takes that int first, by value -- ``uspace_lpips_``'s ``net``)."""
 
     def __init__(self, prefix, name, tensors, cfg=None):
         self.prefix, self.name, self.tensors, self.cfg = prefix, name, tensors, cfg
@@ -28,7 +29,7 @@ class PackedWeights:
         if self._held is not None and self._held[0] == device and self._held[1] == versions:
             return self._held[2]
         L = _hip.lib()
-        lead = () if self.cfg is None else (ctypes.byref(self.cfg),)
+        lead = () if self.cfg is None else (self.cfg if isinstance(self.cfg, int) else ctypes.byref(self.cfg),)
         n = getattr(L, self.prefix + "num_params")(*lead)
         if n != len(ts):
             raise _hip.UspaceHipError(f"{self.name} parameter count mismatch: module {len(ts)} vs library {n}")

@@ -173,6 +173,19 @@ SIGNATURES = {
     "uspace_inception_logits": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "uspace_inception_score_workspace_bytes": (_SZ, [_I, _I, _I]),
     "uspace_inception_score_f64": (_I, [_P, _I, _I, _I, _P, _SZ, _P, _P]),
+    "uspace_lpips_num_params": (_I, [_I]),
+    "uspace_lpips_param_numel": (_L, [_I, _I]),
+    "uspace_lpips_weight_bytes": (_SZ, [_I]),
+    "uspace_lpips_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "uspace_lpips_pack_weights": (_I, [_I, ctypes.POINTER(_P), _I, _P, _SZ, _P]),
+    "uspace_lpips_forward": (_I, [_I, _P, _P, _SZ, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "uspace_lpips_tap": (_I, [_I, _P, _P, _SZ, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "uspace_lpips_distance_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "uspace_lpips_distance_f64": (_I, [_P, _P, _P, _I, _I, _I, _P, _SZ, _P, _P]),
+    "uspace_ssim_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "uspace_ssim_f64": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _SZ, _P, _P]),
+    "uspace_psnr_workspace_bytes": (_SZ, [_I, _L]),
+    "uspace_psnr_f64": (_I, [_P, _P, _I, _L, _D, _P, _SZ, _P, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),
