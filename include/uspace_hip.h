@@ -702,6 +702,61 @@ USPACE_API int uspace_psnr_f64(const float* x, const float* y, int B, long n_per
                                size_t workspace_bytes, double* out, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * DINO towers and the structure distance (uspace_amd/libs/dino.py, tools/dino_metrics.py; csrc/dino.hip): Hugging Face
+ * Dinov2Model in eval mode -- class token, patch embedding WITH bias, position table, pre-LN blocks with non-causal attention,
+ * an erf-GELU MLP (the GEMM's USPACE_EPI_GELU epilogue) and LayerScale on both branches, final LayerNorm; pooler_output is the
+ * final LayerNorm of the class token.  layerscale = 0 gives the plain pre-LN ViT of HF ViTModel (DINO v1).  SwiGLU MLPs and
+ * register tokens are not supported.  Added without a change of USPACE_ABI_VERSION: symbols only.
+ * ------------------------------------------------------------------------------------- */
+/* (struct-then-typedef, as uspace_clipv_config; the binding is uspace_amd/_hip.py DinoConfig) */
+struct uspace_dino_config {
+    int image;       /* 224: side of pixel_values, the side the tower runs at; image % patch == 0 */
+    int patch;       /* 14 */
+    int dim;         /* 1024 = heads * 64 */
+    int heads;       /* 16 */
+    int layers;      /* 24 */
+    int ffn;         /* 4096; % 64 == 0 */
+    int layerscale;  /* 1: layer_scale1 / layer_scale2 parameters exist (Dinov2Model); 0: none (ViTModel) */
+    float eps;       /* 1e-6 (ViTModel: 1e-12) */
+};
+typedef struct uspace_dino_config uspace_dino_config;
+
+/* parameter tensors in the order of Dinov2Model.state_dict() with embeddings.mask_token dropped: embeddings.cls_token [dim],
+ * embeddings.position_embeddings [(image / patch)^2 + 1, dim] -- ALREADY interpolated to this config's grid by the caller --,
+ * embeddings.patch_embeddings.projection.{weight [dim, 3, patch, patch], bias}; per layer norm1.{weight,bias},
+ * attention.attention.{query,key,value}.{weight,bias}, attention.output.dense.{weight,bias}, layer_scale1.lambda1, norm2.{weight,bias},
+ * mlp.fc1.{weight,bias}, mlp.fc2.{weight,bias}, layer_scale2.lambda1 (the two lambda1 only with layerscale = 1); then
+ * layernorm.{weight,bias}.  The patch weight is stored bf16 as [dim, Kp], Kp = 3 patch^2 rounded up to 64 with zero columns.
+ * LayerScale is folded at pack time: the stored out projection and fc2 are bf16(lambda1[n] * W[n, k]) and lambda1[n] * b[n],
+ * computed from the fp32 values.  An invalid config gives USPACE_ERR_ARG / 0 bytes. */
+USPACE_API int uspace_dino_num_params(const uspace_dino_config* cfg);
+USPACE_API long uspace_dino_param_numel(const uspace_dino_config* cfg, int index);
+USPACE_API size_t uspace_dino_weight_bytes(const uspace_dino_config* cfg);
+USPACE_API size_t uspace_dino_workspace_bytes(const uspace_dino_config* cfg, int B);
+USPACE_API int uspace_dino_pack_weights(const uspace_dino_config* cfg, const float* const* params, int n_params, void* blob,
+                                        size_t blob_bytes, uspace_stream_t stream);
+/* pixel_values fp32 [B, 3, image, image] -> pooler_output fp32 [B, dim] (may be NULL when only keys are wanted).
+ * stop_after_layer = -1: the whole model.  k >= 0: stop after k layers and write the fp32 residual stream [B, tokens, dim] to
+ * tap_out (HF hidden_states[k]; k = 0 and -2 both give the embeddings: there is no norm in front of the layers); no pooler then.
+ * key_layer = -1: no keys.  l >= 0 (below the number of layers run): the keys of layer l, LN1(x_l) Wk^T + bk with the heads
+ * concatenated, as the q|k|v GEMM stored them: bf16 [B, tokens, dim] to keys_out.  With keys asked for, tap_out may be NULL. */
+USPACE_API int uspace_dino_forward(const uspace_dino_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                   const float* pixel_values, float* pooler_output, int B, int stop_after_layer, float* tap_out,
+                                   int key_layer, uint16_t* keys_out, uspace_stream_t stream);
+/* Structure distance (Tumanyan et al. 2022): for pair p with bf16 keys Ka, Kb [T, D] at keys_x + p * pair_stride, rows row_stride
+ * elements apart,
+ *   S(K)[i, j] = <k_i, k_j> / max(|k_i| |k_j|, 1e-8),   out[p] = (1 / T^2) sum_ij (S(Ka)[i, j] - S(Kb)[i, j])^2     fp64 [P].
+ * Both Gram tiles of a 16 x 16 tile pair by v_mfma_f32_16x16x32_bf16 with fp32 accumulation, the norms fp32 sums of squares of
+ * the same stored keys, the normalisation after the product; one fp32 sum per tile, the tiles of a pair added in a fixed order
+ * in fp64; no atomics, neither T x T matrix stored.  A pair's value is bit-identical from run to run and whatever P it sits in;
+ * identical members give exactly 0.  D % 64 == 0, strides % 8 == 0, 16-byte aligned keys, T <= 16384, P <= 65535; otherwise
+ * USPACE_ERR_ARG / 0 bytes.  Nothing of the workspace is read before it is written. */
+USPACE_API size_t uspace_self_similarity_mse_workspace_bytes(int P, int T);
+USPACE_API int uspace_self_similarity_mse_f64(const uint16_t* keys_a, const uint16_t* keys_b, int P, int T, int D, long row_stride,
+                                              long pair_stride, void* workspace, size_t workspace_bytes, double* out,
+                                              uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

@@ -55,6 +55,11 @@ class ClipVisionConfig(ctypes.Structure):
                 ("layers", ctypes.c_int), ("ffn", ctypes.c_int), ("proj_dim", ctypes.c_int), ("eps", ctypes.c_float)]
 
 
+class DinoConfig(ctypes.Structure):
+    _fields_ = [("image", ctypes.c_int), ("patch", ctypes.c_int), ("dim", ctypes.c_int), ("heads", ctypes.c_int),
+                ("layers", ctypes.c_int), ("ffn", ctypes.c_int), ("layerscale", ctypes.c_int), ("eps", ctypes.c_float)]
+
+
 class GemmExt(ctypes.Structure):
     _fields_ = [("row_c", ctypes.c_void_p), ("out_cen", ctypes.c_void_p), ("ld_cen", ctypes.c_int),
                 ("part_out", ctypes.c_void_p), ("part_in", ctypes.c_void_p), ("np_in", ctypes.c_int),
@@ -186,6 +191,14 @@ SIGNATURES = {
     "uspace_ssim_f64": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _SZ, _P, _P]),
     "uspace_psnr_workspace_bytes": (_SZ, [_I, _L]),
     "uspace_psnr_f64": (_I, [_P, _P, _I, _L, _D, _P, _SZ, _P, _P]),
+    "uspace_dino_num_params": (_I, [ctypes.POINTER(DinoConfig)]),
+    "uspace_dino_param_numel": (_L, [ctypes.POINTER(DinoConfig), _I]),
+    "uspace_dino_weight_bytes": (_SZ, [ctypes.POINTER(DinoConfig)]),
+    "uspace_dino_workspace_bytes": (_SZ, [ctypes.POINTER(DinoConfig), _I]),
+    "uspace_dino_pack_weights": (_I, [ctypes.POINTER(DinoConfig), _P, _I, _P, _SZ, _P]),
+    "uspace_dino_forward": (_I, [ctypes.POINTER(DinoConfig), _P, _P, _SZ, _P, _P, _I, _I, _P, _I, _P, _P]),
+    "uspace_self_similarity_mse_workspace_bytes": (_SZ, [_I, _I]),
+    "uspace_self_similarity_mse_f64": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _SZ, _P, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),

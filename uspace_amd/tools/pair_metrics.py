@@ -63,12 +63,15 @@ def ssim(a, b, data_range=1.0, ws=None):
 
 class PairMetrics:
     """Per-pair LPIPS / SSIM / PSNR accumulated over batches.  ``lpips``: an ``LPIPS`` module (e.g. with seeded weights) or a
-    weight file's path; with neither, ``LPIPS(net)`` needs its weights at first use and says so."""
+    weight file's path; with neither, ``LPIPS(net)`` needs its weights at first use and says so.  ``structure``: a
+    ``DinoVisionTransformer`` (usually ``DINO_B8``) adds a ``structure`` column, ``dino_metrics.structure_distance`` of every
+    pair on that tower's last-layer keys; the default None leaves the three columns as they are."""
 
-    def __init__(self, device=None, lpips=None, net="alex"):
+    def __init__(self, device=None, lpips=None, net="alex", structure=None):
         self.device = _device(device)
         self.net = net
         self._lpips = lpips
+        self._structure = structure
         self.reset()
 
     @property
@@ -79,6 +82,8 @@ class PairMetrics:
 
     def reset(self):
         self._parts = {"lpips": [], "ssim": [], "psnr": []}
+        if self._structure is not None:
+            self._parts["structure"] = []
 
     @property
     def n(self):
@@ -99,9 +104,15 @@ class PairMetrics:
         self._parts["lpips"].append(self.lpips(x, y, normalize=True))
         self._parts["ssim"].append(ssim(x, y, 1.0))
         self._parts["psnr"].append(psnr(x, y, 1.0))
+        if self._structure is not None:
+            from uspace_amd.tools.dino_metrics import structure_distance
+            # from the inputs as given: the tower's preprocess applies the same quantisation on integers, before its resize
+            xa, xb = (t.detach().to(self.device, torch.float32) for t in (original, edited))
+            self._parts["structure"].append(structure_distance(self._structure, xa, xb, quantize=quantize))
 
     def compute(self):
-        """dict(lpips, ssim, psnr, n): the means over the pairs seen (numpy fp64 means of ``values``)."""
+        """dict(lpips, ssim, psnr, n) -- with ``structure=`` also ``structure`` --: the means over the pairs seen (numpy fp64
+        means of ``values``)."""
         v = self.values
         n = len(v["psnr"])
         if n == 0:
