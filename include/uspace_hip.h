@@ -757,6 +757,66 @@ USPACE_API int uspace_self_similarity_mse_f64(const uint16_t* keys_a, const uint
                                               uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * ArcFace identity tower and the ID similarity (uspace_amd/libs/arcface.py, tools/id_metrics.py; csrc/idnet.hip):
+ * Backbone(input_size, num_layers, mode) of TreB1eN's InsightFace_Pytorch model_irse.py in eval mode -- IR-SE50 at 112 is the
+ * network behind the ID similarity of pSp / e4e.  input_layer = conv3x3(3, 64) + BN + PReLU; units bottleneck_IR(_SE)(in, depth,
+ * stride): res = BN -> conv3x3 -> PReLU -> conv3x3(stride) -> BN (-> SE, reduction 16), out = res + shortcut, the shortcut the
+ * subsample x[:, :, ::stride, ::stride] where in == depth and conv1x1(stride) + BN otherwise; four levels of 64 / 128 / 256 / 512
+ * channels, level l = one unit (in, depth, 2) and blocks[l] - 1 units (depth, depth, 1); output_layer = BN2d -> Flatten (c, y, x)
+ * -> Linear(512 (input_size / 16)^2, 512) -> BN1d; the result divided by its l2 norm (no eps).  Batch norms use the running
+ * statistics, eps 1e-5.  fp32 NHWC activations, every convolution the fp32-MFMA implicit GEMM (a k-ordered fp32 fma chain);
+ * batch norms behind a convolution or the Linear, and output_layer.0, are folded at pack time in fp64; the batch norm in front of
+ * a unit's first convolution is applied to in-bounds operands only (the reference zero-pads after it).  Every sum has one
+ * fixed order: a sample's embedding and a pair's similarity are bit-identical whatever B they sit in and wherever they sit in the
+ * batch.  No atomics; nothing of a workspace is read before it is written.  Added without a change of USPACE_ABI_VERSION:
+ * symbols only.
+ * ------------------------------------------------------------------------------------- */
+/* (struct-then-typedef, as uspace_clipv_config; the binding is uspace_amd/_hip.py IdnetConfig) */
+struct uspace_idnet_config {
+    int input_size;  /* 112: side of the aligned face crop; a positive multiple of 16, at most 4096 */
+    int blocks[4];   /* units per level: IR-50 (3, 4, 14, 3), IR-100 (3, 13, 30, 3), IR-152 (3, 8, 36, 3); each >= 1 */
+    int se;          /* 1: mode "ir_se" (SE modules), 0: mode "ir" */
+};
+typedef struct uspace_idnet_config uspace_idnet_config;
+
+/* parameter tensors in the module's state_dict order with the num_batches_tracked buffers dropped; a batch norm is weight, bias,
+ * running_mean, running_var: input_layer.0.weight [64, 3, 3, 3], input_layer.1.*, input_layer.2.weight [64] (PReLU);
+ * output_layer.0.* [512], output_layer.3.weight [512, 512 (input_size / 16)^2], output_layer.3.bias, output_layer.4.*; per unit
+ * body.u: shortcut_layer.0.weight [depth, in, 1, 1] and shortcut_layer.1.* (only where in != depth), res_layer.0.* [in],
+ * res_layer.1.weight [depth, in, 3, 3], res_layer.2.weight [depth], res_layer.3.weight [depth, depth, 3, 3], res_layer.4.*,
+ * res_layer.5.fc1.weight [depth / 16, depth, 1, 1], res_layer.5.fc2.weight [depth, depth / 16, 1, 1] (the two only with se).
+ * The blob is fp32 pieces on the 256-byte grid of csrc/blob.h; the Linear is stored permuted to (y, x, c).  An invalid config
+ * gives USPACE_ERR_ARG (-1 from param_numel) / 0 bytes; B outside 1 .. 32767 or a tensor of 2^31 elements or more likewise. */
+USPACE_API int uspace_idnet_num_params(const uspace_idnet_config* cfg);
+USPACE_API long uspace_idnet_param_numel(const uspace_idnet_config* cfg, int index);
+USPACE_API size_t uspace_idnet_weight_bytes(const uspace_idnet_config* cfg);
+USPACE_API size_t uspace_idnet_workspace_bytes(const uspace_idnet_config* cfg, int B);
+USPACE_API int uspace_idnet_pack_weights(const uspace_idnet_config* cfg, const float* const* params, int n_params, void* blob,
+                                         size_t blob_bytes, uspace_stream_t stream);
+/* x: fp32 NCHW [B, 3, H, W] -> out: fp32 NHWC [B, out_size, out_size, 3].  normalize != 0 maps [0, 1] to [-1, 1] first
+ * (2 x - 1).  crop != 0 is the ID loss of pSp / e4e: adaptive average pooling to 256 x 256 unless the input has that size, the
+ * crop [35:223, 32:220] (188 x 188), adaptive average pooling to out_size.  crop == 0 pools the whole image to out_size (inputs
+ * that are aligned crops already).  Adaptive pooling: output i of O averages inputs floor(i N / O) .. ceil((i + 1) N / O) - 1;
+ * every window sum is fp32 in row-major order, divided by the count, the 256 x 256 values rounded to fp32 as a stored map would
+ * be.  H, W <= 16384, out_size <= 4096, both tensors below 2^31 elements; otherwise USPACE_ERR_ARG. */
+USPACE_API int uspace_idnet_preprocess(const float* x, int B, int H, int W, int normalize, int crop, int out_size, float* out,
+                                       uspace_stream_t stream);
+/* x_nhwc: fp32 [B, input_size, input_size, 3] in [-1, 1] (uspace_idnet_preprocess's output) -> emb fp32 [B, 512], unit length */
+USPACE_API int uspace_idnet_forward(const uspace_idnet_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                    const float* x_nhwc, int B, float* emb, uspace_stream_t stream);
+/* Test aid: stage 0 = input_layer's output, 1 + u = unit u's output (NHWC fp32 [B, h, w, c]), 1 + (number of units) = the
+ * 512-vector before the l2 normalisation, fp32 [B, 512].  Nothing after the stage runs. */
+USPACE_API int uspace_idnet_tap(const uspace_idnet_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                const float* x_nhwc, int B, int stage, float* dump, uspace_stream_t stream);
+/* Test aid: unit `unit` of the packed tower alone on any map x_nhwc fp32 [B, H, W, in] (1 <= H, W <= 4096; odd sizes, which no
+ * valid input_size reaches) -> out fp32 [B, (H - 1) / stride + 1, (W - 1) / stride + 1, depth]. */
+USPACE_API size_t uspace_idnet_unit_workspace_bytes(const uspace_idnet_config* cfg, int unit, int B, int H, int W);
+USPACE_API int uspace_idnet_unit(const uspace_idnet_config* cfg, const void* blob, void* workspace, size_t workspace_bytes, int unit,
+                                 const float* x_nhwc, int B, int H, int W, float* out, uspace_stream_t stream);
+/* out[b] = sum_k ea[b, k] eb[b, k] over the 512 entries of two embeddings fp32 [B, 512]: products and sum in fp64, in k order */
+USPACE_API int uspace_idnet_similarity_f64(const float* ea, const float* eb, int B, double* out, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

@@ -60,6 +60,10 @@ class DinoConfig(ctypes.Structure):
                 ("layers", ctypes.c_int), ("ffn", ctypes.c_int), ("layerscale", ctypes.c_int), ("eps", ctypes.c_float)]
 
 
+class IdnetConfig(ctypes.Structure):
+    _fields_ = [("input_size", ctypes.c_int), ("blocks", ctypes.c_int * 4), ("se", ctypes.c_int)]
+
+
 class GemmExt(ctypes.Structure):
     _fields_ = [("row_c", ctypes.c_void_p), ("out_cen", ctypes.c_void_p), ("ld_cen", ctypes.c_int),
                 ("part_out", ctypes.c_void_p), ("part_in", ctypes.c_void_p), ("np_in", ctypes.c_int),
@@ -199,6 +203,17 @@ SIGNATURES = {
     "uspace_dino_forward": (_I, [ctypes.POINTER(DinoConfig), _P, _P, _SZ, _P, _P, _I, _I, _P, _I, _P, _P]),
     "uspace_self_similarity_mse_workspace_bytes": (_SZ, [_I, _I]),
     "uspace_self_similarity_mse_f64": (_I, [_P, _P, _I, _I, _I, _L, _L, _P, _SZ, _P, _P]),
+    "uspace_idnet_num_params": (_I, [ctypes.POINTER(IdnetConfig)]),
+    "uspace_idnet_param_numel": (_L, [ctypes.POINTER(IdnetConfig), _I]),
+    "uspace_idnet_weight_bytes": (_SZ, [ctypes.POINTER(IdnetConfig)]),
+    "uspace_idnet_workspace_bytes": (_SZ, [ctypes.POINTER(IdnetConfig), _I]),
+    "uspace_idnet_pack_weights": (_I, [ctypes.POINTER(IdnetConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
+    "uspace_idnet_preprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "uspace_idnet_forward": (_I, [ctypes.POINTER(IdnetConfig), _P, _P, _SZ, _P, _I, _P, _P]),
+    "uspace_idnet_tap": (_I, [ctypes.POINTER(IdnetConfig), _P, _P, _SZ, _P, _I, _I, _P, _P]),
+    "uspace_idnet_unit_workspace_bytes": (_SZ, [ctypes.POINTER(IdnetConfig), _I, _I, _I, _I]),
+    "uspace_idnet_unit": (_I, [ctypes.POINTER(IdnetConfig), _P, _P, _SZ, _I, _P, _I, _I, _I, _P, _P]),
+    "uspace_idnet_similarity_f64": (_I, [_P, _P, _I, _P, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),

@@ -1,5 +1,5 @@
 // The fp32 convolution and 3 x 3 pooling kernels over NHWC activations that the feature networks share (inception.hip,
-// lpips.hip), with their launchers.  fp32 operands on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): that instruction is
+// lpips.hip, idnet.hip), with their launchers.  fp32 operands on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): that instruction is
 // bit-for-bit a k-ordered fp32 fma chain, so every output element is fma(..fma(a_0 b_0, 0)..) over K in the fixed (tap, channel)
 // order, whatever the batch size: each image's activations are bit-identical across batch sizes.
 #pragma once
@@ -57,17 +57,22 @@ __global__ __launch_bounds__(256) void pool3_kernel(const float* __restrict__ x,
 // floats), the next K slice is prefetched into registers while the current one is multiplied.  VEC: Cin % 16 == 0,
 // so a K slice is 16 consecutive channels of one tap and each thread loads 8 of them as two 16-B loads; otherwise
 // (Conv2d_1a, Cin = 3) the slice is gathered element by element.  Padding and rows beyond M read as zeros.
+// idnet.hip adds the template parameter EPI (the epilogue); its default is the kernel as it was.
 struct ConvArgs {
     const float* x;
     const float* w;
     const float* bias;
     float* y;
     int H, W, cin, Ho, Wo, cout, kw, s, ph, pw, K, Kpad, ldo, coff, M;
+    const float* slope = nullptr;       // CONV_EPI_PRELU: per output channel
 };
+
+// Epilogues: bias + ReLU (the feature networks) | bias + per-channel PReLU max(v, 0) + a_n min(v, 0) | bias alone.
+enum { CONV_EPI_RELU = 0, CONV_EPI_PRELU = 1, CONV_EPI_BIAS = 2 };
 
 constexpr int BM = 128, BN = 64, BK = 16;
 
-template <bool VEC>
+template <bool VEC, int EPI = CONV_EPI_RELU>
 __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a) {
     __shared__ float As[BK][BM];
     __shared__ float Bs[BK][BN];
@@ -165,12 +170,19 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a) {
     const int n = n0 + wn * 32 + l32;
     if (n >= a.cout) return;
     const float bias = a.bias[n];
+    float slope = 0.f;
+    if constexpr (EPI == CONV_EPI_PRELU) slope = a.slope[n];
+    auto act = [&](float v) {
+        if constexpr (EPI == CONV_EPI_RELU) return fmaxf(v, 0.f);
+        if constexpr (EPI == CONV_EPI_PRELU) return fmaxf(v, 0.f) + slope * fminf(v, 0.f);
+        return v;
+    };
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
         const int mA = m0 + wm * 64 + row, mB = mA + 32;
-        if (mA < a.M) a.y[(size_t)mA * a.ldo + a.coff + n] = fmaxf(acc0[r] + bias, 0.f);
-        if (mB < a.M) a.y[(size_t)mB * a.ldo + a.coff + n] = fmaxf(acc1[r] + bias, 0.f);
+        if (mA < a.M) a.y[(size_t)mA * a.ldo + a.coff + n] = act(acc0[r] + bias);
+        if (mB < a.M) a.y[(size_t)mB * a.ldo + a.coff + n] = act(acc1[r] + bias);
     }
 }
 
@@ -204,6 +216,44 @@ inline int conv_f32_launch(const ConvSpec& c, const float* x, int B, int H, int 
         hipLaunchKernelGGL(conv_kernel<true>, grid, dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL(conv_kernel<false>, grid, dim3(256), 0, st, a);
+    US_CHECK_LAUNCH();
+    *Ho = a.Ho;
+    *Wo = a.Wo;
+    return USPACE_OK;
+}
+
+// The same with the epilogue chosen (CONV_EPI_*; slope [Cout] for PReLU), output rows Cout channels apart.  conv_f32_launch above is
+// the CONV_EPI_RELU form.  A template, so that only the translation unit that asks for an epilogue carries its kernels.
+template <int EPI>
+int conv_f32_launch_epi(const ConvSpec& c, const float* x, int B, int H, int W, const float* w, const float* bias, float* y,
+                        const float* slope, hipStream_t st, int* Ho, int* Wo) {
+    if (EPI == CONV_EPI_PRELU && !slope) return USPACE_ERR_ARG;
+    ConvArgs a;
+    a.x = x;
+    a.w = w;
+    a.bias = bias;
+    a.y = y;
+    a.H = H;
+    a.W = W;
+    a.cin = c.cin;
+    a.Ho = (H + 2 * c.ph - c.kh) / c.s + 1;
+    a.Wo = (W + 2 * c.pw - c.kw) / c.s + 1;
+    a.cout = c.cout;
+    a.kw = c.kw;
+    a.s = c.s;
+    a.ph = c.ph;
+    a.pw = c.pw;
+    a.K = conv_k(c);
+    a.Kpad = conv_kpad(c);
+    a.ldo = c.cout;
+    a.coff = 0;
+    a.M = B * a.Ho * a.Wo;
+    a.slope = slope;
+    const dim3 grid(us_cdiv(a.M, BM), us_cdiv(c.cout, BN));
+    if (c.cin % 16 == 0)
+        hipLaunchKernelGGL((conv_kernel<true, EPI>), grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((conv_kernel<false, EPI>), grid, dim3(256), 0, st, a);
     US_CHECK_LAUNCH();
     *Ho = a.Ho;
     *Wo = a.Wo;

@@ -61,11 +61,25 @@ def ssim(a, b, data_range=1.0, ws=None):
     return out
 
 
-class PairMetrics:
+class _IdentityColumn(type):
+    """``PairMetrics(..., identity=tower)``: the keyword is taken here, before ``__init__`` runs, and kept on the instance.
+    ``PairMetrics.__init__`` keeps the parameter list it had (``tests/test_dino_host.py`` pins it name by name), so code that
+    inspects or forwards that list sees no difference; subclasses inherit the keyword."""
+
+    def __call__(cls, *args, identity=None, **kw):
+        self = cls.__new__(cls)
+        self._identity = identity
+        self.__init__(*args, **kw)
+        return self
+
+
+class PairMetrics(metaclass=_IdentityColumn):
     """Per-pair LPIPS / SSIM / PSNR accumulated over batches.  ``lpips``: an ``LPIPS`` module (e.g. with seeded weights) or a
     weight file's path; with neither, ``LPIPS(net)`` needs its weights at first use and says so.  ``structure``: a
     ``DinoVisionTransformer`` (usually ``DINO_B8``) adds a ``structure`` column, ``dino_metrics.structure_distance`` of every
-    pair on that tower's last-layer keys; the default None leaves the three columns as they are."""
+    pair on that tower's last-layer keys; ``identity``: an ArcFace ``Backbone`` (usually ``IR_SE50``) adds an ``identity`` column,
+    ``id_metrics.id_similarity`` of every pair (a keyword of the call, see ``_IdentityColumn``).  The defaults None leave the three
+    columns as they are."""
 
     def __init__(self, device=None, lpips=None, net="alex", structure=None):
         self.device = _device(device)
@@ -84,6 +98,8 @@ class PairMetrics:
         self._parts = {"lpips": [], "ssim": [], "psnr": []}
         if self._structure is not None:
             self._parts["structure"] = []
+        if self._identity is not None:
+            self._parts["identity"] = []
 
     @property
     def n(self):
@@ -109,10 +125,13 @@ class PairMetrics:
             # from the inputs as given: the tower's preprocess applies the same quantisation on integers, before its resize
             xa, xb = (t.detach().to(self.device, torch.float32) for t in (original, edited))
             self._parts["structure"].append(structure_distance(self._structure, xa, xb, quantize=quantize))
+        if self._identity is not None:
+            from uspace_amd.tools.id_metrics import id_similarity
+            self._parts["identity"].append(id_similarity(self._identity, x, y, quantize=False))     # x, y are quantised above
 
     def compute(self):
-        """dict(lpips, ssim, psnr, n) -- with ``structure=`` also ``structure`` --: the means over the pairs seen (numpy fp64
-        means of ``values``)."""
+        """dict(lpips, ssim, psnr, n) -- with ``structure=`` also ``structure``, with ``identity=`` also ``identity`` --: the means
+        over the pairs seen (numpy fp64 means of ``values``)."""
         v = self.values
         n = len(v["psnr"])
         if n == 0:
