@@ -1,4 +1,4 @@
-"""The packed-weight blobs of the six models as the library lays them out: which configurations are pinned, how a size
+"""The packed-weight blobs of the models as the library lays them out: which configurations are pinned, how a size
 record and a blob digest are taken.  Shared by tests/golden/make_blob_golden.py (which records them) and by
 tests/test_blob_layout.py / tests/test_gpu_blob_pack.py (which compare).  Nothing here goes through the Python wrappers'
 own pack path: the size queries and ``uspace_*_pack_weights`` are called through ctypes."""
@@ -55,6 +55,28 @@ def clipv_cfg(hidden_size, intermediate_size, num_hidden_layers, num_attention_h
                                  projection_dim, layer_norm_eps)
 
 
+def dino_cfg(hidden_size, num_attention_heads, num_hidden_layers, patch_size, image_size, layerscale, layer_norm_eps, mlp_ratio=4, **_):
+    from uspace_amd import _hip
+    return _hip.DinoConfig(image_size, patch_size, hidden_size, num_attention_heads, num_hidden_layers, hidden_size * mlp_ratio,
+                           1 if layerscale else 0, layer_norm_eps)
+
+
+def idnet_cfg(input_size, blocks, se):
+    from uspace_amd import _hip
+    return _hip.IdnetConfig(input_size, (ctypes.c_int * 4)(*blocks), se)
+
+
+def tiny_dino():
+    """The golden DINOv2 tower of tests/dino_cases.py at its table's own side (no interpolation of the position table)."""
+    from tests import dino_cases as D
+    return D.golden_module_config("dinov2", 70)
+
+
+def lead_args(cfg):
+    """What every entry point of a family takes first: nothing, an int by value (``uspace_lpips_``'s ``net``) or its config struct."""
+    return () if cfg is None else (cfg if isinstance(cfg, int) else ctypes.byref(cfg),)
+
+
 def size_cases(golden_dir):
     """{case name: (symbol prefix, config or None, [(label, extra workspace arguments)])}.  The U-ViT cases are every model of
     tools/bench_configs.py and the two tiny fixtures; they are recorded once per setting of uspace_gemm_set_sk (size_table)."""
@@ -79,11 +101,21 @@ def size_cases(golden_dir):
     cases["clipv/L"] = ("uspace_clipv_", clipv_cfg(**CLIP_L_VISION), plain)
     cases["clipv/tiny"] = ("uspace_clipv_", clipv_cfg(**TINY_VISION), plain)
     cases["inception"] = ("uspace_inception_", None, [("299/", (299, 299)), ("64/", (64, 64))])
+    from uspace_amd.libs.arcface import BLOCKS
+    from uspace_amd.libs.dino import DINOV2_L14
+    from uspace_amd.tools.lpips import NETS
+    for net in ("alex", "vgg"):
+        cases[f"lpips/{net}"] = ("uspace_lpips_", NETS[net], [("64/", (64, 64)), ("256/", (256, 256))])
+    cases["idnet/IR_SE50"] = ("uspace_idnet_", idnet_cfg(112, BLOCKS[50], 1), plain)
+    cases["idnet/tiny_se"] = ("uspace_idnet_", idnet_cfg(32, (1, 1, 1, 1), 1), plain)
+    cases["idnet/tiny_ir"] = ("uspace_idnet_", idnet_cfg(32, (1, 1, 1, 1), 0), plain)
+    cases["dino/L14"] = ("uspace_dino_", dino_cfg(**DINOV2_L14), plain)
+    cases["dino/tiny"] = ("uspace_dino_", dino_cfg(**tiny_dino()), plain)
     return cases
 
 
 def size_record(L, prefix, cfg, ws_forms):
-    lead = () if cfg is None else (ctypes.byref(cfg),)
+    lead = lead_args(cfg)
     fn = lambda what: getattr(L, prefix + what)
     n = fn("num_params")(*lead)
     return dict(num_params=n, param_numel=[fn("param_numel")(*lead, i) for i in range(n)], weight_bytes=fn("weight_bytes")(*lead),
@@ -144,20 +176,34 @@ def tiny_model(kind, golden_dir):
         m.load_state_dict(V.case_params("tiny"))
         m = m.cuda()
         return m, "uspace_clipv_", clipv_cfg(**cfg), list(m.parameters())
-    assert kind == "inception"
-    from uspace_amd.tools.inception import InceptionV3
-    m = InceptionV3([3], seed=0).cuda()
-    return m, "uspace_inception_", None, list(m.state_dict().values())
+    if kind == "inception":
+        from uspace_amd.tools.inception import InceptionV3
+        m = InceptionV3([3], seed=0).cuda()
+        return m, "uspace_inception_", None, list(m.state_dict().values())
+    if kind in ("lpips_alex", "lpips_vgg"):
+        from uspace_amd.tools.lpips import LPIPS, NETS
+        m = LPIPS(kind[6:], seed=3).cuda()
+        return m, "uspace_lpips_", NETS[m.net], m._canonical_params()
+    if kind in ("idnet", "idnet_ir"):
+        from uspace_amd.libs.arcface import Backbone
+        kw = dict(mode="ir", seed=9) if kind == "idnet_ir" else dict(seed=5)
+        m = Backbone(input_size=32, blocks=(1, 1, 1, 1), **kw).cuda()
+        return m, "uspace_idnet_", m.cfg, m._canonical_params()
+    assert kind == "dino"
+    from uspace_amd.libs.dino import DinoVisionTransformer
+    m = DinoVisionTransformer(seed=0, **tiny_dino()).cuda()
+    return m, "uspace_dino_", m._c_cfg(), m._canonical_params()
 
 
-TINY_KINDS = ("tiny_u", "tiny_t2i", "vae", "vae_enc", "clip", "clipv", "inception")
+TINY_KINDS = ("tiny_u", "tiny_t2i", "vae", "vae_enc", "clip", "clipv", "inception", "lpips_alex", "lpips_vgg", "idnet", "idnet_ir",
+              "dino")
 
 
 def blob_digest(prefix, cfg, tensors):
     """sha256 of the whole blob ``{prefix}pack_weights`` writes into zeroed memory (so the padding is compared too)."""
     from uspace_amd import _hip
     L = _hip.lib()
-    lead = () if cfg is None else (ctypes.byref(cfg),)
+    lead = lead_args(cfg)
     srcs = [t.detach().to(torch.float32).contiguous() for t in tensors]
     nbytes = getattr(L, prefix + "weight_bytes")(*lead)
     assert nbytes > 0 and getattr(L, prefix + "num_params")(*lead) == len(srcs)

@@ -1,4 +1,4 @@
-"""Every size the library reports for the packed weight blobs and the workspaces of the six models, against
+"""Every size the library reports for the packed weight blobs and the workspaces of every model, against
 tests/golden/blob_sizes.json (recorded by tests/golden/make_blob_golden.py at the commit named in the file): exact integers, no
 margin.  Host queries only; the library loads without a GPU."""
 import ctypes
@@ -31,7 +31,7 @@ def test_param_numel_rejects_indices_outside_the_parameters(golden_dir):
     from uspace_amd import _hip
     L = _hip.lib()
     for name, (prefix, cfg, _ws) in C.size_cases(golden_dir).items():
-        lead = () if cfg is None else (ctypes.byref(cfg),)
+        lead = C.lead_args(cfg)
         numel = getattr(L, prefix + "param_numel")
         n = getattr(L, prefix + "num_params")(*lead)
         assert n > 0 and numel(*lead, -1) < 0 and numel(*lead, n) < 0, name       # U-ViT: n is its first derived entry
@@ -47,8 +47,12 @@ def test_invalid_configs_report_no_parameters_and_no_bytes():
            ("uspace_vae_", _hip.VaeConfig(100, mult, 4, 2, 256)),                           # ch not a multiple of 64
            ("uspace_vae_enc_", _hip.VaeConfig(192, mult, 4, 2, 256)),                       # encoder: ch not a power of two
            ("uspace_clip_", _hip.ClipConfig(49408, 768, 8, 12, 3072, 77, 1e-5)),           # head_dim != 64
-           ("uspace_clipv_", _hip.ClipVisionConfig(224, 14, 1024, 12, 24, 4096, 768, 1e-5))]   # heads * 64 != dim
+           ("uspace_clipv_", _hip.ClipVisionConfig(224, 14, 1024, 12, 24, 4096, 768, 1e-5)),   # heads * 64 != dim
+           ("uspace_idnet_", C.idnet_cfg(40, (1, 1, 1, 1), 1)),                             # input_size not a multiple of 16
+           ("uspace_dino_", _hip.DinoConfig(224, 14, 1024, 12, 24, 4096, 1, 1e-6)),        # heads * 64 != dim
+           ("uspace_lpips_", 2)]                                                            # neither of the two nets (by value)
     for prefix, cfg in bad:
-        ref = ctypes.byref(cfg)
+        ref, = C.lead_args(cfg)
+        size = (64, 64) if prefix == "uspace_lpips_" else ()       # its workspace depends on the image size too
         assert getattr(L, prefix + "num_params")(ref) < 0 and getattr(L, prefix + "param_numel")(ref, 0) < 0, prefix
-        assert getattr(L, prefix + "weight_bytes")(ref) == 0 and getattr(L, prefix + "workspace_bytes")(ref, 8) == 0, prefix
+        assert getattr(L, prefix + "weight_bytes")(ref) == 0 and getattr(L, prefix + "workspace_bytes")(ref, 8, *size) == 0, prefix

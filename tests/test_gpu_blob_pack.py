@@ -39,14 +39,18 @@ WRAPPERS = {
     "clip": ("_packed_blob", "_ws", 1, lambda m, B: m(torch.zeros(B, 77, dtype=torch.long, device="cuda"))),
     "clipv": ("_packed_blob", "_ws", 1, lambda m, B: m(torch.zeros(B, 3, m.cfg["image"], m.cfg["image"], device="cuda"))),
     "inception": ("_blob", "_ws", 1, lambda m, B: m.features(torch.rand(B, 3, 64, 64, device="cuda"))),
+    "lpips": ("_packed_blob", "_ws", 1, lambda m, B: m(torch.rand(B, 3, 64, 64, device="cuda"), torch.rand(B, 3, 64, 64, device="cuda"))),
+    "dino": ("_packed_blob", "_ws", 1, lambda m, B: m(torch.zeros(B, 3, m.cfg["image"], m.cfg["image"], device="cuda"))),
+    "arcface": ("_blob", "_ws", 2, lambda m, B: m(torch.zeros(B, 3, 32, 32, device="cuda"))),
 }
+TINY_OF = {"lpips": "lpips_alex", "arcface": "idnet"}      # the wrapper's tiny model where its kind is named otherwise
 
 
 @pytest.mark.parametrize("kind", sorted(WRAPPERS))
 def test_blob_and_workspace_cache_contract(tiny, kind):
     from uspace_amd._blob import WorkspaceCache
     getter, ws_attr, slots, run = WRAPPERS[kind]
-    m, _prefix, _cfg, tensors = tiny[kind]
+    m, _prefix, _cfg, tensors = tiny[TINY_OF.get(kind, kind)]
     blob = getattr(m, getter)
     dev = torch.device("cuda", torch.cuda.current_device())
     p = tensors[0]

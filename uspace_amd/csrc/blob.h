@@ -1,7 +1,8 @@
 // One layout for every model's packed weights and workspaces (host side only): the aligned arena, the parameter table and
-// the loop that packs fp32 checkpoint tensors into a device blob.  uvit.hip, vae.hip (both halves), clip.hip and clip_vision.hip
-// (the two towers' layers through clip_encoder.h) describe their parameters with a ParamTable and serve num_params / param_numel / weight_bytes / pack_weights from it; inception.hip keeps its
-// own layout (64-byte pieces, batch norm folded in fp64 at pack time).
+// the loop that packs fp32 checkpoint tensors into a device blob.  Every model describes its parameters with a ParamTable and serves
+// num_params / param_numel / weight_bytes / pack_weights from it: uvit.hip, vae.hip (both halves), clip.hip and clip_vision.hip (the two
+// towers' layers through clip_encoder.h), dino.hip, and the fp32 convolution towers inception.hip, lpips.hip and idnet.hip, whose
+// convolutions and batch norms are P_OWNER entries that conv_f32.h's pack step writes.
 #pragma once
 #include <vector>
 
@@ -12,9 +13,10 @@ inline size_t us_align_up(size_t v) { return (v + US_BLOB_ALIGN - 1) / US_BLOB_A
 
 struct Arena {
     size_t off = 0;   // bytes handed out so far = the size to allocate
+    size_t align = US_BLOB_ALIGN;   // inception.hip and lpips.hip place their pieces 64 bytes apart
     size_t take(size_t bytes) {
         const size_t o = off;
-        off = us_align_up(off + bytes);
+        off = (off + bytes + align - 1) / align * align;
         return o;
     }
 };
@@ -25,6 +27,7 @@ enum PKind {
     P_BF16 = 1,         // cast (GEMM weights in nn.Linear [N][K] layout, 1x1 convolutions)
     P_CONV3_BF16 = 2,   // 3x3 convolution [Co][Ci][3][3] -> bf16 [Co][9][Ci]
     P_CONV3_F32T = 3,   // ... -> fp32 [Co][9][Ci]
+    P_OWNER = 4,        // counted and sized here, stored by the model's own pack step (or folded into another tensor): no space
 };
 
 struct PDesc {
@@ -43,7 +46,9 @@ struct ParamTable {
     bool derived = false;
 
     static size_t bytes_of(long numel, PKind k) { return (size_t)numel * ((k == P_BF16 || k == P_CONV3_BF16) ? 2 : 4); }
-    int add(long numel, PKind k, int co = 0, int ci = 0) { return add_at(arena.take(bytes_of(numel, k)), numel, k, co, ci); }
+    int add(long numel, PKind k, int co = 0, int ci = 0) {
+        return add_at(k == P_OWNER ? 0 : arena.take(bytes_of(numel, k)), numel, k, co, ci);
+    }
     // at `offset` inside space the caller took from the arena itself (several parameters packed into one region)
     int add_at(size_t offset, long numel, PKind k, int co = 0, int ci = 0) {
         p.push_back(PDesc{numel, k, co, ci, offset, bytes_of(numel, k)});
@@ -79,6 +84,8 @@ inline int us_pack_table(const ParamTable& t, const float* const* params, int n_
             case P_CONV3_BF16:
             case P_CONV3_F32T:
                 US_TRY(us_repack_conv3(params[i], dst, d.co, d.ci, d.kind == P_CONV3_BF16, s));
+                break;
+            case P_OWNER:
                 break;
         }
     }

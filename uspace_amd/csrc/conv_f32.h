@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void pool3_kernel(const float* __restrict__ x,
 // floats), the next K slice is prefetched into registers while the current one is multiplied.  VEC: Cin % 16 == 0,
 // so a K slice is 16 consecutive channels of one tap and each thread loads 8 of them as two 16-B loads; otherwise
 // (Conv2d_1a, Cin = 3) the slice is gathered element by element.  Padding and rows beyond M read as zeros.
-// idnet.hip adds the template parameter EPI (the epilogue); its default is the kernel as it was.
+// EPI chooses the epilogue (below); only idnet.hip asks for another than the default.
 struct ConvArgs {
     const float* x;
     const float* w;
@@ -186,11 +186,14 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a) {
     }
 }
 
-// ---- launchers.  w: packed W'[k = (ty * kw + tx) * Cin + c][n] with rows K .. Kpad - 1 zero, bias [Cout]; the output pixel
+// ---- launcher.  w: packed W'[k = (ty * kw + tx) * Cin + c][n] with rows K .. Kpad - 1 zero, bias [Cout]; the output pixel
 // rows are ldo channels apart and the result lands at channel offset coff (Cout % 4 == 0: the weight rows are read 16 bytes
-// at a time).  Ho / Wo receive the output size.
-inline int conv_f32_launch(const ConvSpec& c, const float* x, int B, int H, int W, const float* w, const float* bias, float* y,
-                           int ldo, int coff, hipStream_t st, int* Ho, int* Wo) {
+// at a time).  EPI: the epilogue (CONV_EPI_*; slope [Cout] for PReLU); a template, so that only the translation unit that asks
+// for an epilogue carries its kernels.  Ho / Wo receive the output size.
+template <int EPI = CONV_EPI_RELU>
+int conv_f32_launch(const ConvSpec& c, const float* x, int B, int H, int W, const float* w, const float* bias, float* y, int ldo,
+                    int coff, hipStream_t st, int* Ho, int* Wo, const float* slope = nullptr) {
+    if (EPI == CONV_EPI_PRELU && !slope) return USPACE_ERR_ARG;
     ConvArgs a;
     a.x = x;
     a.w = w;
@@ -211,43 +214,6 @@ inline int conv_f32_launch(const ConvSpec& c, const float* x, int B, int H, int 
     a.ldo = ldo;
     a.coff = coff;
     a.M = B * a.Ho * a.Wo;
-    const dim3 grid(us_cdiv(a.M, BM), us_cdiv(c.cout, BN));
-    if (c.cin % 16 == 0)
-        hipLaunchKernelGGL(conv_kernel<true>, grid, dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(conv_kernel<false>, grid, dim3(256), 0, st, a);
-    US_CHECK_LAUNCH();
-    *Ho = a.Ho;
-    *Wo = a.Wo;
-    return USPACE_OK;
-}
-
-// The same with the epilogue chosen (CONV_EPI_*; slope [Cout] for PReLU), output rows Cout channels apart.  conv_f32_launch above is
-// the CONV_EPI_RELU form.  A template, so that only the translation unit that asks for an epilogue carries its kernels.
-template <int EPI>
-int conv_f32_launch_epi(const ConvSpec& c, const float* x, int B, int H, int W, const float* w, const float* bias, float* y,
-                        const float* slope, hipStream_t st, int* Ho, int* Wo) {
-    if (EPI == CONV_EPI_PRELU && !slope) return USPACE_ERR_ARG;
-    ConvArgs a;
-    a.x = x;
-    a.w = w;
-    a.bias = bias;
-    a.y = y;
-    a.H = H;
-    a.W = W;
-    a.cin = c.cin;
-    a.Ho = (H + 2 * c.ph - c.kh) / c.s + 1;
-    a.Wo = (W + 2 * c.pw - c.kw) / c.s + 1;
-    a.cout = c.cout;
-    a.kw = c.kw;
-    a.s = c.s;
-    a.ph = c.ph;
-    a.pw = c.pw;
-    a.K = conv_k(c);
-    a.Kpad = conv_kpad(c);
-    a.ldo = c.cout;
-    a.coff = 0;
-    a.M = B * a.Ho * a.Wo;
     a.slope = slope;
     const dim3 grid(us_cdiv(a.M, BM), us_cdiv(c.cout, BN));
     if (c.cin % 16 == 0)
@@ -257,6 +223,55 @@ int conv_f32_launch_epi(const ConvSpec& c, const float* x, int B, int H, int W, 
     US_CHECK_LAUNCH();
     *Ho = a.Ho;
     *Wo = a.Wo;
+    return USPACE_OK;
+}
+// every translation unit carries the default epilogue's two kernels, as it did while that launcher was not a template
+template int conv_f32_launch<CONV_EPI_RELU>(const ConvSpec&, const float*, int, int, int, const float*, const float*, float*, int, int,
+                                            hipStream_t, int*, int*, const float*);
+
+// ---- weight packing.  Where a packed convolution's scale and bias come from: the eval-mode batch norm that follows it
+// (gamma != NULL), folded in fp64 and rounded once to fp32 -- W' = w s_n, s_n = gamma_n / sqrt(var_n + eps), bias_n = beta_n - mean_n s_n;
+// or its own bias, copied; or neither: the plain weights, bout untouched.
+struct ConvPackSource {
+    const float *gamma = nullptr, *beta = nullptr, *mean = nullptr, *var = nullptr;
+    double eps = 0.0;
+    const float* bias = nullptr;
+    // p: the batch norm's weight, bias, running_mean, running_var (state-dict order)
+    static ConvPackSource batch_norm(const float* const* p, double eps) { return {p[0], p[1], p[2], p[3], eps, nullptr}; }
+    static ConvPackSource with_bias(const float* b) { return {nullptr, nullptr, nullptr, nullptr, 0.0, b}; }
+};
+
+// w [Cout][Cin][kh][kw] -> wout W'[k = (ty * kw + tx) * Cin + c][n], zero rows k >= K; then bout [Cout]
+__global__ __launch_bounds__(256) void pack_conv_kernel(const float* __restrict__ w, ConvPackSource src, float* __restrict__ wout,
+                                                        float* __restrict__ bout, int cin, int cout, int kh, int kw, int K,
+                                                        int Kpad) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long nw = (long)Kpad * cout;
+    if (idx < nw) {
+        const int k = (int)(idx / cout), n = (int)(idx - (long)k * cout);
+        float v = 0.f;
+        if (k < K) {
+            const int tap = k / cin, c = k - tap * cin, ty = tap / kw, tx = tap - ty * kw;
+            v = w[(((long)n * cin + c) * kh + ty) * kw + tx];
+            if (src.gamma) v = (float)((double)v * ((double)src.gamma[n] / sqrt((double)src.var[n] + src.eps)));
+        }
+        wout[idx] = v;
+    } else if (idx < nw + cout) {
+        const int n = (int)(idx - nw);
+        if (src.gamma) {
+            const double s = (double)src.gamma[n] / sqrt((double)src.var[n] + src.eps);
+            bout[n] = (float)((double)src.beta[n] - (double)src.mean[n] * s);
+        } else if (src.bias) {
+            bout[n] = src.bias[n];
+        }
+    }
+}
+
+inline int conv_f32_pack(const ConvSpec& c, const float* w, const ConvPackSource& src, float* wout, float* bout, hipStream_t st) {
+    const long n = (long)conv_kpad(c) * c.cout + c.cout;
+    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, src, wout, bout, c.cin, c.cout, c.kh,
+                       c.kw, conv_k(c), conv_kpad(c));
+    US_CHECK_LAUNCH();
     return USPACE_OK;
 }
 

@@ -40,15 +40,20 @@ struct Unit {
     bool conv_sc;
     // blob offsets in floats
     size_t pre_s, pre_b, w1, slope, w2, b2, wsc, bsc, fc1, fc2;
+    // parameter indices: the weights of the shortcut convolution and of the two 3 x 3 convolutions (the batch norm after i_sc and
+    // i_w2 is the next four parameters), res_layer.0's batch norm (four)
+    int i_sc, i_pre, i_w1, i_w2;
 };
 struct Net {
     int S, se, side;              // input side; SE modules present; side of the last map (S / 16)
     std::vector<Unit> units;
     size_t in_w, in_b, in_slope, zeros, head_w, head_b;
-    std::vector<long> numel;      // the caller's parameters in state-dict order (num_batches_tracked left out)
-    size_t bytes;
+    int i_in, i_head;             // input_layer's convolution (its batch norm follows); output_layer's ten parameters
+    ParamTable t;                 // the caller's parameters in state-dict order (num_batches_tracked left out)
 };
 
+// The blob, piece by piece in the order the pieces lie in it, and beside each piece the parameters it is made from.  Convolutions,
+// batch norms and the output layer are P_OWNER: uspace_idnet_pack_weights folds them into the pieces taken here.
 bool make_net(const uspace_idnet_config* cfg, Net* out) {
     if (!cfg || cfg->input_size < 16 || cfg->input_size % 16 || cfg->input_size > 4096) return false;
     for (int l = 0; l < 4; ++l)
@@ -58,26 +63,29 @@ bool make_net(const uspace_idnet_config* cfg, Net* out) {
     n.S = cfg->input_size;
     n.se = cfg->se;
     n.side = n.S / 16;
-    Arena ar;
-    auto take = [&](size_t floats) { return ar.take(floats * sizeof(float)) / sizeof(float); };
-    auto bn = [&](int c) {
-        for (int j = 0; j < 4; ++j) n.numel.push_back(c);
+    ParamTable& t = n.t;
+    auto take = [&](size_t floats) { return t.arena.take(floats * sizeof(float)) / sizeof(float); };
+    auto copied = [&](long numel) { return t.at(t.add(numel, P_F32)) / sizeof(float); };
+    auto own = [&](long numel) { return t.add(numel, P_OWNER); };
+    auto own_bn = [&](int c) {
+        const int i = own(c);
+        for (int j = 1; j < 4; ++j) own(c);
+        return i;
     };
     const ConvSpec in_conv{3, 64, 3, 3, 1, 1, 1};
     n.in_w = take((size_t)conv_kpad(in_conv) * 64);
     n.in_b = take(64);
-    n.in_slope = take(64);
+    n.i_in = own(64 * 27);
+    own_bn(64);
+    n.in_slope = copied(64);
     n.zeros = take(kEmb);
-    n.numel.push_back(64 * 27);
-    bn(64);
-    n.numel.push_back(64);
     const long K = (long)kEmb * n.side * n.side;
     n.head_w = take((size_t)K * kEmb);
     n.head_b = take(kEmb);
-    bn(512);
-    n.numel.push_back(K * kEmb);
-    n.numel.push_back(kEmb);
-    bn(kEmb);
+    n.i_head = own_bn(512);
+    own(K * kEmb);
+    own(kEmb);
+    own_bn(kEmb);
     for (int l = 0; l < 4; ++l)
         for (int j = 0; j < cfg->blocks[l]; ++j) {
             Unit u{};
@@ -89,29 +97,25 @@ bool make_net(const uspace_idnet_config* cfg, Net* out) {
             if (u.conv_sc) {
                 u.wsc = take((size_t)u.cin * u.d);
                 u.bsc = take(u.d);
-                n.numel.push_back((long)u.d * u.cin);
-                bn(u.d);
+                u.i_sc = own((long)u.d * u.cin);
+                own_bn(u.d);
             }
             u.pre_s = take(u.cin);
             u.pre_b = take(u.cin);
+            u.i_pre = own_bn(u.cin);
             u.w1 = take((size_t)9 * u.cin * u.d);
-            u.slope = take(u.d);
+            u.i_w1 = own((long)u.d * u.cin * 9);
+            u.slope = copied(u.d);
             u.w2 = take((size_t)9 * u.d * u.d);
             u.b2 = take(u.d);
-            bn(u.cin);
-            n.numel.push_back((long)u.d * u.cin * 9);
-            n.numel.push_back(u.d);
-            n.numel.push_back((long)u.d * u.d * 9);
-            bn(u.d);
+            u.i_w2 = own((long)u.d * u.d * 9);
+            own_bn(u.d);
             if (n.se) {
-                u.fc1 = take((size_t)r * u.d);
-                u.fc2 = take((size_t)u.d * r);
-                n.numel.push_back((long)r * u.d);
-                n.numel.push_back((long)u.d * r);
+                u.fc1 = copied((long)r * u.d);
+                u.fc2 = copied((long)u.d * r);
             }
             n.units.push_back(u);
         }
-    n.bytes = ar.off;
     *out = std::move(n);
     return true;
 }
@@ -173,32 +177,6 @@ bool plan(const Net& n, int B, Carve* c) {
 }
 
 // ------------------------------------------------------------------------------------------------ pack kernels
-// Convolution weight with the batch norm that follows it folded in (fp64, rounded once):
-// W'[k = (ty * kw + tx) * Cin + c][n] = w[n][c][ty][tx] * s_n, s_n = gamma_n / sqrt(var_n + eps), zero rows k >= K;
-// bias_n = beta_n - mean_n s_n.  bn == 0 (no batch norm follows): s_n = 1 and no bias is written.
-__global__ __launch_bounds__(256) void idnet_pack_conv_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, const float* __restrict__ mean,
-                                                              const float* __restrict__ var, int bn, float* __restrict__ wout,
-                                                              float* __restrict__ bout, int cin, int cout, int kh, int kw, int K,
-                                                              int Kpad) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nw = (long)Kpad * cout;
-    if (idx < nw) {
-        const int k = (int)(idx / cout), n = (int)(idx - (long)k * cout);
-        double v = 0.0;
-        if (k < K) {
-            const int tap = k / cin, c = k - tap * cin, ty = tap / kw, tx = tap - ty * kw;
-            v = (double)w[(((long)n * cin + c) * kh + ty) * kw + tx];
-            if (bn) v *= (double)gamma[n] / sqrt((double)var[n] + kBnEps);
-        }
-        wout[idx] = (float)v;
-    } else if (bn && idx < nw + cout) {
-        const int n = (int)(idx - nw);
-        const double s = (double)gamma[n] / sqrt((double)var[n] + kBnEps);
-        bout[n] = (float)((double)beta[n] - (double)mean[n] * s);
-    }
-}
-
 // an eval-mode batch norm as y = x s_c + t_c
 __global__ __launch_bounds__(256) void idnet_bn_affine_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               const float* __restrict__ mean, const float* __restrict__ var,
@@ -208,11 +186,6 @@ __global__ __launch_bounds__(256) void idnet_bn_affine_kernel(const float* __res
     const double s = (double)gamma[c] / sqrt((double)var[c] + kBnEps);
     s_out[c] = (float)s;
     t_out[c] = (float)((double)beta[c] - (double)mean[c] * s);
-}
-
-__global__ __launch_bounds__(256) void idnet_fill_kernel(float* __restrict__ dst, long n, float v) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = v;
 }
 
 // The head: out_n = BN1d(Linear(flatten_cyx(BN2d(x)))) as one matrix and one bias.  bn0 / bn1: gamma, beta, mean, var.
@@ -243,8 +216,7 @@ __global__ __launch_bounds__(64) void idnet_pack_head_b_kernel(const float* __re
         const double s0 = (double)g0[c] / sqrt((double)v0[c] + kBnEps);
         s += (double)w[(long)n * K + k] * ((double)b0[c] - (double)m0[c] * s0);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum_f64(s);
     if (threadIdx.x == 0) {
         const double s1 = (double)g1[n] / sqrt((double)v1[n] + kBnEps);
         bout[n] = (float)(((double)b[n] + s) * s1 + ((double)b1[n] - (double)m1[n] * s1));
@@ -467,12 +439,12 @@ int run_unit(const Net& n, const Unit& u, const float* wts, const float* x, int 
     hipLaunchKernelGGL(idnet_bn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, wts + u.pre_s, wts + u.pre_b, bf.pre,
                        n4, u.cin / 4);
     US_CHECK_LAUNCH();
-    US_TRY(conv_f32_launch_epi<CONV_EPI_PRELU>(c1, bf.pre, B, H, W, wts + u.w1, wts + n.zeros, bf.t1, wts + u.slope, st, &h1, &w1));
-    US_TRY(conv_f32_launch_epi<CONV_EPI_BIAS>(c2, bf.t1, B, h1, w1, wts + u.w2, wts + u.b2, bf.t2, nullptr, st, &ho, &wo));
+    US_TRY(conv_f32_launch<CONV_EPI_PRELU>(c1, bf.pre, B, H, W, wts + u.w1, wts + n.zeros, bf.t1, u.d, 0, st, &h1, &w1, wts + u.slope));
+    US_TRY(conv_f32_launch<CONV_EPI_BIAS>(c2, bf.t1, B, h1, w1, wts + u.w2, wts + u.b2, bf.t2, u.d, 0, st, &ho, &wo));
     const float* sc = nullptr;
     if (u.conv_sc) {
         int hs, ws_;
-        US_TRY(conv_f32_launch_epi<CONV_EPI_BIAS>(cs, x, B, H, W, wts + u.wsc, wts + u.bsc, bf.sc, nullptr, st, &hs, &ws_));
+        US_TRY(conv_f32_launch<CONV_EPI_BIAS>(cs, x, B, H, W, wts + u.wsc, wts + u.bsc, bf.sc, u.d, 0, st, &hs, &ws_));
         if (hs != ho || ws_ != wo) return USPACE_ERR_ARG;
         sc = bf.sc;
     }
@@ -516,8 +488,8 @@ int run(const uspace_idnet_config* cfg, const void* blob, void* ws, size_t ws_by
     const Bufs bf = bufs_of(base, cv);
     const float* wts = (const float*)blob;
     int h, w, cur = 0, c = 64;
-    US_TRY(conv_f32_launch_epi<CONV_EPI_PRELU>(ConvSpec{3, 64, 3, 3, 1, 1, 1}, x, B, n.S, n.S, wts + n.in_w, wts + n.in_b, xb[0],
-                                               wts + n.in_slope, st, &h, &w));
+    US_TRY(conv_f32_launch<CONV_EPI_PRELU>(ConvSpec{3, 64, 3, 3, 1, 1, 1}, x, B, n.S, n.S, wts + n.in_w, wts + n.in_b, xb[0], 64, 0, st,
+                                           &h, &w, wts + n.in_slope));
     for (int u = 0; u < U && u < last; ++u) {
         US_TRY(run_unit(n, n.units[u], wts, xb[cur], B, h, w, bf, xb[cur ^ 1], st, &h, &w));
         cur ^= 1;
@@ -540,24 +512,21 @@ int run(const uspace_idnet_config* cfg, const void* blob, void* ws, size_t ws_by
     return USPACE_OK;
 }
 
-int launch_1d(long n) { return (int)((n + 255) / 256); }
-
 }  // namespace
 
 extern "C" int uspace_idnet_num_params(const uspace_idnet_config* cfg) {
     Net n;
-    return make_net(cfg, &n) ? (int)n.numel.size() : USPACE_ERR_ARG;
+    return make_net(cfg, &n) ? n.t.n_params : USPACE_ERR_ARG;
 }
 
 extern "C" long uspace_idnet_param_numel(const uspace_idnet_config* cfg, int index) {
     Net n;
-    if (!make_net(cfg, &n) || index < 0 || index >= (int)n.numel.size()) return -1;
-    return n.numel[index];
+    return make_net(cfg, &n) ? n.t.numel(index) : USPACE_ERR_ARG;
 }
 
 extern "C" size_t uspace_idnet_weight_bytes(const uspace_idnet_config* cfg) {
     Net n;
-    return make_net(cfg, &n) ? n.bytes : 0;
+    return make_net(cfg, &n) ? n.t.bytes() : 0;
 }
 
 extern "C" size_t uspace_idnet_workspace_bytes(const uspace_idnet_config* cfg, int B) {
@@ -569,59 +538,36 @@ extern "C" size_t uspace_idnet_workspace_bytes(const uspace_idnet_config* cfg, i
 extern "C" int uspace_idnet_pack_weights(const uspace_idnet_config* cfg, const float* const* params, int n_params, void* blob,
                                          size_t blob_bytes, uspace_stream_t stream) {
     Net n;
-    if (!make_net(cfg, &n) || !params || !blob || n_params != (int)n.numel.size()) return USPACE_ERR_ARG;
-    if (blob_bytes < n.bytes) return USPACE_ERR_WORKSPACE;
-    for (int i = 0; i < n_params; ++i)
-        if (!params[i]) return USPACE_ERR_ARG;
+    if (!make_net(cfg, &n)) return USPACE_ERR_ARG;
+    US_TRY(us_pack_table(n.t, params, n_params, blob, blob_bytes, stream));      // the checks; the PReLU slopes and the SE weights
     hipStream_t st = (hipStream_t)stream;
     float* out = (float*)blob;
-    int at = 0;     // cursor into params, state-dict order
-    // conv (+ the batch norm after it, the next four parameters, when bn)
-    auto conv = [&](const ConvSpec& c, bool bn, size_t w_off, size_t b_off) -> int {
-        const float* w = params[at++];
-        const float *g = nullptr, *b = nullptr, *m = nullptr, *v = nullptr;
-        if (bn) g = params[at], b = params[at + 1], m = params[at + 2], v = params[at + 3], at += 4;
-        const long cnt = (long)conv_kpad(c) * c.cout + c.cout;
-        hipLaunchKernelGGL(idnet_pack_conv_kernel, dim3(launch_1d(cnt)), dim3(256), 0, st, w, g, b, m, v, bn ? 1 : 0, out + w_off,
-                           out + b_off, c.cin, c.cout, c.kh, c.kw, conv_k(c), conv_kpad(c));
-        US_CHECK_LAUNCH();
-        return USPACE_OK;
+    // a convolution with the batch norm after it (the four parameters behind its weight) folded in
+    auto conv_bn = [&](const ConvSpec& c, int i_w, size_t w_off, size_t b_off) {
+        return conv_f32_pack(c, params[i_w], ConvPackSource::batch_norm(params + i_w + 1, kBnEps), out + w_off, out + b_off, st);
     };
-    auto copy = [&](size_t off, long cnt) -> int {
-        if (hipMemcpyAsync(out + off, params[at++], cnt * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return USPACE_ERR_LAUNCH;
-        return USPACE_OK;
-    };
-    hipLaunchKernelGGL(idnet_fill_kernel, dim3(launch_1d(kEmb)), dim3(256), 0, st, out + n.zeros, (long)kEmb, 0.f);
-    US_CHECK_LAUNCH();
-    US_TRY(conv(ConvSpec{3, 64, 3, 3, 1, 1, 1}, true, n.in_w, n.in_b));
-    US_TRY(copy(n.in_slope, 64));
+    if (hipMemsetAsync(out + n.zeros, 0, kEmb * sizeof(float), st) != hipSuccess) return USPACE_ERR_LAUNCH;
+    US_TRY(conv_bn(ConvSpec{3, 64, 3, 3, 1, 1, 1}, n.i_in, n.in_w, n.in_b));
     {   // output_layer: BN2d (4), Linear weight, bias, BN1d (4)
-        const float* const* p = params + at;
+        const float* const* p = params + n.i_head;
         const int hw = n.side * n.side;
-        hipLaunchKernelGGL(idnet_pack_head_w_kernel, dim3(launch_1d((long)hw * kEmb * kEmb)), dim3(256), 0, st, p[4], p[0], p[3], p[6],
-                           p[9], out + n.head_w, hw);
+        hipLaunchKernelGGL(idnet_pack_head_w_kernel, dim3((unsigned)(((long)hw * kEmb * kEmb + 255) / 256)), dim3(256), 0, st, p[4], p[0],
+                           p[3], p[6], p[9], out + n.head_w, hw);
         US_CHECK_LAUNCH();
         hipLaunchKernelGGL(idnet_pack_head_b_kernel, dim3(kEmb), dim3(64), 0, st, p[4], p[5], p[0], p[1], p[2], p[3], p[6], p[7], p[8],
                            p[9], out + n.head_b, hw);
         US_CHECK_LAUNCH();
-        at += 10;
     }
     for (const Unit& u : n.units) {
-        if (u.conv_sc) US_TRY(conv(ConvSpec{u.cin, u.d, 1, 1, u.s, 0, 0}, true, u.wsc, u.bsc));
-        hipLaunchKernelGGL(idnet_bn_affine_kernel, dim3(launch_1d(u.cin)), dim3(256), 0, st, params[at], params[at + 1], params[at + 2],
-                           params[at + 3], out + u.pre_s, out + u.pre_b, u.cin);
+        if (u.conv_sc) US_TRY(conv_bn(ConvSpec{u.cin, u.d, 1, 1, u.s, 0, 0}, u.i_sc, u.wsc, u.bsc));
+        const float* const* pre = params + u.i_pre;
+        hipLaunchKernelGGL(idnet_bn_affine_kernel, dim3(us_cdiv(u.cin, 256)), dim3(256), 0, st, pre[0], pre[1], pre[2], pre[3],
+                           out + u.pre_s, out + u.pre_b, u.cin);
         US_CHECK_LAUNCH();
-        at += 4;
-        US_TRY(conv(ConvSpec{u.cin, u.d, 3, 3, 1, 1, 1}, false, u.w1, 0));
-        US_TRY(copy(u.slope, u.d));
-        US_TRY(conv(ConvSpec{u.d, u.d, 3, 3, u.s, 1, 1}, true, u.w2, u.b2));
-        if (n.se) {
-            US_TRY(copy(u.fc1, (long)(u.d / 16) * u.d));
-            US_TRY(copy(u.fc2, (long)u.d * (u.d / 16)));
-        }
+        US_TRY(conv_f32_pack(ConvSpec{u.cin, u.d, 3, 3, 1, 1, 1}, params[u.i_w1], ConvPackSource{}, out + u.w1, nullptr, st));
+        US_TRY(conv_bn(ConvSpec{u.d, u.d, 3, 3, u.s, 1, 1}, u.i_w2, u.w2, u.b2));
     }
-    return at == n_params ? USPACE_OK : USPACE_ERR_ARG;
+    return USPACE_OK;
 }
 
 extern "C" int uspace_idnet_preprocess(const float* x, int B, int H, int W, int normalize, int crop, int out_size, float* out,
@@ -629,7 +575,7 @@ extern "C" int uspace_idnet_preprocess(const float* x, int B, int H, int W, int 
     if (!x || !out || B < 1 || H < 1 || W < 1 || out_size < 1 || out_size > 4096 || H > 16384 || W > 16384) return USPACE_ERR_ARG;
     if ((size_t)B * 3 * H * W >= ((size_t)1 << 31) || (size_t)B * 3 * out_size * out_size >= ((size_t)1 << 31)) return USPACE_ERR_ARG;
     const long cnt = (long)B * out_size * out_size;
-    hipLaunchKernelGGL(idnet_preprocess_kernel, dim3(launch_1d(cnt)), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W,
+    hipLaunchKernelGGL(idnet_preprocess_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W,
                        normalize ? 1 : 0, crop ? 1 : 0, out_size);
     US_CHECK_LAUNCH();
     return USPACE_OK;

@@ -14,6 +14,7 @@
 
 #include <vector>
 
+#include "blob.h"
 #include "common.h"
 #include "conv_f32.h"
 
@@ -21,8 +22,6 @@ namespace {
 
 constexpr int kIn = 299;              // resize target (pytorch-fid resizes every input to 299 x 299)
 constexpr double kBnEps = 1e-3;       // BatchNorm2d(eps=0.001) of torchvision's BasicConv2d
-constexpr int kNumConvs = 94;
-constexpr int kParamsPerConv = 5;     // conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var
 constexpr int kNumStages = 20;        // 0 resized input .. 18 Mixed_7c, 19 global mean
 // per-image buffer sizes (floats): P/Q hold block inputs and outputs (largest: Conv2d_2b_3x3, 147 x 147 x 64), T1-T3 the
 // branch intermediates (largest: the pooled input of Mixed_5d, 35 x 35 x 288; the resized input, 299 x 299 x 3, lives in T1)
@@ -90,49 +89,26 @@ const std::vector<ConvSpec>& conv_specs() {
     return specs;
 }
 
-// packed blob: per conv, W [K_pad, Cout] then bias [Cout], every piece starting at a multiple of 16 floats
+// The caller's parameters, per conv: conv.weight, then bn.weight, bn.bias, bn.running_mean, bn.running_var, all five folded into
+// the conv's two pieces of the blob: W [K_pad, Cout] then bias [Cout], every piece starting at a multiple of 16 floats.
 struct BlobLayout {
-    std::vector<size_t> w_off, b_off;
-    size_t floats = 0;
+    ParamTable t;
+    std::vector<size_t> w_off, b_off;     // floats
+    std::vector<int> i_w;                 // parameter index of the weight; its batch norm is i_w + 1 .. i_w + 4
 };
 const BlobLayout& blob_layout() {
     static const BlobLayout L = [] {
         BlobLayout l;
-        size_t o = 0;
+        l.t.arena.align = 16 * sizeof(float);
         for (const ConvSpec& c : conv_specs()) {
-            l.w_off.push_back(o);
-            o += ((size_t)conv_kpad(c) * c.cout + 15) & ~(size_t)15;
-            l.b_off.push_back(o);
-            o += ((size_t)c.cout + 15) & ~(size_t)15;
+            l.w_off.push_back(l.t.arena.take((size_t)conv_kpad(c) * c.cout * sizeof(float)) / sizeof(float));
+            l.b_off.push_back(l.t.arena.take(c.cout * sizeof(float)) / sizeof(float));
+            l.i_w.push_back(l.t.add((long)c.cout * c.cin * c.kh * c.kw, P_OWNER));
+            for (int j = 0; j < 4; ++j) l.t.add(c.cout, P_OWNER);
         }
-        l.floats = o;
         return l;
     }();
     return L;
-}
-
-// ---- weight packing: BN folded in fp64, rounded once to fp32; W'[k = (ty * kw + tx) * Cin + c][n], zero rows k >= K
-__global__ __launch_bounds__(256) void pack_conv_kernel(const float* __restrict__ w, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, const float* __restrict__ mean,
-                                                        const float* __restrict__ var, float* __restrict__ wout,
-                                                        float* __restrict__ bout, int cin, int cout, int kh, int kw, int K,
-                                                        int Kpad) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nw = (long)Kpad * cout;
-    if (idx < nw) {
-        const int k = (int)(idx / cout), n = (int)(idx - (long)k * cout);
-        float v = 0.f;
-        if (k < K) {
-            const int tap = k / cin, c = k - tap * cin, ty = tap / kw, tx = tap - ty * kw;
-            const double s = (double)gamma[n] / sqrt((double)var[n] + kBnEps);
-            v = (float)((double)w[(((long)n * cin + c) * kh + ty) * kw + tx] * s);
-        }
-        wout[idx] = v;
-    } else if (idx < nw + cout) {
-        const int n = (int)(idx - nw);
-        const double s = (double)gamma[n] / sqrt((double)var[n] + kBnEps);
-        bout[n] = (float)((double)beta[n] - (double)mean[n] * s);
-    }
 }
 
 // ---- input: bilinear resize (align_corners=False) of NCHW [B,3,H,W] to 299 x 299, then 2x - 1, written NHWC
@@ -456,15 +432,11 @@ int run(const void* blob, void* ws, size_t ws_bytes, const float* x, int B, int 
 
 }  // namespace
 
-extern "C" int uspace_inception_num_params(void) { return kNumConvs * kParamsPerConv; }
+extern "C" int uspace_inception_num_params(void) { return blob_layout().t.n_params; }
 
-extern "C" long uspace_inception_param_numel(int index) {
-    if (index < 0 || index >= kNumConvs * kParamsPerConv) return -1;
-    const ConvSpec& c = conv_specs()[index / kParamsPerConv];
-    return index % kParamsPerConv == 0 ? (long)c.cout * c.cin * c.kh * c.kw : (long)c.cout;
-}
+extern "C" long uspace_inception_param_numel(int index) { return blob_layout().t.numel(index); }
 
-extern "C" size_t uspace_inception_weight_bytes(void) { return blob_layout().floats * sizeof(float); }
+extern "C" size_t uspace_inception_weight_bytes(void) { return blob_layout().t.bytes(); }
 
 extern "C" size_t uspace_inception_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
@@ -473,21 +445,12 @@ extern "C" size_t uspace_inception_workspace_bytes(int B, int H, int W) {
 
 extern "C" int uspace_inception_pack_weights(const float* const* params, int n_params, void* blob, size_t blob_bytes,
                                              uspace_stream_t stream) {
-    if (!params || !blob || n_params != kNumConvs * kParamsPerConv) return USPACE_ERR_ARG;
     const BlobLayout& L = blob_layout();
-    if (blob_bytes < L.floats * sizeof(float)) return USPACE_ERR_WORKSPACE;
-    for (int i = 0; i < kNumConvs * kParamsPerConv; ++i)
-        if (!params[i]) return USPACE_ERR_ARG;
+    US_TRY(us_pack_table(L.t, params, n_params, blob, blob_bytes, stream));      // the checks: every entry is the pack step's below
     float* out = (float*)blob;
-    for (int i = 0; i < kNumConvs; ++i) {
-        const ConvSpec& c = conv_specs()[i];
-        const float* const* p = params + i * kParamsPerConv;
-        const long n = (long)conv_kpad(c) * c.cout + c.cout;
-        hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p[0], p[1],
-                           p[2], p[3], p[4], out + L.w_off[i], out + L.b_off[i], c.cin, c.cout, c.kh, c.kw, conv_k(c),
-                           conv_kpad(c));
-        US_CHECK_LAUNCH();
-    }
+    for (size_t i = 0; i < L.i_w.size(); ++i)
+        US_TRY(conv_f32_pack(conv_specs()[i], params[L.i_w[i]], ConvPackSource::batch_norm(params + L.i_w[i] + 1, kBnEps),
+                             out + L.w_off[i], out + L.b_off[i], (hipStream_t)stream));
     return USPACE_OK;
 }
 

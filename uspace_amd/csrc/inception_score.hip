@@ -61,11 +61,6 @@ __global__ __launch_bounds__(256) void logits_kernel(const float* __restrict__ x
 // ---- score statistics
 constexpr int kRowChunk = 256;      // rows per partial column sum (a constant of the summation order, not of the launch)
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ double wave_max_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));

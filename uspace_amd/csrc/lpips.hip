@@ -15,6 +15,7 @@
 
 #include <vector>
 
+#include "blob.h"
 #include "common.h"
 #include "conv_f32.h"
 
@@ -30,9 +31,12 @@ struct Net {
     std::vector<ConvSpec> convs;
     std::vector<Op> stage[kNumTaps];      // stage l + 1 of uspace_lpips_tap: the operations from tap l - 1 (or the scaled input) to tap l
     int tap_c[kNumTaps];
-    std::vector<size_t> w_off, b_off;     // packed blob (floats): per conv W [K_pad, Cout] then bias [Cout]; then lin0 .. lin4,
-    size_t lin_off[kNumTaps];             // every piece starting at a multiple of 16 floats
-    size_t floats = 0;
+    // The caller's parameters: per conv weight and bias, then lin0 .. lin4.  Packed blob (offsets in floats): per conv W [K_pad, Cout]
+    // then bias [Cout]; then the lin vectors, copied by the table; every piece starting at a multiple of 16 floats
+    ParamTable t;
+    std::vector<size_t> w_off, b_off;
+    std::vector<int> i_w;                 // parameter index of a conv's weight; its bias is i_w + 1
+    size_t lin_off[kNumTaps];
 };
 
 Net make_net(int which) {
@@ -60,19 +64,17 @@ Net make_net(int which) {
             }
         }
     }
-    size_t o = 0;
+    n.t.arena.align = 16 * sizeof(float);
     for (const ConvSpec& c : n.convs) {
-        n.w_off.push_back(o);
-        o += ((size_t)conv_kpad(c) * c.cout + 15) & ~(size_t)15;
-        n.b_off.push_back(o);
-        o += ((size_t)c.cout + 15) & ~(size_t)15;
+        n.w_off.push_back(n.t.arena.take((size_t)conv_kpad(c) * c.cout * sizeof(float)) / sizeof(float));
+        n.b_off.push_back(n.t.arena.take(c.cout * sizeof(float)) / sizeof(float));
+        n.i_w.push_back(n.t.add((long)c.cout * c.cin * c.kh * c.kw, P_OWNER));
+        n.t.add(c.cout, P_OWNER);
     }
     for (int l = 0; l < kNumTaps; ++l) {
         n.tap_c[l] = n.convs[n.stage[l].back().conv].cout;
-        n.lin_off[l] = o;
-        o += ((size_t)n.tap_c[l] + 15) & ~(size_t)15;
+        n.lin_off[l] = n.t.at(n.t.add(n.tap_c[l], P_F32)) / sizeof(float);
     }
-    n.floats = o;
     return n;
 }
 
@@ -80,8 +82,6 @@ const Net* net_of(int which) {
     static const Net nets[2] = {make_net(0), make_net(1)};
     return which == 0 || which == 1 ? &nets[which] : nullptr;
 }
-
-int num_params(const Net& n) { return 2 * (int)n.convs.size() + kNumTaps; }
 
 // What the walk produces for an H x W input: the size of every tap and the largest activation of one image (floats).
 // false where a map would vanish (an input too small for the stack).
@@ -120,31 +120,6 @@ bool walk(const Net& n, int H, int W, Walk* out) {
 }
 
 // ------------------------------------------------------------------------------------------------ small kernels
-// weight packing, bias and no batch norm: W'[k = (ty * kw + tx) * Cin + c][n] = w[n][c][ty][tx], zero rows k >= K; bias copied
-__global__ __launch_bounds__(256) void pack_conv_bias_kernel(const float* __restrict__ w, const float* __restrict__ bias,
-                                                             float* __restrict__ wout, float* __restrict__ bout, int cin, int cout,
-                                                             int kh, int kw, int K, int Kpad) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nw = (long)Kpad * cout;
-    if (idx < nw) {
-        const int k = (int)(idx / cout), n = (int)(idx - (long)k * cout);
-        float v = 0.f;
-        if (k < K) {
-            const int tap = k / cin, c = k - tap * cin, ty = tap / kw, tx = tap - ty * kw;
-            v = w[(((long)n * cin + c) * kh + ty) * kw + tx];
-        }
-        wout[idx] = v;
-    } else if (idx < nw + cout) {
-        const int n = (int)(idx - nw);
-        bout[n] = bias[n];
-    }
-}
-
-__global__ __launch_bounds__(256) void copy_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
 // the ScalingLayer of lpips: NCHW fp32 [B, 3, H, W] -> NHWC (v - shift_c) / scale_c, v = x (images in [-1, 1]) or 2 x - 1
 // (normalize: images in [0, 1]).  The shift is not folded into the first convolution: its zero padding pads this tensor.
 __global__ __launch_bounds__(256) void scale_input_kernel(const float* __restrict__ x, float* __restrict__ out, long npix, int HW,
@@ -180,12 +155,6 @@ __global__ __launch_bounds__(256) void pool2_kernel(const float* __restrict__ x,
 #pragma unroll
     for (int j = 0; j < 4; ++j) m[j] = fmaxf(fmaxf(v00[j], v01[j]), fmaxf(v10[j], v11[j]));
     *(f32x4*)(y + pix * C + c) = m;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // the four waves' sums joined in wave order; every thread passes its wave's value, thread 0 receives the sum
@@ -484,21 +453,17 @@ int run(int which, const void* blob, void* ws, size_t ws_bytes, const float* x0,
 
 extern "C" int uspace_lpips_num_params(int net) {
     const Net* n = net_of(net);
-    return n ? num_params(*n) : USPACE_ERR_ARG;
+    return n ? n->t.n_params : USPACE_ERR_ARG;
 }
 
 extern "C" long uspace_lpips_param_numel(int net, int index) {
     const Net* n = net_of(net);
-    if (!n || index < 0 || index >= num_params(*n)) return -1;
-    const int nc = (int)n->convs.size();
-    if (index >= 2 * nc) return n->tap_c[index - 2 * nc];
-    const ConvSpec& c = n->convs[index / 2];
-    return index % 2 == 0 ? (long)c.cout * c.cin * c.kh * c.kw : (long)c.cout;
+    return n ? n->t.numel(index) : USPACE_ERR_ARG;
 }
 
 extern "C" size_t uspace_lpips_weight_bytes(int net) {
     const Net* n = net_of(net);
-    return n ? n->floats * sizeof(float) : 0;
+    return n ? n->t.bytes() : 0;
 }
 
 extern "C" size_t uspace_lpips_workspace_bytes(int net, int B, int H, int W) {
@@ -511,26 +476,13 @@ extern "C" size_t uspace_lpips_workspace_bytes(int net, int B, int H, int W) {
 
 extern "C" int uspace_lpips_pack_weights(int net, const float* const* params, int n_params, void* blob, size_t blob_bytes,
                                          uspace_stream_t stream) {
-    const Net* np = net_of(net);
-    if (!np || !params || !blob || n_params != num_params(*np)) return USPACE_ERR_ARG;
-    const Net& n = *np;
-    if (blob_bytes < n.floats * sizeof(float)) return USPACE_ERR_WORKSPACE;
-    for (int i = 0; i < n_params; ++i)
-        if (!params[i]) return USPACE_ERR_ARG;
+    const Net* n = net_of(net);
+    if (!n) return USPACE_ERR_ARG;
+    US_TRY(us_pack_table(n->t, params, n_params, blob, blob_bytes, stream));      // the checks and the lin vectors
     float* out = (float*)blob;
-    const int nc = (int)n.convs.size();
-    for (int i = 0; i < nc; ++i) {
-        const ConvSpec& c = n.convs[i];
-        const long cnt = (long)conv_kpad(c) * c.cout + c.cout;
-        hipLaunchKernelGGL(pack_conv_bias_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params[2 * i],
-                           params[2 * i + 1], out + n.w_off[i], out + n.b_off[i], c.cin, c.cout, c.kh, c.kw, conv_k(c), conv_kpad(c));
-        US_CHECK_LAUNCH();
-    }
-    for (int l = 0; l < kNumTaps; ++l) {
-        hipLaunchKernelGGL(copy_f32_kernel, dim3(us_cdiv(n.tap_c[l], 256)), dim3(256), 0, (hipStream_t)stream, params[2 * nc + l],
-                           out + n.lin_off[l], n.tap_c[l]);
-        US_CHECK_LAUNCH();
-    }
+    for (size_t i = 0; i < n->convs.size(); ++i)
+        US_TRY(conv_f32_pack(n->convs[i], params[n->i_w[i]], ConvPackSource::with_bias(params[n->i_w[i] + 1]), out + n->w_off[i],
+                             out + n->b_off[i], (hipStream_t)stream));
     return USPACE_OK;
 }
 

@@ -40,8 +40,7 @@ __global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x,
         const double v = (double)p[k];
         s = __fma_rn(v, v, s);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum_f64(s);
     if (lane == 0) out[r] = s;
 }
 
@@ -307,8 +306,7 @@ struct PolyConsumer {
     }
     __device__ void finish(double* scratch) {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        sum = wave_sum_f64(sum);
         __syncthreads();
         if (lane == 0) scratch[wave] = sum;
         __syncthreads();

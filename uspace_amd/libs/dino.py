@@ -201,6 +201,9 @@ class DinoVisionTransformer(nn.Module):
         pos = self.embeddings.position_embeddings
         return [self.position_table() if p is pos else p for p in self.parameters()]
 
+    def _packed_blob(self, device):
+        return self._packed.blob(device)
+
     def _c_cfg(self):
         c = self.cfg
         return _hip.DinoConfig(c["image"], c["patch"], c["dim"], c["heads"], c["layers"], c["ffn"], c["layerscale"], c["eps"])

@@ -149,6 +149,9 @@ class LPIPS(nn.Module):
     def _canonical_params(self):
         return list(self.state_dict().values())
 
+    def _packed_blob(self, device):
+        return self._packed.blob(device)
+
     def _workspace(self, B, H, W, device):
         nbytes = _hip.lib().uspace_lpips_workspace_bytes(NETS[self.net], B, H, W)
         if nbytes == 0:
