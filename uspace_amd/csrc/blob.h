@@ -1,8 +1,8 @@
 // One layout for every model's packed weights and workspaces (host side only): the aligned arena, the parameter table and
 // the loop that packs fp32 checkpoint tensors into a device blob.  Every model describes its parameters with a ParamTable and serves
-// num_params / param_numel / weight_bytes / pack_weights from it: uvit.hip, vae.hip (both halves), clip.hip and clip_vision.hip (the two
-// towers' layers through clip_encoder.h), dino.hip, and the fp32 convolution towers inception.hip, lpips.hip and idnet.hip, whose
-// convolutions and batch norms are P_OWNER entries that conv_f32.h's pack step writes.
+// num_params / param_numel / weight_bytes / pack_weights from it: uvit.hip, vae.hip (both halves), clip.hip, clip_vision.hip and dino.hip
+// (their layers through vit_encoder.h, the patch weight through vit_embed.h), and the fp32 convolution towers inception.hip, lpips.hip
+// and idnet.hip, whose convolutions and batch norms are P_OWNER entries that conv_f32.h's pack step writes.
 #pragma once
 #include <vector>
 
@@ -56,6 +56,7 @@ struct ParamTable {
         return (int)p.size() - 1;
     }
     size_t at(int i) const { return p[i].offset; }
+    size_t put(long numel, PKind k) { return at(add(numel, k)); }   // add, and the offset it got
     size_t bytes() const { return arena.off; }
     long numel(int i) const { return (i < 0 || i >= n_params) ? (long)USPACE_ERR_ARG : p[i].numel; }
 };

@@ -1,11 +1,11 @@
 // CLIP text transformer (the encoder behind the reference's FrozenCLIPEmbedder, libs/clip.py:40-91: HF
 // CLIPTextModel(input_ids).last_hidden_state) on the kernels of this library: token + position table lookup,
-// the pre-LN blocks of clip_encoder.h (shared with clip_vision.hip) with CAUSAL attention, final LayerNorm.
+// the pre-LN blocks of vit_encoder.h (shared with clip_vision.hip and dino.hip) with CAUSAL attention, final LayerNorm.
 // One-off per prompt on the sampling path; kept resident so repeated prompts cost one launch
 // sequence instead of re-instantiating the encoder (tools/utils_t2i.py:25-39 does that on every call).
 #include <vector>
 
-#include "clip_encoder.h"
+#include "vit_encoder.h"
 
 namespace {
 
@@ -13,33 +13,30 @@ namespace {
 struct ClipModel {
     ParamTable t;
     size_t tok, pos, fg, fb;
-    std::vector<ClipEncLayer> layers;
+    std::vector<VitEncLayer> layers;
 };
 
 bool valid_clip(const uspace_clip_config* c) {
-    if (!c || c->vocab <= 0 || c->dim <= 0 || c->heads <= 0 || c->layers < 0 || c->ffn <= 0 || c->max_pos <= 0) return false;
-    if (c->dim != c->heads * 64 || (c->dim & 63) || (c->ffn & 63) || c->dim > 4096) return false;   // head_dim 64, K % 64
-    if (c->max_pos > 160) return false;                                                              // causal kernel: <= 10 key tiles
-    return true;
+    if (!c || !vit_enc_valid(c->dim, c->heads, c->layers, c->ffn)) return false;
+    return c->vocab > 0 && c->max_pos > 0 && c->max_pos <= 160;   // causal kernel: <= 10 key tiles
 }
 
-// HF state_dict order: embeddings.{token,position}_embedding.weight; the layers (clip_encoder.h); final_layer_norm.*
+// HF state_dict order: embeddings.{token,position}_embedding.weight; the layers (vit_encoder.h); final_layer_norm.*
 ClipModel build_clip(const uspace_clip_config& c) {
     ClipModel m;
     ParamTable& t = m.t;
-    auto put = [&t](long numel, PKind k) { return t.at(t.add(numel, k)); };
     const long D = c.dim;
-    m.tok = put((long)c.vocab * D, P_F32);
-    m.pos = put((long)c.max_pos * D, P_F32);
-    for (int i = 0; i < c.layers; ++i) m.layers.push_back(clip_enc_add_layer(t, D, c.ffn));
-    m.fg = put(D, P_F32);
-    m.fb = put(D, P_F32);
+    m.tok = t.put((long)c.vocab * D, P_F32);
+    m.pos = t.put((long)c.max_pos * D, P_F32);
+    for (int i = 0; i < c.layers; ++i) m.layers.push_back(vit_enc_add_layer(t, D, c.ffn, VIT_ORDER_CLIP, false));
+    m.fg = t.put(D, P_F32);
+    m.fb = t.put(D, P_F32);
     return m;
 }
 
 struct ClipWs {
     size_t x;
-    ClipEncWs enc;
+    VitEncWs enc;
     size_t total;
 };
 ClipWs plan_clip_ws(const uspace_clip_config& c, int B) {
@@ -47,7 +44,7 @@ ClipWs plan_clip_ws(const uspace_clip_config& c, int B) {
     Arena a;
     const size_t M = (size_t)B * c.max_pos, D = c.dim;
     w.x = a.take(M * D * 4);
-    w.enc = clip_enc_take_ws(a, M, D, (size_t)c.ffn);
+    w.enc = vit_enc_take_ws(a, M, D, (size_t)c.ffn);
     w.total = a.off;
     return w;
 }
@@ -86,8 +83,9 @@ extern "C" int uspace_clip_text_forward(const uspace_clip_config* cfg, const voi
     auto PF = [&](size_t off) { return (const float*)(wb + off); };
     US_TRY(uspace_table_embed(ids, PF(m.tok), PF(m.pos), x, B, L, D, cfg->vocab, stream));
     // stop_after_layer: -1 = whole model incl. final norm; k >= 0: hidden state after k layers (0 = embeddings), no final norm
-    US_TRY(clip_enc_layers(m.layers, stop_after_layer, blob, workspace, w.enc, x, B, L, D, cfg->ffn, cfg->heads, cfg->eps, true,
-                           stream));
+    const VitEncRun run = {D, cfg->ffn, cfg->heads, cfg->eps, /*causal=*/true, /*erf_gelu=*/false};
+    const int n = stop_after_layer < 0 ? cfg->layers : stop_after_layer;
+    US_TRY(vit_enc_layers(m.layers, n, run, blob, workspace, w.enc, x, B, L, -1, nullptr, stream));
     if (stop_after_layer >= 0) {
         if (hipMemcpyAsync(out, x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return USPACE_ERR_LAUNCH;
         return USPACE_OK;

@@ -1,13 +1,14 @@
 // CLIP's image side and the CLIP score (HF CLIPVisionModelWithProjection + the cosine of CLIPModel): image preprocessing
 // (save_image quantisation, antialiased bicubic resize, mean / std), the vision tower on the kernels of this library -- patch rows ->
-// uspace_gemm_bf16, class token + position table, pre_layrnorm, the pre-LN blocks of clip_encoder.h (shared with clip.hip) with NON-causal
-// attention, post_layernorm of token 0, visual_projection -- and the small fp32 pieces of the metric: a no-bias fp32 linear for the two
-// projections, a row gather for the text pooling, the cosine and the normalised difference of the directional (editing) similarity.
+// uspace_gemm_bf16, class token + position table (the front of vit_embed.h, shared with dino.hip), pre_layrnorm, the pre-LN blocks of
+// vit_encoder.h (shared with clip.hip and dino.hip) with NON-causal attention, post_layernorm of token 0, visual_projection -- and the
+// small fp32 pieces of the metric: a no-bias fp32 linear for the two projections, a row gather for the text pooling, the cosine and
+// the normalised difference of the directional (editing) similarity.
 // Every reduction runs in a fixed order inside one wave or one block: no atomics, run-to-run bit-equal.
 #include <vector>
 
-#include "clip_encoder.h"
 #include "vit_embed.h"
+#include "vit_encoder.h"
 
 namespace {
 
@@ -169,56 +170,47 @@ __global__ __launch_bounds__(256) void normalized_diff_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------------------- the model
 struct VModel {
     ParamTable t;
-    size_t cls, patch, pos, preg, preb, postg, postb, proj;
-    std::vector<ClipEncLayer> layers;
+    size_t cls, pos, preg, preb, postg, postb, proj;
+    VitPatchWeight patch;
+    std::vector<VitEncLayer> layers;
 };
 
-int patch_k(const uspace_clipv_config& c) { return 3 * c.patch * c.patch; }
-int patch_kp(const uspace_clipv_config& c) { return (patch_k(c) + 63) / 64 * 64; }
-int n_patches(const uspace_clipv_config& c) { return (c.image / c.patch) * (c.image / c.patch); }
-
 bool valid_clipv(const uspace_clipv_config* c) {
-    if (!c || c->image <= 0 || c->patch <= 0 || c->dim <= 0 || c->heads <= 0 || c->layers < 0 || c->ffn <= 0 || c->proj_dim <= 0) return false;
-    if (c->dim != c->heads * 64 || (c->dim & 63) || (c->ffn & 63) || c->dim > 4096 || (c->proj_dim & 3)) return false;
-    if (c->image % c->patch || c->image > 4096 || c->patch > 256) return false;
-    return true;
+    if (!c || !vit_enc_valid(c->dim, c->heads, c->layers, c->ffn) || !vit_patch_valid(c->image, c->patch)) return false;
+    return c->proj_dim > 0 && !(c->proj_dim & 3);
 }
 
 // HF CLIPVisionModelWithProjection.state_dict() order (see the header)
 VModel build_clipv(const uspace_clipv_config& c) {
     VModel m;
     ParamTable& t = m.t;
-    auto put = [&t](long numel, PKind k) { return t.at(t.add(numel, k)); };
-    const long D = c.dim, K = patch_k(c), Kp = patch_kp(c);
-    m.cls = put(D, P_F32);
-    // patch weight [D, K] fp32 -> bf16 [D, Kp]: the region is Kp wide, the cast fills K of every row (the forward's pack step)
-    m.patch = t.arena.take((size_t)D * Kp * 2);
-    t.add_at(m.patch, D * K, P_BF16);
-    m.pos = put((long)(n_patches(c) + 1) * D, P_F32);
-    m.preg = put(D, P_F32);
-    m.preb = put(D, P_F32);
-    for (int i = 0; i < c.layers; ++i) m.layers.push_back(clip_enc_add_layer(t, D, c.ffn));
-    m.postg = put(D, P_F32);
-    m.postb = put(D, P_F32);
-    m.proj = put((long)c.proj_dim * D, P_F32);
+    const VitPatch g = vit_patch(c);
+    const long D = c.dim;
+    m.cls = t.put(D, P_F32);
+    m.patch = vit_patch_add_weight(t, g);
+    m.pos = t.put((long)g.tokens() * D, P_F32);
+    m.preg = t.put(D, P_F32);
+    m.preb = t.put(D, P_F32);
+    for (int i = 0; i < c.layers; ++i) m.layers.push_back(vit_enc_add_layer(t, D, c.ffn, VIT_ORDER_CLIP, false));
+    m.postg = t.put(D, P_F32);
+    m.postb = t.put(D, P_F32);
+    m.proj = t.put((long)c.proj_dim * D, P_F32);
     return m;
 }
 
 struct VWs {
-    size_t x, e, pe, rows;
-    ClipEncWs enc;
-    size_t tok0, pool, total;
+    size_t x, e;   // the residual stream; the embeddings before pre_layrnorm (the "embeddings" tap)
+    VitTowerWs vit;
+    size_t pool, total;   // pooler_output when the caller takes none
 };
 VWs plan_clipv_ws(const uspace_clipv_config& c, int B) {
     VWs w;
     Arena a;
-    const size_t N = n_patches(c), M = (size_t)B * (N + 1), D = c.dim;
+    const VitPatch g = vit_patch(c);
+    const size_t M = (size_t)B * g.tokens(), D = c.dim;
     w.x = a.take(M * D * 4);
     w.e = a.take(M * D * 4);
-    w.pe = a.take((size_t)B * N * D * 4);
-    w.rows = a.take((size_t)B * N * patch_kp(c) * 2);
-    w.enc = clip_enc_take_ws(a, M, D, (size_t)c.ffn);
-    w.tok0 = a.take((size_t)B * D * 4);
+    w.vit = vit_tower_take_ws(a, g, (size_t)B, (size_t)c.ffn);
     w.pool = a.take((size_t)B * D * 4);
     w.total = a.off;
     return w;
@@ -235,8 +227,8 @@ extern "C" long uspace_clipv_param_numel(const uspace_clipv_config* cfg, int ind
 }
 
 extern "C" size_t uspace_clipv_weight_bytes(const uspace_clipv_config* cfg) {
-    // + one dense bf16 copy of the patch weight behind the table: the staging area of the pad step
-    return valid_clipv(cfg) ? build_clipv(*cfg).t.bytes() + us_align_up((size_t)cfg->dim * patch_k(*cfg) * 2) : 0;
+    // + the staging area of the patch weight's pad step behind the table
+    return valid_clipv(cfg) ? build_clipv(*cfg).t.bytes() + vit_patch_stage_bytes(vit_patch(*cfg)) : 0;
 }
 
 extern "C" size_t uspace_clipv_workspace_bytes(const uspace_clipv_config* cfg, int B) {
@@ -246,18 +238,8 @@ extern "C" size_t uspace_clipv_workspace_bytes(const uspace_clipv_config* cfg, i
 extern "C" int uspace_clipv_pack_weights(const uspace_clipv_config* cfg, const float* const* params, int n_params, void* blob,
                                          size_t blob_bytes, uspace_stream_t stream) {
     if (!valid_clipv(cfg)) return USPACE_ERR_ARG;
-    if (blob && blob_bytes < uspace_clipv_weight_bytes(cfg)) return USPACE_ERR_WORKSPACE;
     VModel m = build_clipv(*cfg);
-    // the shared loop casts the patch weight densely ([D, K]); it goes to the staging area behind the table and is then
-    // spread to rows of Kp with zero pad columns
-    const int K = patch_k(*cfg), Kp = patch_kp(*cfg);
-    const size_t stage = m.t.bytes();
-    m.t.p[1].offset = stage;
-    US_TRY(us_pack_table(m.t, params, n_params, blob, blob_bytes, stream));
-    hipLaunchKernelGGL(pad_patch_rows_kernel, dim3(cfg->dim), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)((char*)blob + stage),
-                       (bf16_t*)((char*)blob + m.patch), K, Kp);
-    US_CHECK_LAUNCH();
-    return USPACE_OK;
+    return vit_pack_table(m.t, vit_patch(*cfg), m.patch, params, n_params, blob, blob_bytes, stream);
 }
 
 extern "C" int uspace_clipv_forward(const uspace_clipv_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
@@ -272,35 +254,25 @@ extern "C" int uspace_clipv_forward(const uspace_clipv_config* cfg, const void* 
     const char* wb = (const char*)blob;
     char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
-    const int D = cfg->dim, G = cfg->image / cfg->patch, N = G * G, T = N + 1, M = B * T;
-    const int K = patch_k(*cfg), Kp = patch_kp(*cfg);
+    const VitPatch g = vit_patch(*cfg);
+    const int D = cfg->dim, T = g.tokens(), M = B * T;
     float* x = (float*)(ws + w.x);
     float* e = (float*)(ws + w.e);
-    float* pe = (float*)(ws + w.pe);
-    uint16_t* rows = (uint16_t*)(ws + w.rows);
-    float* tok0 = (float*)(ws + w.tok0);
     float* pool = pooler_output ? pooler_output : (float*)(ws + w.pool);
     auto PF = [&](size_t off) { return (const float*)(wb + off); };
-    auto PH = [&](size_t off) { return (const uint16_t*)(wb + off); };
     auto dump = [&](const float* src) {
         return hipMemcpyAsync(tap_out, src, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s) == hipSuccess ? USPACE_OK : USPACE_ERR_LAUNCH;
     };
 
-    hipLaunchKernelGGL(patch_rows_kernel, dim3(B * N), dim3(256), 0, s, pixel_values, rows, cfg->image, cfg->patch, G, K, Kp);
-    US_CHECK_LAUNCH();
-    US_TRY(uspace_gemm_bf16(rows, Kp, nullptr, 0, Kp, PH(m.patch), Kp, B * N, D, Kp, USPACE_EPI_OUT_F32, nullptr, nullptr, 0, pe, D,
-                            nullptr, 0, stream));
-    hipLaunchKernelGGL(assemble_tokens_kernel, dim3(M), dim3(256), 0, s, pe, PF(m.cls), PF(m.pos), e, T, D);
-    US_CHECK_LAUNCH();
+    US_TRY(vit_embed(g, (const uint16_t*)(wb + m.patch.offset), nullptr, PF(m.cls), PF(m.pos), workspace, w.vit, pixel_values, e, B,
+                     stream));
     // stop_after_layer: -1 = the whole model; -2 = the embeddings before pre_layrnorm; k >= 0 = the hidden state after k layers
     if (stop_after_layer == -2) return dump(e);
     US_TRY(uspace_layernorm_f32(e, PF(m.preg), PF(m.preb), x, M, D, cfg->eps, stream));
-    US_TRY(clip_enc_layers(m.layers, stop_after_layer, blob, workspace, w.enc, x, B, T, D, cfg->ffn, cfg->heads, cfg->eps, false,
-                           stream));
+    const VitEncRun run = {D, cfg->ffn, cfg->heads, cfg->eps, /*causal=*/false, /*erf_gelu=*/false};
+    US_TRY(vit_enc_layers(m.layers, tap ? stop_after_layer : cfg->layers, run, blob, workspace, w.vit.enc, x, B, T, -1, nullptr, stream));
     if (tap) return dump(x);
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, s, x, (const int*)nullptr, tok0, T, D);
-    US_CHECK_LAUNCH();
-    US_TRY(uspace_layernorm_f32(tok0, PF(m.postg), PF(m.postb), pool, B, D, cfg->eps, stream));
+    US_TRY(vit_class_token_norm(x, workspace, w.vit, PF(m.postg), PF(m.postb), pool, B, T, D, cfg->eps, stream));
     return uspace_linear_f32(pool, PF(m.proj), image_embeds, B, cfg->proj_dim, D, stream);
 }
 

@@ -168,7 +168,7 @@ int us_gemm_bf16_ext(const uint16_t* A, int lda, const uint16_t* A2, int lda2, i
 int us_gemm_part_slots_k(int M, int N, int K, bool sk_on);
 size_t us_gemm_sk_ws_bytes(int M, int N, int K, bool sk_on);
 
-// The attention of a block at any length (attention_long.hip; used by uvit.hip and clip_encoder.h, not exported): the resident kernel
+// The attention of a block at any length (attention_long.hip; used by uvit.hip and vit_encoder.h, not exported): the resident kernel
 // wherever uspace_attention_plan takes the shape, the streaming kernel beyond.  key_scale may be NULL.
 int us_attention_any(const uint16_t* qkv, const float* key_scale, uint16_t* out, int B, int L, int H, uspace_stream_t stream);
 

@@ -1,85 +1,45 @@
 // The DINO image towers (HF Dinov2Model; with layerscale = 0 a plain pre-LN ViT such as HF ViTModel / DINO v1) and the structure
-// distance of an edit.  The tower runs on the kernels of this library: patch rows -> uspace_gemm_bf16 with the patch bias, class token
-// + position table (vit_embed.h, shared with clip_vision.hip), then per layer LN1 -> q|k|v -> non-causal attention -> out projection
-// (+ residual) -> LN2 -> fc1 with the erf-GELU epilogue -> fc2 (+ residual): seven launches, and the final LayerNorm of the class
-// token.  LayerScale is folded into the out projection and fc2 when the blob is packed: W' = bf16(lambda[n] W[n, k]) from the fp32
-// checkpoint values (one rounding), b' = lambda[n] b[n]; the forward never sees lambda.  The position table arrives already
-// interpolated to image / patch (the host does that once, in torch).
+// distance of an edit.  The tower runs through the two headers it shares with the CLIP towers: the front of vit_embed.h (patch rows ->
+// the patch GEMM with the patch bias, class token + position table; the padded patch weight; the final LayerNorm of the class token)
+// and the layers of vit_encoder.h (LN1 -> q|k|v -> non-causal attention -> out projection (+ residual) -> LN2 -> fc1 with the erf-GELU
+// epilogue -> fc2 (+ residual): seven launches, and the copy of one layer's keys).  LayerScale is folded into the out projection and
+// fc2 when the blob is packed: W' = bf16(lambda[n] W[n, k]) from the fp32 checkpoint values (one rounding), b' = lambda[n] b[n]; the
+// forward never sees lambda.  The position table arrives already interpolated to image / patch (the host does that once, in torch).
 // The structure distance compares the cosine self-similarity matrices of two key sets tile by tile on the bf16 matrix cores; neither
 // T x T matrix is stored, and every sum has one fixed order (no atomics).
 #include <vector>
 
-#include "clip_encoder.h"
 #include "vit_embed.h"
+#include "vit_encoder.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------- the model
-struct DinoLayer {
-    size_t ln1g, ln1b, wqkv, bqkv, wo, bo, ln2g, ln2b, w1, b1, w2, b2;
-    int i_wo, i_bo, i_ls1, i_w2, i_b2, i_ls2;   // parameter indices of the LayerScale fold (i_ls* = -1 without LayerScale)
-};
-
 struct DModel {
     ParamTable t;
-    size_t cls, pos, patch, patchb, ng, nb;
-    int i_patch;
-    std::vector<DinoLayer> layers;
+    size_t cls, pos, patchb, ng, nb;
+    VitPatchWeight patch;
+    std::vector<VitEncLayer> layers;
 };
 
-int patch_k(const uspace_dino_config& c) { return 3 * c.patch * c.patch; }
-int patch_kp(const uspace_dino_config& c) { return (patch_k(c) + 63) / 64 * 64; }
-int n_patches(const uspace_dino_config& c) { return (c.image / c.patch) * (c.image / c.patch); }
-
 bool valid_dino(const uspace_dino_config* c) {
-    if (!c || c->image <= 0 || c->patch <= 0 || c->dim <= 0 || c->heads <= 0 || c->layers < 0 || c->ffn <= 0) return false;
-    if (c->dim != c->heads * 64 || (c->dim & 63) || (c->ffn & 63) || c->dim > 4096) return false;
-    if (c->image % c->patch || c->image > 4096 || c->patch > 256) return false;
-    if (c->layerscale != 0 && c->layerscale != 1) return false;
-    return true;
+    if (!c || !vit_enc_valid(c->dim, c->heads, c->layers, c->ffn) || !vit_patch_valid(c->image, c->patch)) return false;
+    return c->layerscale == 0 || c->layerscale == 1;
 }
 
 // HF Dinov2Model.state_dict() order without mask_token (see the header)
 DModel build_dino(const uspace_dino_config& c) {
     DModel m;
     ParamTable& t = m.t;
-    auto put = [&t](long numel, PKind k) { return t.at(t.add(numel, k)); };
-    const long D = c.dim, F = c.ffn, K = patch_k(c), Kp = patch_kp(c);
-    m.cls = put(D, P_F32);
-    m.pos = put((long)(n_patches(c) + 1) * D, P_F32);
-    // patch weight [D, K] fp32 -> bf16 [D, Kp]: the region is Kp wide, the cast fills K of every row (the pack step pads)
-    m.patch = t.arena.take((size_t)D * Kp * 2);
-    m.i_patch = t.add_at(m.patch, D * K, P_BF16);
-    m.patchb = put(D, P_F32);
-    for (int i = 0; i < c.layers; ++i) {
-        DinoLayer l;
-        l.ln1g = put(D, P_F32);
-        l.ln1b = put(D, P_F32);
-        // packed projection rows q | k | v (the attention kernel's layout), which is also HF's order here
-        l.wqkv = t.arena.take(3 * D * D * 2);
-        l.bqkv = t.arena.take(3 * D * 4);
-        for (int slot = 0; slot < 3; ++slot) {
-            t.add_at(l.wqkv + slot * D * D * 2, D * D, P_BF16);
-            t.add_at(l.bqkv + slot * D * 4, D, P_F32);
-        }
-        l.i_wo = t.add(D * D, P_BF16);
-        l.i_bo = t.add(D, P_F32);
-        l.i_ls1 = c.layerscale ? t.add(D, P_F32) : -1;
-        l.ln2g = put(D, P_F32);
-        l.ln2b = put(D, P_F32);
-        l.w1 = put(F * D, P_BF16);
-        l.b1 = put(F, P_F32);
-        l.i_w2 = t.add(D * F, P_BF16);
-        l.i_b2 = t.add(D, P_F32);
-        l.i_ls2 = c.layerscale ? t.add(D, P_F32) : -1;
-        l.wo = t.at(l.i_wo);
-        l.bo = t.at(l.i_bo);
-        l.w2 = t.at(l.i_w2);
-        l.b2 = t.at(l.i_b2);
-        m.layers.push_back(l);
-    }
-    m.ng = put(D, P_F32);
-    m.nb = put(D, P_F32);
+    const VitPatch g = vit_patch(c);
+    const long D = c.dim;
+    m.cls = t.put(D, P_F32);
+    m.pos = t.put((long)g.tokens() * D, P_F32);
+    m.patch = vit_patch_add_weight(t, g);
+    m.patchb = t.put(D, P_F32);
+    for (int i = 0; i < c.layers; ++i) m.layers.push_back(vit_enc_add_layer(t, D, c.ffn, VIT_ORDER_DINOV2, c.layerscale != 0));
+    m.ng = t.put(D, P_F32);
+    m.nb = t.put(D, P_F32);
     return m;
 }
 
@@ -94,19 +54,16 @@ __global__ __launch_bounds__(256) void fold_layerscale_kernel(const float* __res
 }
 
 struct DWs {
-    size_t x, pe, rows;
-    ClipEncWs enc;
-    size_t tok0, total;
+    size_t x;
+    VitTowerWs vit;
+    size_t total;
 };
 DWs plan_dino_ws(const uspace_dino_config& c, int B) {
     DWs w;
     Arena a;
-    const size_t N = n_patches(c), M = (size_t)B * (N + 1), D = c.dim;
-    w.x = a.take(M * D * 4);
-    w.pe = a.take((size_t)B * N * D * 4);
-    w.rows = a.take((size_t)B * N * patch_kp(c) * 2);
-    w.enc = clip_enc_take_ws(a, M, D, (size_t)c.ffn);
-    w.tok0 = a.take((size_t)B * D * 4);
+    const VitPatch g = vit_patch(c);
+    w.x = a.take((size_t)B * g.tokens() * c.dim * 4);
+    w.vit = vit_tower_take_ws(a, g, (size_t)B, (size_t)c.ffn);
     w.total = a.off;
     return w;
 }
@@ -212,8 +169,8 @@ extern "C" long uspace_dino_param_numel(const uspace_dino_config* cfg, int index
 }
 
 extern "C" size_t uspace_dino_weight_bytes(const uspace_dino_config* cfg) {
-    // + one dense bf16 copy of the patch weight behind the table: the staging area of the pad step
-    return valid_dino(cfg) ? build_dino(*cfg).t.bytes() + us_align_up((size_t)cfg->dim * patch_k(*cfg) * 2) : 0;
+    // + the staging area of the patch weight's pad step behind the table
+    return valid_dino(cfg) ? build_dino(*cfg).t.bytes() + vit_patch_stage_bytes(vit_patch(*cfg)) : 0;
 }
 
 extern "C" size_t uspace_dino_workspace_bytes(const uspace_dino_config* cfg, int B) {
@@ -223,19 +180,14 @@ extern "C" size_t uspace_dino_workspace_bytes(const uspace_dino_config* cfg, int
 extern "C" int uspace_dino_pack_weights(const uspace_dino_config* cfg, const float* const* params, int n_params, void* blob,
                                         size_t blob_bytes, uspace_stream_t stream) {
     if (!valid_dino(cfg)) return USPACE_ERR_ARG;
-    if (blob && blob_bytes < uspace_dino_weight_bytes(cfg)) return USPACE_ERR_WORKSPACE;
     DModel m = build_dino(*cfg);
     hipStream_t s = (hipStream_t)stream;
-    const int K = patch_k(*cfg), Kp = patch_kp(*cfg), D = cfg->dim, F = cfg->ffn;
-    const size_t stage = m.t.bytes();
-    m.t.p[m.i_patch].offset = stage;
-    US_TRY(us_pack_table(m.t, params, n_params, blob, blob_bytes, stream));
+    const int D = cfg->dim, F = cfg->ffn;
+    US_TRY(vit_pack_table(m.t, vit_patch(*cfg), m.patch, params, n_params, blob, blob_bytes, stream));
     char* wb = (char*)blob;
-    hipLaunchKernelGGL(pad_patch_rows_kernel, dim3(D), dim3(256), 0, s, (const bf16_t*)(wb + stage), (bf16_t*)(wb + m.patch), K, Kp);
-    US_CHECK_LAUNCH();
     if (cfg->layerscale) {
         // over the plain casts the table loop just made: the branch's last linear with lambda folded in, from the fp32 values
-        for (const DinoLayer& l : m.layers) {
+        for (const VitEncLayer& l : m.layers) {
             hipLaunchKernelGGL(fold_layerscale_kernel, dim3(D), dim3(256), 0, s, params[l.i_wo], params[l.i_bo], params[l.i_ls1],
                                (bf16_t*)(wb + l.wo), (float*)(wb + l.bo), D);
             US_CHECK_LAUNCH();
@@ -263,51 +215,22 @@ extern "C" int uspace_dino_forward(const uspace_dino_config* cfg, const void* bl
     const DWs w = plan_dino_ws(*cfg, B);
     if (workspace_bytes < w.total) return USPACE_ERR_WORKSPACE;
     const char* wb = (const char*)blob;
-    char* ws = (char*)workspace;
-    hipStream_t s = (hipStream_t)stream;
-    const int D = cfg->dim, F = cfg->ffn, G = cfg->image / cfg->patch, N = G * G, T = N + 1, M = B * T;
-    const int K = patch_k(*cfg), Kp = patch_kp(*cfg);
-    float* x = (float*)(ws + w.x);
-    float* pe = (float*)(ws + w.pe);
-    uint16_t* rows = (uint16_t*)(ws + w.rows);
-    uint16_t* h = (uint16_t*)(ws + w.enc.h);
-    uint16_t* qkv = (uint16_t*)(ws + w.enc.qkv);
-    uint16_t* att = (uint16_t*)(ws + w.enc.att);
-    uint16_t* f = (uint16_t*)(ws + w.enc.f);
-    float* tok0 = (float*)(ws + w.tok0);
+    const VitPatch g = vit_patch(*cfg);
+    const int D = cfg->dim, T = g.tokens();
+    float* x = (float*)((char*)workspace + w.x);
     auto PF = [&](size_t off) { return (const float*)(wb + off); };
-    auto PH = [&](size_t off) { return (const uint16_t*)(wb + off); };
-    constexpr int B_ = USPACE_EPI_BIAS, G_ = USPACE_EPI_GELU, R_ = USPACE_EPI_RESIDUAL, F_ = USPACE_EPI_OUT_F32,
-                  H_ = USPACE_EPI_OUT_BF16;
 
-    hipLaunchKernelGGL(patch_rows_kernel, dim3(B * N), dim3(256), 0, s, pixel_values, rows, cfg->image, cfg->patch, G, K, Kp);
-    US_CHECK_LAUNCH();
-    US_TRY(uspace_gemm_bf16(rows, Kp, nullptr, 0, Kp, PH(m.patch), Kp, B * N, D, Kp, B_ | F_, PF(m.patchb), nullptr, 0, pe, D, nullptr,
-                            0, stream));
-    hipLaunchKernelGGL(assemble_tokens_kernel, dim3(M), dim3(256), 0, s, pe, PF(m.cls), PF(m.pos), x, T, D);
-    US_CHECK_LAUNCH();
-    for (int i = 0; i < n_run; ++i) {
-        const DinoLayer& l = m.layers[i];
-        US_TRY(uspace_layernorm_f32_bf16(x, PF(l.ln1g), PF(l.ln1b), h, M, D, cfg->eps, stream));
-        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(l.wqkv), D, M, 3 * D, D, B_ | H_, PF(l.bqkv), nullptr, 0, nullptr, 0, qkv, 3 * D,
-                                stream));
-        if (i == key_layer &&
-            hipMemcpy2DAsync(keys_out, (size_t)D * 2, qkv + D, (size_t)3 * D * 2, (size_t)D * 2, M, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return USPACE_ERR_LAUNCH;
-        US_TRY(us_attention_any(qkv, nullptr, att, B, T, cfg->heads, stream));
-        US_TRY(uspace_gemm_bf16(att, D, nullptr, 0, D, PH(l.wo), D, M, D, D, B_ | R_ | F_, PF(l.bo), x, D, x, D, nullptr, 0, stream));
-        US_TRY(uspace_layernorm_f32_bf16(x, PF(l.ln2g), PF(l.ln2b), h, M, D, cfg->eps, stream));
-        US_TRY(uspace_gemm_bf16(h, D, nullptr, 0, D, PH(l.w1), D, M, F, D, B_ | G_ | H_, PF(l.b1), nullptr, 0, nullptr, 0, f, F, stream));
-        US_TRY(uspace_gemm_bf16(f, F, nullptr, 0, F, PH(l.w2), F, M, D, F, B_ | R_ | F_, PF(l.b2), x, D, x, D, nullptr, 0, stream));
-    }
+    US_TRY(vit_embed(g, (const uint16_t*)(wb + m.patch.offset), PF(m.patchb), PF(m.cls), PF(m.pos), workspace, w.vit, pixel_values, x, B,
+                     stream));
+    const VitEncRun run = {D, cfg->ffn, cfg->heads, cfg->eps, /*causal=*/false, /*erf_gelu=*/true};
+    US_TRY(vit_enc_layers(m.layers, n_run, run, blob, workspace, w.vit.enc, x, B, T, key_layer, keys_out, stream));
     if (stopped) {
-        if (tap_out && hipMemcpyAsync(tap_out, x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return USPACE_ERR_LAUNCH;
+        if (tap_out && hipMemcpyAsync(tap_out, x, (size_t)B * T * D * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+            return USPACE_ERR_LAUNCH;
         return USPACE_OK;
     }
     if (!pooler_output) return USPACE_OK;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, s, x, (const int*)nullptr, tok0, T, D);
-    US_CHECK_LAUNCH();
-    return uspace_layernorm_f32(tok0, PF(m.ng), PF(m.nb), pooler_output, B, D, cfg->eps, stream);
+    return vit_class_token_norm(x, workspace, w.vit, PF(m.ng), PF(m.nb), pooler_output, B, T, D, cfg->eps, stream);
 }
 
 extern "C" size_t uspace_self_similarity_mse_workspace_bytes(int P, int T) {

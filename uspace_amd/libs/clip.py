@@ -6,14 +6,12 @@ works.  Tokenisation stays on the host with the HF tokenizer, exactly as the ref
 be created once and kept (the reference re-instantiates the encoder on every call, tools/utils_t2i.py:25-39).
 SURVEY.md 8(f) rank 4.
 """
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from .._blob import PackedWeights, WorkspaceCache
+from ._tower import _ImageTower, _Tower
 from ._uvit_core import ParamGroup
 
 CLIP_L_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
@@ -86,11 +84,11 @@ def _encoder_layers(n, hidden_size, intermediate_size):
     return nn.ModuleList(layers)
 
 
-class _CLIPTower(nn.Module):
-    """What the two towers share on the host: the checks of the encoder's shape, HF's initialisation, the packed blob and the
-    workspace cache.  A subclass names its library symbols (``_SYMBOLS``), itself (``_DISPLAY``, ``_WHICH``) and supplies
-    ``_c_cfg()``; its constructor builds the parameters between ``super().__init__(...)`` and ``self._finish_init()``."""
-    _SYMBOLS = _DISPLAY = _WHICH = None
+class _CLIPTower(_Tower):
+    """What the two CLIP towers add to ``_Tower``: the checks of the encoder's shape and HF's initialisation.  A subclass also
+    names itself for the messages (``_WHICH``); its constructor builds the parameters between ``super().__init__(...)`` and
+    ``self._finish_init()``."""
+    _WHICH = None
 
     def __init__(self, hidden_act, hidden_size, num_attention_heads, intermediate_size):
         super().__init__()
@@ -108,20 +106,7 @@ class _CLIPTower(nn.Module):
                     prm.zero_()
                 else:
                     prm.normal_(0.0, 0.02)
-        self._packed = PackedWeights(self._SYMBOLS, self._DISPLAY, self._canonical_params, self._c_cfg())
-        self._ws = WorkspaceCache(1)
-        self.eval()
-        self.requires_grad_(False)
-
-    def invalidate_packed(self):
-        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
-        self._packed.invalidate()
-
-    def _canonical_params(self):
-        return list(self.parameters())
-
-    def _packed_blob(self, device):
-        return self._packed.blob(device)
+        super()._finish_init()
 
 
 class CLIPTextTransformer(_CLIPTower):
@@ -172,16 +157,13 @@ class CLIPTextTransformer(_CLIPTower):
         dev = input_ids.device
         if input_ids.shape[0] == 0 or input_ids.shape[1] == 0:
             return torch.empty(input_ids.shape[0], input_ids.shape[1], self.cfg["dim"], dtype=torch.float32, device=dev)
-        blob = self._packed_blob(dev)
-        L = _hip.lib()
-        cfg = self._c_cfg()
         B, T = input_ids.shape
-        ws = self._ws.take(B, dev, L.uspace_clip_workspace_bytes(ctypes.byref(cfg), B))
+        L, lead = self._forward_args(B, dev)
         ids = input_ids.to(torch.int32).contiguous()
         out = torch.empty(B, T, self.cfg["dim"], dtype=torch.float32, device=dev)
-        _hip.check(L.uspace_clip_text_forward(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(ids),
-                                              _hip.ptr(out), B, T, -1 if hidden_state is None else int(hidden_state),
-                                              _hip.stream_ptr()), "uspace_clip_text_forward")
+        _hip.check(L.uspace_clip_text_forward(*lead, _hip.ptr(ids), _hip.ptr(out), B, T,
+                                              -1 if hidden_state is None else int(hidden_state), _hip.stream_ptr()),
+                   "uspace_clip_text_forward")
         return out
 
 
@@ -191,7 +173,7 @@ CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)                                 
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
-class CLIPVisionTransformer(_CLIPTower):
+class CLIPVisionTransformer(_CLIPTower, _ImageTower):
     """HF CLIPVisionModelWithProjection's computation (``image_embeds``) in libuspace_hip.so (``uspace_clipv_forward``), with the
     image preprocessing of ``uspace_clip_preprocess`` in front of it; parameters in the HF state_dict order and naming
     (``vision_model.*``, ``visual_projection.weight``)."""
@@ -237,44 +219,23 @@ class CLIPVisionTransformer(_CLIPTower):
     def preprocess(self, images, quantize=True, mean=CLIP_MEAN, std=CLIP_STD):
         """images [B, 3, H, H] fp32 in [0, 1] on the device -> pixel_values [B, 3, image_size, image_size]: ``save_image``'s
         rounding (``quantize``), antialiased bicubic resize (``uspace_clip_preprocess``), CLIP's mean and std."""
-        _hip.require_device(images, "images")
-        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
-            raise ValueError(f"images must be [B, 3, H, H] (square), got {tuple(images.shape)}")
-        S = self.cfg["image"]
-        x = images.detach().to(torch.float32).contiguous()
-        B, _, H, W = x.shape
-        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=x.device)
-        if B == 0:
-            return out
-        m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-        _hip.check(_hip.lib().uspace_clip_preprocess(_hip.ptr(x), _hip.ptr(out), B, H, W, S, 1 if quantize else 0, m3, s3,
-                                                     _hip.stream_ptr()), "uspace_clip_preprocess")
-        return out
+        return self._preprocess(images, quantize, mean, std)
 
     def forward(self, pixel_values, hidden_state=None, return_pooled=False):
         """pixel_values [B, 3, S, S] -> image_embeds [B, projection_dim] fp32 (``return_pooled``: also HF's ``pooler_output``
         [B, D]).  ``hidden_state=k``: the state [B, tokens, D] after k layers instead (k = 0: after pre_layrnorm, HF
         ``hidden_states[k]``; "embeddings": before pre_layrnorm)."""
-        _hip.require_device(pixel_values, "pixel_values")
-        S, D, P = self.cfg["image"], self.cfg["dim"], self.cfg["proj_dim"]
-        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
-            raise ValueError(f"pixel_values must be [B, 3, {S}, {S}], got {tuple(pixel_values.shape)}")
-        dev = pixel_values.device
-        B = pixel_values.shape[0]
-        stop = -1 if hidden_state is None else (-2 if hidden_state == "embeddings" else int(hidden_state))
-        if stop < -2:
-            raise ValueError("hidden_state must be None, 'embeddings' or a layer count >= 0")
-        tap = torch.empty(B, self.tokens, D, dtype=torch.float32, device=dev) if stop != -1 else None
-        emb = torch.empty(B, P, dtype=torch.float32, device=dev) if stop == -1 else None
-        pooled = torch.empty(B, D, dtype=torch.float32, device=dev) if (return_pooled and stop == -1) else None
+        B = self._check_pixel_values(pixel_values)
+        D, P = self.cfg["dim"], self.cfg["proj_dim"]
+        stop = self._stop(hidden_state)
+        tap = self._out(pixel_values, self.tokens, D) if stop != -1 else None
+        emb = self._out(pixel_values, P) if stop == -1 else None
+        pooled = self._out(pixel_values, D) if (return_pooled and stop == -1) else None
         if B:
-            blob = self._packed_blob(dev)
-            L = _hip.lib()
-            cfg = self._c_cfg()
-            ws = self._ws.take(B, dev, L.uspace_clipv_workspace_bytes(ctypes.byref(cfg), B))
+            L, lead = self._forward_args(B, pixel_values.device)
             pv = pixel_values.detach().to(torch.float32).contiguous()
-            _hip.check(L.uspace_clipv_forward(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(pv), _hip.ptr(emb),
-                                              _hip.ptr(pooled), B, stop, _hip.ptr(tap), _hip.stream_ptr()), "uspace_clipv_forward")
+            _hip.check(L.uspace_clipv_forward(*lead, _hip.ptr(pv), _hip.ptr(emb), _hip.ptr(pooled), B, stop, _hip.ptr(tap),
+                                              _hip.stream_ptr()), "uspace_clipv_forward")
         if stop != -1:
             return tap
         return (emb, pooled) if return_pooled else emb

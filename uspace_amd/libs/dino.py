@@ -18,14 +18,13 @@ weights.  The original DINOv2 repository interpolates by ``scale_factor`` with `
 different tables; that form is not offered, and neither could be compared against features of the published weights.
 
 Nothing is ever downloaded: weights come from ``weights=`` (a local state-dict file) or ``seed=``."""
-import ctypes
 import os
 
 import torch
 import torch.nn as nn
 
 from .. import _hip
-from .._blob import PackedWeights, WorkspaceCache
+from ._tower import _ImageTower
 from ._uvit_core import ParamGroup
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -85,9 +84,10 @@ def _affine(group, name, *shape):
     c.add("bias", shape[0])
 
 
-class DinoVisionTransformer(nn.Module):
+class DinoVisionTransformer(_ImageTower):
     """HF ``Dinov2Model``'s computation in libuspace_hip.so (``uspace_dino_forward``).  ``image_size``: the side the tower runs
     at; ``table_size``: the side the checkpoint's position table was made for (default: ``image_size``)."""
+    _SYMBOLS, _DISPLAY = "uspace_dino_", "DINO tower"
 
     def __init__(self, hidden_size=1024, num_attention_heads=16, num_hidden_layers=24, patch_size=14, image_size=224, table_size=None,
                  mlp_ratio=4, layerscale=True, layer_norm_eps=1e-6, hidden_act="gelu", use_swiglu_ffn=False, num_register_tokens=0,
@@ -149,11 +149,8 @@ class DinoVisionTransformer(nn.Module):
                     f"DINO tower weights not found at {weights}: pass weights= (a state dict of HF Dinov2Model or ViTModel saved "
                     "with torch.save) or seed=; uspace_amd never downloads")
             self.load_state_dict(torch.load(weights, map_location="cpu"))
-        self._packed = PackedWeights("uspace_dino_", "DINO tower", self._canonical_params, self._c_cfg())
-        self._ws = WorkspaceCache(1)
         self._pos = None           # ((data_ptr, version, device), interpolated table)
-        self.eval()
-        self.requires_grad_(False)
+        self._finish_init()
 
     @torch.no_grad()
     def _seed(self, seed):
@@ -184,8 +181,8 @@ class DinoVisionTransformer(nn.Module):
         return super().load_state_dict(sd, strict=strict, assign=assign)
 
     def invalidate_packed(self):
-        """Forget the packed weight blob; needed only after in-place edits through ``p.data`` (``PackedWeights.invalidate``)."""
-        self._packed.invalidate()
+        """Forget the packed weight blob and the interpolated table; needed only after in-place edits through ``p.data``."""
+        super().invalidate_packed()
         self._pos = None
 
     def position_table(self):
@@ -201,9 +198,6 @@ class DinoVisionTransformer(nn.Module):
         pos = self.embeddings.position_embeddings
         return [self.position_table() if p is pos else p for p in self.parameters()]
 
-    def _packed_blob(self, device):
-        return self._packed.blob(device)
-
     def _c_cfg(self):
         c = self.cfg
         return _hip.DinoConfig(c["image"], c["patch"], c["dim"], c["heads"], c["layers"], c["ffn"], c["layerscale"], c["eps"])
@@ -211,39 +205,19 @@ class DinoVisionTransformer(nn.Module):
     def preprocess(self, images, quantize=True, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         """images [B, 3, H, H] fp32 in [0, 1] on the device -> pixel_values [B, 3, image_size, image_size]: ``save_image``'s
         rounding (``quantize``), antialiased bicubic resize (``uspace_clip_preprocess``), ImageNet mean and std."""
-        _hip.require_device(images, "images")
-        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
-            raise ValueError(f"images must be [B, 3, H, H] (square), got {tuple(images.shape)}")
-        S = self.cfg["image"]
-        x = images.detach().to(torch.float32).contiguous()
-        B, _, H, W = x.shape
-        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=x.device)
-        if B == 0:
-            return out
-        m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-        _hip.check(_hip.lib().uspace_clip_preprocess(_hip.ptr(x), _hip.ptr(out), B, H, W, S, 1 if quantize else 0, m3, s3,
-                                                     _hip.stream_ptr()), "uspace_clip_preprocess")
-        return out
+        return self._preprocess(images, quantize, mean, std)
 
     def _run(self, pixel_values, stop, key_layer, want_pooler):
-        _hip.require_device(pixel_values, "pixel_values")
-        S, D = self.cfg["image"], self.cfg["dim"]
-        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, S, S):
-            raise ValueError(f"pixel_values must be [B, 3, {S}, {S}], got {tuple(pixel_values.shape)}")
-        dev = pixel_values.device
-        B = pixel_values.shape[0]
-        tap = torch.empty(B, self.tokens, D, dtype=torch.float32, device=dev) if (stop != -1 and key_layer < 0) else None
-        pooled = torch.empty(B, D, dtype=torch.float32, device=dev) if want_pooler else None
-        keys = torch.empty(B, self.tokens, D, dtype=torch.bfloat16, device=dev) if key_layer >= 0 else None
+        B = self._check_pixel_values(pixel_values)
+        D = self.cfg["dim"]
+        tap = self._out(pixel_values, self.tokens, D) if (stop != -1 and key_layer < 0) else None
+        pooled = self._out(pixel_values, D) if want_pooler else None
+        keys = self._out(pixel_values, self.tokens, D, dtype=torch.bfloat16) if key_layer >= 0 else None
         if B:
-            blob = self._packed.blob(dev)
-            L = _hip.lib()
-            cfg = self._c_cfg()
-            ws = self._ws.take(B, dev, L.uspace_dino_workspace_bytes(ctypes.byref(cfg), B))
+            L, lead = self._forward_args(B, pixel_values.device)
             pv = pixel_values.detach().to(torch.float32).contiguous()
-            _hip.check(L.uspace_dino_forward(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(pv), _hip.ptr(pooled),
-                                             B, stop, _hip.ptr(tap), key_layer, _hip.ptr(keys), _hip.stream_ptr()),
-                       "uspace_dino_forward")
+            _hip.check(L.uspace_dino_forward(*lead, _hip.ptr(pv), _hip.ptr(pooled), B, stop, _hip.ptr(tap), key_layer, _hip.ptr(keys),
+                                             _hip.stream_ptr()), "uspace_dino_forward")
         return pooled, tap, keys
 
     @torch.no_grad()
@@ -251,9 +225,7 @@ class DinoVisionTransformer(nn.Module):
         """pixel_values [B, 3, S, S] -> ``pooler_output`` [B, D] fp32 (the final LayerNorm of the class token).
         ``hidden_state=k``: the residual stream [B, tokens, D] after k layers instead (HF ``hidden_states[k]``; 0 or
         "embeddings": the embeddings)."""
-        stop = -1 if hidden_state is None else (-2 if hidden_state == "embeddings" else int(hidden_state))
-        if stop < -2:
-            raise ValueError("hidden_state must be None, 'embeddings' or a layer count >= 0")
+        stop = self._stop(hidden_state)
         pooled, tap, _ = self._run(pixel_values, stop, -1, stop == -1)
         return pooled if stop == -1 else tap
 
