@@ -203,6 +203,23 @@ USPACE_API int uspace_attention_long_bf16(const uint16_t* qkv, const float* key_
  * (grid = B * H * ceil(L / QB)), NW waves per workgroup. */
 USPACE_API int uspace_attention_long_plan(int B, int L, int H, int scaled, int* out);
 
+/* Single-head, non-causal attention with a wide head (the VAE's mid-block AttnBlock beyond 1 024 tokens):
+ *   out[b, i, :] = softmax_j(q[b, i] . k[b, j] * scale) . v[b, j, :]
+ * q, k, v: token-major bf16 [B * N, C] with leading dimension ld (elements; a multiple of 8, 16-byte aligned pointers); out bf16
+ * [B * N, C] with leading dimension ld_out (a multiple of 4, 8-byte aligned).  C = 64, 128, 256 or 512; any N >= 1.  K and V stream
+ * through LDS in 32-key tiles; online softmax in fp32 (running maximum and sum, accumulator rescaling), P rounded to bf16 once per
+ * key tile for both P.V and the row sum, one division at the end, keys >= N masked before the maximum.  A query row is never split
+ * across workgroups and there are no atomics: a row's bits depend on neither B nor the grid, and repeat from run to run.  Nothing is
+ * read before it is written.  USPACE_ERR_ARG for any other C, B or N <= 0, NULL or misaligned operands, ld or ld_out < C, a scale
+ * that is not positive and finite, or B * N or the grid beyond INT_MAX.  Added without a change of USPACE_ABI_VERSION: symbols only. */
+USPACE_API int uspace_attention_wide_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int ld,
+                                          uint16_t* out, int ld_out, int B, int N, int C, float scale,
+                                          uspace_stream_t stream);
+/* host-side, no GPU work: out[6] = {KT, QB, NW, grid, block, dynamic LDS bytes} of the launch uspace_attention_wide_bf16 takes for
+ * (B, N, C); USPACE_ERR_ARG where that call would refuse these three.  KT keys per key tile, QB = 16 NW queries per workgroup
+ * (grid = B * ceil(N / QB)), NW waves per workgroup. */
+USPACE_API int uspace_attention_wide_plan(int B, int N, int C, int* out);
+
 /* Head-mean attention map of the same packed qkv (what tools/utils_t2i.py:141-193 vis_attention_map draws from the reference's
  * [B, H, L, L] softmax, libs/uvit_t2i.py:101-103):
  *     out[b, i, j] = (1/H) * sum_h softmax_k( q[b,h,q0+i] . k[b,h,k] * 64^-0.5 )[k0+j]       fp32, [B, nq, nk]
@@ -825,7 +842,7 @@ USPACE_API int uspace_prof_gemm_begin(int epi_flags, int N, int K, int max_launc
 USPACE_API int uspace_prof_gemm_end(double* total_ms, int* n_launches);
 /* The same around EVERY GEMM and attention launch (bench.py's roofline_all): _end() aggregates the recorded launches by
  * (kind, flags, M, N, K) into keys[6 * i + {0: kind (0 GEMM, 1 attention), 1: epi_flags (attention: 1 = key scales, 2 = the streaming form
- * uspace_attention_long_bf16),
+ * uspace_attention_long_bf16, 4 = the wide single-head form uspace_attention_wide_bf16, whose M is B and whose K is C),
  * 2: M (attention: B * H), 3: N (attention: L), 4: K (attention: head dim), 5: launches}] and total_ms[i], i < *n_records <= max_records. */
 USPACE_API int uspace_prof_all_begin(int max_launches);
 USPACE_API int uspace_prof_all_end(int* keys, double* total_ms, int max_records, int* n_records);

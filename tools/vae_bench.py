@@ -1,7 +1,9 @@
 """Throughput of the SD KL-VAE decode (4x32x32 -> 3x256x256) on the HIP path, with the algorithmic FLOPs of the
 reference's Decoder (libs/autoencoder.py:303-409) counted from the configuration; with --encode, of the encode
 (3x256x256 -> moments 8x32x32, Encoder + quant_conv, libs/autoencoder.py:215-300,428-431) instead.
-    python tools/vae_bench.py [--batch 8] [--iters 5] [--encode]"""
+The model keeps its nominal 256^2 configuration; --resolution R feeds it R x R images / R/8 x R/8 latents (512: 64 x 64 latents, where
+the mid-block attention is the streaming kernel of attention_wide.hip).
+    python tools/vae_bench.py [--batch 8] [--iters 5] [--encode] [--resolution 256]"""
 import argparse
 import json
 import os
@@ -72,13 +74,17 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--encode", action="store_true", help="measure encode_moments instead of decode")
+    ap.add_argument("--resolution", type=int, default=256, help="image size (a multiple of 8); the model stays the 256^2 SD configuration")
     a = ap.parse_args()
+    if a.resolution < 8 or a.resolution % 8:
+        ap.error("--resolution must be a positive multiple of 8")
     from uspace_amd.libs.autoencoder import FrozenAutoencoderKL
     torch.manual_seed(0)
     if a.encode:
         return bench_encode(a, FrozenAutoencoderKL)
     vae = FrozenAutoencoderKL(SD, 4).cuda()
-    z = (torch.randn(a.batch, 4, 32, 32) * 0.18215).cuda()
+    R, h = a.resolution, a.resolution // 8
+    z = (torch.randn(a.batch, 4, h, h) * 0.18215).cuda()
     vae.decode(z, chunk=a.batch)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -86,14 +92,15 @@ def main():
         vae.decode(z, chunk=a.batch)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.iters
-    fl = decoder_flops(SD)
-    print(json.dumps({"workload": "SD KL-VAE decode 4x32x32 -> 3x256x256", "batch": a.batch, "ms_per_batch": dt * 1e3,
+    fl = decoder_flops(dict(SD, resolution=R))
+    print(json.dumps({"workload": f"SD KL-VAE decode 4x{h}x{h} -> 3x{R}x{R}", "batch": a.batch, "ms_per_batch": dt * 1e3,
                       "img_per_s": a.batch / dt, "gflop_per_img": fl / 1e9, "tflops": fl * a.batch / dt / 1e12}))
 
 
 def bench_encode(a, FrozenAutoencoderKL):
     vae = FrozenAutoencoderKL(SD, 4, encoder=True).cuda()
-    x = (torch.rand(a.batch, 3, 256, 256) * 2 - 1).cuda()
+    R, h = a.resolution, a.resolution // 8
+    x = (torch.rand(a.batch, 3, R, R) * 2 - 1).cuda()
     vae.encode_moments(x, chunk=a.batch)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -101,8 +108,8 @@ def bench_encode(a, FrozenAutoencoderKL):
         vae.encode_moments(x, chunk=a.batch)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.iters
-    fl = encoder_flops(SD)
-    print(json.dumps({"workload": "SD KL-VAE encode_moments 3x256x256 -> 8x32x32", "batch": a.batch,
+    fl = encoder_flops(dict(SD, resolution=R))
+    print(json.dumps({"workload": f"SD KL-VAE encode_moments 3x{R}x{R} -> 8x{h}x{h}", "batch": a.batch,
                       "ms_per_batch": dt * 1e3, "img_per_s": a.batch / dt, "gflop_per_img": fl / 1e9,
                       "tflops": fl * a.batch / dt / 1e12}))
 

@@ -101,6 +101,8 @@ SIGNATURES = {
     "uspace_attention_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I)]),
     "uspace_attention_long_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "uspace_attention_long_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "uspace_attention_wide_bf16": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P]),
+    "uspace_attention_wide_plan": (_I, [_I, _I, _I, ctypes.POINTER(_I)]),
     "uspace_attention_map_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "uspace_embed_tokens": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "uspace_output_head": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
@@ -378,6 +380,18 @@ def attention_long(qkv, B, L, H, key_scale=None):
     out = torch.empty(B * L, H * 64, dtype=torch.bfloat16, device=qkv.device)
     check(lib().uspace_attention_long_bf16(ptr(qkv), ptr(key_scale), ptr(out), B, L, H, stream_ptr()),
           "uspace_attention_long_bf16")
+    return out
+
+
+def attention_wide(q, k, v, B, N, C, scale, ld=None, out=None, ld_out=None):
+    """Single-head attention with a wide head (C = 64 .. 512; the VAE's mid block beyond 1 024 tokens): q, k, v bf16 [B * N, ld]
+    (``ld`` defaults to C), ``out`` bf16 [B * N, ld_out] (allocated [B * N, C] where None)."""
+    require_device(q, "q")
+    ld = C if ld is None else ld
+    if out is None:
+        out, ld_out = torch.empty(B * N, C, dtype=torch.bfloat16, device=q.device), C
+    check(lib().uspace_attention_wide_bf16(ptr(q), ptr(k), ptr(v), ld, ptr(out), C if ld_out is None else ld_out, B, N, C,
+                                           float(scale), stream_ptr()), "uspace_attention_wide_bf16")
     return out
 
 

@@ -1,6 +1,7 @@
-// What the two attention kernels share (attention.hip: K and V of a head resident in LDS, L <= 336; attention_long.hip: K and V
+// What the attention kernels share (attention.hip: K and V of a head resident in LDS, L <= 336; attention_long.hip: K and V
 // streamed through LDS in key tiles, any L): the LDS image of K / V rows with its bank-spreading swizzles, the LDS-DMA that stages
-// eight rows per wave-instruction, the transposing V read and the cross-lane step of the row maximum.  head_dim 64: a row is 128 B.
+// eight rows per wave-instruction, the transposing V read and the cross-lane step of the row maximum.  head_dim 64: a row is 128 B;
+// attention_wide.hip lays a wider head out as 64-column panels of this image.
 #pragma once
 #include "common.h"
 

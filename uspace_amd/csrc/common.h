@@ -138,7 +138,8 @@ static inline int us_cdiv(int a, int b) { return (a + b - 1) / b; }
 // Launch recorder (prof.hip; bench.py's roofline objects): HIP events on the launching stream around the launches of the
 // hot kernels.  us_rec_begin returns -1 unless a recording was started through the C-ABI (uspace_prof_*_begin).
 enum { US_REC_GEMM = 0, US_REC_ATTENTION = 1 };
-enum { US_REC_ATT_SCALED = 1, US_REC_ATT_LONG = 2 };     // flags of an attention record: key scales; the streaming form (attention_long.hip)
+// flags of an attention record: key scales; the streaming form (attention_long.hip); the wide single-head form (attention_wide.hip)
+enum { US_REC_ATT_SCALED = 1, US_REC_ATT_LONG = 2, US_REC_ATT_WIDE = 4 };
 int us_rec_begin(int kind, int flags, int M, int N, int K, hipStream_t s);
 void us_rec_end(int idx, hipStream_t s);
 

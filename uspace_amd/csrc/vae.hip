@@ -646,6 +646,12 @@ std::vector<MapStep> enc_steps(const uspace_vae_config& c) {
     return st;
 }
 
+// The mid-block attention over H x H tokens: up to 1 024 tokens the whole fp32 S = q k^T per image (HW^2 * 6 bytes of workspace,
+// three launches per image), beyond that uspace_attention_wide_bf16 (one launch per chunk, no S) -- and also below wherever the token
+// count is no multiple of the GEMM's 64-element K step, which the P.V GEMM of the first path refuses (any side that is no multiple
+// of 8).  plan_ws and mid_attn both ask here.
+inline bool wide_attn(int H) { return (long)H * H > 1024 || (H * H) % 64 != 0; }
+
 // two fp32 maps and two bf16 operand buffers sized for the largest step, GroupNorm statistics, the mid-block attention's buffers
 VaeWs plan_ws(const std::vector<MapStep>& steps, int B, int z_res, int c_top) {
     VaeWs w;
@@ -660,7 +666,13 @@ VaeWs plan_ws(const std::vector<MapStep>& steps, int B, int z_res, int c_top) {
     w.stats = a.take((size_t)B * (1 + USPACE_GN_MAX_CHUNKS) * 64 * 4);
     const size_t T = (size_t)B * z_res * z_res, Cc = c_top, HW = (size_t)z_res * z_res;
     w.tok = a.take(T * Cc * 2); w.q = a.take(T * Cc * 2); w.k = a.take(T * Cc * 2); w.v = a.take(T * Cc * 2);
-    w.vt = a.take(T * Cc * 2); w.s = a.take(HW * HW * 4); w.pr = a.take(HW * HW * 2); w.o = a.take(T * Cc * 2);
+    if (wide_attn(z_res)) {
+        // the streaming kernel keeps S and P in registers and reads V as it lies: linear in HW
+        w.vt = w.s = w.pr = a.off;
+    } else {
+        w.vt = a.take(T * Cc * 2); w.s = a.take(HW * HW * 4); w.pr = a.take(HW * HW * 2);
+    }
+    w.o = a.take(T * Cc * 2);
     w.po = a.take(T * Cc * 4);
     w.total = a.off;
     return w;
@@ -744,10 +756,15 @@ struct VaeRun {
         US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(a.q_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(a.q_b), nullptr, 0, nullptr, 0, q, Cc, stream));
         US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(a.k_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(a.k_b), nullptr, 0, nullptr, 0, k, Cc, stream));
         US_TRY(uspace_gemm_bf16(tok, Cc, nullptr, 0, Cc, PH(a.v_w), Cc, (int)T, Cc, Cc, B_ | H_, PF(a.v_b), nullptr, 0, nullptr, 0, v, Cc, stream));
-        hipLaunchKernelGGL(transpose_kernel, dim3(us_cdiv(Cc, 32), us_cdiv(HW, 32), B), dim3(256), 0, s, v, vt, HW, Cc);
-        US_CHECK_LAUNCH();
         const float scale = 1.0f / sqrtf((float)Cc);
-        for (int b = 0; b < B; ++b) {
+        if (wide_attn(H)) {
+            // one streaming launch for the chunk; vt, s and pr are not reserved on this branch (plan_ws)
+            US_TRY(uspace_attention_wide_bf16(q, k, v, Cc, o, Cc, B, HW, Cc, scale, stream));
+        } else {
+            hipLaunchKernelGGL(transpose_kernel, dim3(us_cdiv(Cc, 32), us_cdiv(HW, 32), B), dim3(256), 0, s, v, vt, HW, Cc);
+            US_CHECK_LAUNCH();
+        }
+        for (int b = 0; b < (wide_attn(H) ? 0 : B); ++b) {
             // w_ = softmax(q k^T * c^-0.5) over keys; h_ = w_ v   (libs/autoencoder.py:179-191)
             US_TRY(uspace_gemm_bf16(q + (size_t)b * HW * Cc, Cc, nullptr, 0, Cc, k + (size_t)b * HW * Cc, Cc, HW, HW, Cc, F_,
                                     nullptr, nullptr, 0, sc, HW, nullptr, 0, stream));

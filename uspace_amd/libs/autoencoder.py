@@ -1,6 +1,9 @@
 """Drop-in for the reference's frozen SD KL-VAE (libs/autoencoder.py:215-300 ``Encoder``, :303-409 ``Decoder``,
 :412-458 ``FrozenAutoencoderKL``): latents [B,4,32,32] -> images [B,3,256,256] and, with ``encoder=True``, images ->
-moments [B,8,32,32] -> latents.
+moments [B,8,32,32] -> latents.  Those are the nominal sizes (``ddconfig["resolution"]``): the network is fully
+convolutional, so ``decode`` takes any square [B,4,h,h] and ``encode*`` any square [B,3,R,R] with R a multiple of 2^(levels-1) (8 here), with
+the same weights -- 64x64 latents <-> 512^2 images among them.  Beyond 1 024 latent positions the mid-block attention is
+the streaming kernel of attention_wide.hip.
 
 Same ``state_dict`` keys as the reference.  Decoder-only (the default) holds ``decoder.*`` and ``post_quant_conv.*``
 and ignores the encoder half of a checkpoint; ``encoder=True`` holds all four halves and loads strictly.  The
@@ -245,42 +248,64 @@ class FrozenAutoencoderKL(nn.Module):
         m = dump[: B * (H + 2) * (H + 2) * C].view(B, H + 2, H + 2, C)
         return m[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).contiguous()
 
-    def decode(self, z, chunk=8):
-        """z [B,4,h,h] (scaled latents, as produced by the sampler) -> images [B,3,R,R] fp32.  Decodes ``chunk``
-        images at a time (the reference chunks by 50, dissect_lfm.py:86-98)."""
+    def _cfg_at(self, resolution):
+        """The model's config at another image size.  The network is fully convolutional and takes its size from the tensor, as
+        the reference's does; ``self.resolution`` stays the nominal size and the packed weights do not depend on it."""
+        if resolution == self.resolution:
+            return self._cfg
+        c = self._cfg
+        return _hip.VaeConfig(c.ch, c.ch_mult, c.n_levels, c.num_res_blocks, int(resolution))
+
+    def _ws_key(self, chunk, resolution):
+        """Workspace cache key: (chunk, resolution) off the nominal size; at the nominal size the chunk alone, the key every
+        wrapper's cache uses (``WorkspaceCache``: (batch or chunk, device))."""
+        return chunk if resolution == self.resolution else (chunk, resolution)
+
+    def _check_latents(self, z):
+        """-> the image size R = h * 2^(levels-1) of latents z [B, z_channels, h, h]: any square h >= 1."""
         _hip.require_device(z, "z")
-        if z.dim() != 4 or z.shape[1] != self.z_channels or z.shape[2] != self.z_res or z.shape[3] != self.z_res:
-            raise ValueError(f"z must be [B,{self.z_channels},{self.z_res},{self.z_res}], got {tuple(z.shape)}")
+        if z.dim() != 4 or z.shape[1] != self.z_channels or z.shape[2] != z.shape[3] or z.shape[2] < 1:
+            raise ValueError(f"z must be square [B,{self.z_channels},h,h] with h >= 1 ({self.z_res} at the nominal "
+                             f"resolution {self.resolution}), got {tuple(z.shape)}")
+        return z.shape[2] * 2 ** (len(self.ch_mult) - 1)
+
+    def decode(self, z, chunk=8):
+        """z [B,4,h,h] (scaled latents, as produced by the sampler; any h >= 1) -> images [B,3,R,R] fp32, R = h *
+        2^(levels-1).  Decodes ``chunk`` images at a time (the reference chunks by 50, dissect_lfm.py:86-98)."""
+        R = self._check_latents(z)
         dev = z.device
         if z.shape[0] == 0:
-            return torch.empty(0, self.out_ch, self.resolution, self.resolution, dtype=z.dtype, device=dev)
+            return torch.empty(0, self.out_ch, R, R, dtype=z.dtype, device=dev)
         blob = self._packed_blob(dev)
         L = _hip.lib()
+        cfg = self._cfg_at(R)
         zin = z.detach().to(torch.float32).contiguous()
         B = zin.shape[0]
-        out = torch.empty(B, self.out_ch, self.resolution, self.resolution, dtype=torch.float32, device=dev)
-        max_chunk = _max_chunk([(self.resolution, 512)])
+        out = torch.empty(B, self.out_ch, R, R, dtype=torch.float32, device=dev)
+        max_chunk = _max_chunk([(R, 512)])
         chunk = max(1, min(chunk, max_chunk, B))
-        ws = self._ws.take(chunk, dev, L.uspace_vae_workspace_bytes(ctypes.byref(self._cfg), chunk))
+        ws = self._ws.take(self._ws_key(chunk, R), dev, L.uspace_vae_workspace_bytes(ctypes.byref(cfg), chunk))
         for lo in range(0, B, chunk):
             n = min(chunk, B - lo)
-            _hip.check(L.uspace_vae_decode(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
+            _hip.check(L.uspace_vae_decode(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
                                            _hip.ptr(zin[lo:lo + n]), float(self.scale_factor), _hip.ptr(out[lo:lo + n]),
                                            n, _hip.stream_ptr()), "uspace_vae_decode")
         return out if z.dtype == torch.float32 else out.to(z.dtype)
 
     def decode_tap(self, z, stage):
         """Test aid: the fp32 feature map after ``stage`` (see uspace_vae_decode_tap) as [B, C, H, W]."""
+        R = self._check_latents(z)
         dev = z.device
         blob = self._packed_blob(dev)
         L = _hip.lib()
+        cfg = self._cfg_at(R)
         zin = z.detach().to(torch.float32).contiguous()
         B = zin.shape[0]
-        nbytes = L.uspace_vae_workspace_bytes(ctypes.byref(self._cfg), B)
+        nbytes = L.uspace_vae_workspace_bytes(ctypes.byref(cfg), B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        dump = torch.zeros(B * (self.resolution + 2) ** 2 * 512, dtype=torch.float32, device=dev)
+        dump = torch.zeros(B * (R + 2) ** 2 * 512, dtype=torch.float32, device=dev)
         hc = (ctypes.c_int * 2)()
-        _hip.check(L.uspace_vae_decode_tap(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(zin),
+        _hip.check(L.uspace_vae_decode_tap(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(zin),
                                            float(self.scale_factor), B, int(stage), _hip.ptr(dump), hc, _hip.stream_ptr()),
                    "uspace_vae_decode_tap")
         return self._tap_map(dump, hc, B)
@@ -290,9 +315,10 @@ class FrozenAutoencoderKL(nn.Module):
         if not self.has_encoder:
             raise NotImplementedError(f"{what}: this model was built without the encoder (encoder=False)")
 
-    def max_encode_chunk(self):
-        """Largest legal encode chunk: every map of the down path below 2^30 elements (126 images at 256^2)."""
-        res, chan, rc = self.resolution, self.ch, []
+    def max_encode_chunk(self, resolution=None):
+        """Largest legal encode chunk at ``resolution`` (the nominal one where None): every map of the down path below
+        2^30 elements (126 images at 256^2)."""
+        res, chan, rc = (self.resolution if resolution is None else resolution), self.ch, []
         for lvl, m in enumerate(self.ch_mult):
             rc.append((res, max(chan, self.ch * m)))
             chan = self.ch * m
@@ -301,29 +327,35 @@ class FrozenAutoencoderKL(nn.Module):
         return _max_chunk(rc)
 
     def _check_images(self, x):
+        """-> the size R of images x [B, 3, R, R]: any square R that the down path halves evenly."""
         _hip.require_device(x, "x")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.resolution or x.shape[3] != self.resolution:
-            raise ValueError(f"x must be [B,3,{self.resolution},{self.resolution}], got {tuple(x.shape)}")
+        f = 2 ** (len(self.ch_mult) - 1)
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] < f or x.shape[2] % f:
+            raise ValueError(f"x must be square [B,3,R,R] with R a positive multiple of {f} ({self.resolution} at the "
+                             f"nominal resolution), got {tuple(x.shape)}")
+        return x.shape[2]
 
     def encode_moments(self, x, chunk=8):
-        """images x [B,3,R,R] in [-1, 1] -> moments [B, 2*embed_dim, h, h] (mean, logvar) fp32, ``chunk`` images at a
-        time (the reference's feature extraction runs batches of 256, scripts/extract_*_feature.py)."""
+        """images x [B,3,R,R] in [-1, 1] (any R that is a multiple of 2^(levels-1)) -> moments [B, 2*embed_dim, h, h]
+        (mean, logvar) fp32, ``chunk`` images at a time (the reference's feature extraction runs batches of 256,
+        scripts/extract_*_feature.py)."""
         self._require_encoder("encode_moments")
-        self._check_images(x)
+        R = self._check_images(x)
         dev = x.device
-        h = self.z_res
+        h = R // 2 ** (len(self.ch_mult) - 1)
         if x.shape[0] == 0:
             return torch.empty(0, 2 * self.embed_dim, h, h, dtype=x.dtype, device=dev)
         blob = self._packed_enc_blob(dev)
         L = _hip.lib()
+        cfg = self._cfg_at(R)
         xin = x.detach().to(torch.float32).contiguous()
         B = xin.shape[0]
         out = torch.empty(B, 2 * self.embed_dim, h, h, dtype=torch.float32, device=dev)
-        chunk = max(1, min(chunk, self.max_encode_chunk(), B))
-        ws = self._ws_enc.take(chunk, dev, L.uspace_vae_enc_workspace_bytes(ctypes.byref(self._cfg), chunk))
+        chunk = max(1, min(chunk, self.max_encode_chunk(R), B))
+        ws = self._ws_enc.take(self._ws_key(chunk, R), dev, L.uspace_vae_enc_workspace_bytes(ctypes.byref(cfg), chunk))
         for lo in range(0, B, chunk):
             n = min(chunk, B - lo)
-            _hip.check(L.uspace_vae_encode_moments(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
+            _hip.check(L.uspace_vae_encode_moments(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
                                                    _hip.ptr(xin[lo:lo + n]), _hip.ptr(out[lo:lo + n]), n,
                                                    _hip.stream_ptr()), "uspace_vae_encode_moments")
         return out if x.dtype == torch.float32 else out.to(x.dtype)
@@ -353,18 +385,19 @@ class FrozenAutoencoderKL(nn.Module):
     def encode_tap(self, x, stage):
         """Test aid: the fp32 feature map after encode ``stage`` (see uspace_vae_encode_tap) as [B, C, H, W]."""
         self._require_encoder("encode_tap")
-        self._check_images(x)
+        R = self._check_images(x)
         dev = x.device
         blob = self._packed_enc_blob(dev)
         L = _hip.lib()
+        cfg = self._cfg_at(R)
         xin = x.detach().to(torch.float32).contiguous()
         B = xin.shape[0]
-        nbytes = L.uspace_vae_enc_workspace_bytes(ctypes.byref(self._cfg), B)
+        nbytes = L.uspace_vae_enc_workspace_bytes(ctypes.byref(cfg), B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         cmax = self.ch * max(self.ch_mult)
-        dump = torch.zeros(B * (self.resolution + 2) ** 2 * cmax, dtype=torch.float32, device=dev)
+        dump = torch.zeros(B * (R + 2) ** 2 * cmax, dtype=torch.float32, device=dev)
         hc = (ctypes.c_int * 2)()
-        _hip.check(L.uspace_vae_encode_tap(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(xin),
+        _hip.check(L.uspace_vae_encode_tap(ctypes.byref(cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(), _hip.ptr(xin),
                                            B, int(stage), _hip.ptr(dump), hc, _hip.stream_ptr()), "uspace_vae_encode_tap")
         return self._tap_map(dump, hc, B)
 
