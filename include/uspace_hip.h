@@ -616,7 +616,7 @@ USPACE_API int uspace_normalized_diff_f32(const float* a, const float* b, float*
  * owns 64 rows and walks the column tiles, the reductions fused.  No floating-point atomics: every output is bit-equal from
  * run to run.  workspace: uspace_metric_workspace_bytes(nx, ny, n_subsets, m) bytes (norms of both sets + the partial sums of
  * uspace_metric_poly_sums; pass ny = 0 for uspace_metric_knn_radius2, n_subsets = m = 0 where no sums are asked for); 0 on
- * invalid arguments.  The layout is one formula for all three consumers, norms first: uspace_metric_poly_sums computes no norms and
+ * invalid arguments.  The layout is one formula for all four consumers, norms first: uspace_metric_poly_sums computes no norms and
  * leaves those (nx + ny) doubles untouched ahead of its partial sums (128 MiB per 2^24-row set, allocated and unused).
  * Nothing of the workspace is read before it is written.  These functions were added without a change
  * of USPACE_ABI_VERSION: they only add symbols.
@@ -638,6 +638,18 @@ USPACE_API int uspace_metric_manifold(const float* x, int nx, const float* y, in
 USPACE_API int uspace_metric_poly_sums(const float* x, int nx, const float* y, int ny, int F, const int* idx_x, const int* idx_y,
                                        int n_subsets, int m, int degree, double gamma, double coef0, double* sums, void* workspace,
                                        size_t workspace_bytes, uspace_stream_t stream);
+/* The sums of the Gaussian RBF kernel K(a, b) = exp(-gamma D2(a, b)) behind MMD^2 / CMMD (uspace_amd/tools/cmmd.py), over whole sets:
+ *   sums[0] = sum_{i != j} K(x_i, x_j),   sums[1] = sum_{i != j} K(y_i, y_j),   sums[2] = sum_{i, j} K(x_i, y_j);   sums: fp64 [3].
+ * The diagonal is left out by index (K(a, a) = 1 is the caller's to add where its estimator wants it), and so is everything beyond
+ * either set.  normalize = 1: D2 is taken between the unit vectors a / |a|, b / |b|, formed in fp64 from the same dot product and
+ * norms -- no fp32 normalisation pass, no second copy of the features; a zero row counts as the zero vector.  normalize = 0: the
+ * raw D2 above.  exp is the fp64 device exp; K <= 1 because D2 >= 0.  One launch over the three set pairs, per-workgroup partial
+ * sums finished in a fixed order, no atomics: bit-equal from run to run.  USPACE_ERR_ARG: a NULL pointer, nx or ny outside
+ * 1 .. 2^24, F < 1, gamma negative or not finite, normalize not 0 or 1 -- checked, like USPACE_ERR_WORKSPACE, before any GPU work.
+ * workspace: uspace_metric_workspace_bytes(nx, ny, 1, max(nx, ny)) bytes (the norms of both sets, then three partial sums per
+ * 64-row block of the larger set); nothing of it is read before it is written.  Symbols only: USPACE_ABI_VERSION is unchanged. */
+USPACE_API int uspace_metric_rbf_sums(const float* x, int nx, const float* y, int ny, int F, double gamma, int normalize,
+                                      double* sums, void* workspace, size_t workspace_bytes, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Inception Score and sFID (uspace_amd/tools/inception_score.py, sfid_score.py, eval_suite.py): the pool features, the

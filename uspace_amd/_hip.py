@@ -180,6 +180,7 @@ SIGNATURES = {
     "uspace_metric_knn_radius2": (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
     "uspace_metric_manifold": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "uspace_metric_poly_sums": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _D, _D, _P, _P, _SZ, _P]),
+    "uspace_metric_rbf_sums": (_I, [_P, _I, _P, _I, _I, _D, _I, _P, _P, _SZ, _P]),
     "uspace_inception_forward_suite": (_I, [_P, _P, _SZ, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
     "uspace_inception_logits": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "uspace_inception_score_workspace_bytes": (_SZ, [_I, _I, _I]),
@@ -552,6 +553,22 @@ def metric_poly_sums(x, y, idx_x, idx_y, degree, gamma, coef0, ws=None):
     check(lib().uspace_metric_poly_sums(ptr(x), x.shape[0], ptr(y), y.shape[0], x.shape[1], ptr(idx_x), ptr(idx_y), n_subsets, m,
                                         int(degree), float(gamma), float(coef0), ptr(sums), ptr(ws), ws.numel(), stream_ptr()),
           "uspace_metric_poly_sums")
+    return sums
+
+
+def metric_rbf_sums(x, y, gamma, normalize=False, ws=None):
+    """fp64 [3]: the sums of exp(-gamma D2(a, b)) over the pairs of x with x and of y with y without i == j, and of x with y over
+    all; ``normalize``: D2 between the rows scaled to unit length in fp64 (a zero row counts as the zero vector)."""
+    _metric_features(x, "x")
+    _metric_features(y, "y")
+    if x.shape[1] != y.shape[1]:
+        raise UspaceHipError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    nx, ny = x.shape[0], y.shape[0]
+    if ws is None:
+        ws = metric_workspace(nx, ny, 1, max(nx, ny), device=x.device)
+    sums = torch.empty(3, dtype=torch.float64, device=x.device)
+    check(lib().uspace_metric_rbf_sums(ptr(x), nx, ptr(y), ny, x.shape[1], float(gamma), 1 if normalize else 0, ptr(sums), ptr(ws),
+                                       ws.numel(), stream_ptr()), "uspace_metric_rbf_sums")
     return sums
 
 

@@ -1,7 +1,7 @@
-// Feature-set metrics (KID, precision / recall / density / coverage): reductions over the pairwise quantities of two fp32 feature
-// sets x [nx, F] and y [ny, F], computed in fp64 on v_mfma_f64_16x16x4_f64 and never stored as an nx x ny matrix.
+// Feature-set metrics (KID, precision / recall / density / coverage, RBF-kernel MMD / CMMD): reductions over the pairwise
+// quantities of two fp32 feature sets x [nx, F] and y [ny, F], computed in fp64 on v_mfma_f64_16x16x4_f64 and never stored as an nx x ny matrix.
 //
-// One tile engine, three consumers.  A workgroup (4 waves) owns 64 rows of x and walks every 128-column tile of y; wave w owns
+// One tile engine, four consumers.  A workgroup (4 waves) owns 64 rows of x and walks every 128-column tile of y; wave w owns
 // rows 16 w .. 16 w + 15 of the block against all 128 columns (8 MFMA tiles), so a row lives in ONE wave and every reduction along
 // a row is finished inside it: integer adds and minima (exact in any order), or fp64 sums in one fixed order.  No atomics.
 //   dot(i, j)  the fp64 MFMA over the fp32 values widened to fp64; k beyond F contributes exact zeros
@@ -14,6 +14,8 @@
 // slots of the 256-byte bank row.
 // Tile sizes, the single LDS buffer and the occupancy are a first choice: no alternative was measured.
 #include "common.h"
+
+#include <cfloat>
 
 namespace {
 
@@ -315,6 +317,80 @@ struct PolyConsumer {
     }
 };
 
+// ---- consumer 4: sums of the Gaussian RBF kernel K(a, b) = exp(-gamma D2(a, b)) over whole sets.  blockIdx.z: 0 x against x,
+// 1 y against y (both without i == j, left out by index), 2 x against y.  With `normalize` D2 is taken between a / |a| and
+// b / |b|, formed in fp64 from the same dot and norms: dot * (1 / |a|)(1 / |b|) and squared norms of 1 (a zero row: factor and
+// squared norm 0, the zero vector).  Without it the factors are 1 and the line below is dist2 of the raw values.  Elements
+// beyond either set and the diagonal never enter the sum: a padded column has D2 = |a|^2 and K > 0, so it cannot be masked by
+// value.  A row block beyond the pair's rows walks no tile and writes a zero partial.  Summation as PolyConsumer:
+// partial[which * row_blocks + blockIdx.x], finished by poly_finish_kernel.
+struct RbfConsumer {
+    const float *x, *y;
+    const double *norm_x, *norm_y;
+    double* partial;
+    int nx, ny, F;
+    double gamma;
+    bool normalize, vec;
+    double sum;
+    double na[4], sa[4];
+    int prow[4];
+
+    __device__ int which() const { return blockIdx.z; }
+    __device__ int rows() const { return which() == 1 ? ny : nx; }
+    __device__ int cols() const { return which() == 0 ? nx : ny; }
+    __device__ int n_cols() const { return (int)blockIdx.x * kBM < rows() ? cols() : 0; }
+    __device__ const float* row_a(int r) const { return r < rows() ? (which() == 1 ? y : x) + (size_t)r * F : nullptr; }
+    __device__ const float* row_b(int j) const { return j < cols() ? (which() == 0 ? x : y) + (size_t)j * F : nullptr; }
+    // (squared norm, factor on the dot product) of a row with squared norm n2
+    __device__ void unit(double n2, double& n, double& s) const {
+        if (!normalize) {
+            n = n2;
+            s = 1.0;
+        } else {
+            n = n2 > 0.0 ? 1.0 : 0.0;
+            s = n2 > 0.0 ? 1.0 / sqrt(n2) : 0.0;
+        }
+    }
+    __device__ void init(double*) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const double* norm_a = which() == 1 ? norm_y : norm_x;
+        sum = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            prow[r] = blockIdx.x * kBM + wave * 16 + (lane >> 4) + 4 * r;
+            unit(prow[r] < rows() ? norm_a[prow[r]] : 0.0, na[r], sa[r]);
+        }
+    }
+    __device__ void tile(f64x4 (&acc)[kNT], int col0, double*) {
+        const int c16 = threadIdx.x & 15;
+        const bool off_diagonal_only = which() != 2;
+        const double* norm_b = which() == 0 ? norm_x : norm_y;
+        const int n_rows = rows(), n_col = cols();
+#pragma unroll
+        for (int t = 0; t < kNT; ++t) {
+            const int q = col0 + t * 16 + c16;
+            if (q >= n_col) continue;
+            double nb, sb;
+            unit(norm_b[q], nb, sb);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (prow[r] >= n_rows || (off_diagonal_only && q == prow[r])) continue;
+                const double d = dist2(na[r], nb, acc[t][r] * (sa[r] * sb));
+                sum += exp(-gamma * d);
+            }
+        }
+    }
+    __device__ void finish(double* scratch) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        sum = wave_sum_f64(sum);
+        __syncthreads();
+        if (lane == 0) scratch[wave] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partial[(size_t)blockIdx.z * gridDim.x + blockIdx.x] = ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
+    }
+};
+
 __global__ void poly_finish_kernel(const double* __restrict__ partial, int n_sums, int blocks, double* __restrict__ sums) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_sums) return;
@@ -412,6 +488,37 @@ extern "C" int uspace_metric_poly_sums(const float* x, int nx, const float* y, i
     US_CHECK_LAUNCH();
     hipLaunchKernelGGL(poly_finish_kernel, dim3((unsigned)us_cdiv(n_subsets * 3, 256)), dim3(256), 0, st, (const double*)c.partial,
                        n_subsets * 3, blocks, sums);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_metric_rbf_sums(const float* x, int nx, const float* y, int ny, int F, double gamma, int normalize,
+                                      double* sums, void* workspace, size_t workspace_bytes, uspace_stream_t stream) {
+    if (!x || !y || !sums || !workspace || !size_ok(nx) || !size_ok(ny) || F < 1) return USPACE_ERR_ARG;
+    if (!(gamma >= 0.0) || gamma > DBL_MAX || (normalize != 0 && normalize != 1)) return USPACE_ERR_ARG;
+    const int n_max = nx > ny ? nx : ny;
+    if (workspace_bytes < uspace_metric_workspace_bytes(nx, ny, 1, n_max)) return USPACE_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = us_cdiv(n_max, kBM);
+    double* norm_x = (double*)workspace;
+    double* norm_y = norm_x + nx;
+    US_TRY(launch_norms(x, nx, F, norm_x, st));
+    US_TRY(launch_norms(y, ny, F, norm_y, st));
+    RbfConsumer c = {};
+    c.x = x;
+    c.y = y;
+    c.norm_x = norm_x;
+    c.norm_y = norm_y;
+    c.partial = norm_y + ny;
+    c.nx = nx;
+    c.ny = ny;
+    c.F = F;
+    c.gamma = gamma;
+    c.normalize = normalize != 0;
+    c.vec = can_vec(x, F) && can_vec(y, F);
+    hipLaunchKernelGGL(gram_kernel<RbfConsumer>, dim3((unsigned)blocks, 1, 3), dim3(256), 0, st, c);
+    US_CHECK_LAUNCH();
+    hipLaunchKernelGGL(poly_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)c.partial, 3, blocks, sums);
     US_CHECK_LAUNCH();
     return USPACE_OK;
 }

@@ -169,6 +169,7 @@ class CLIPTextTransformer(_CLIPTower):
 
 CLIP_L_VISION = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224,
                      patch_size=14, projection_dim=768, layer_norm_eps=1e-5)                  # openai/clip-vit-large-patch14
+CLIP_L_336_VISION = dict(CLIP_L_VISION, image_size=336)       # openai/clip-vit-large-patch14-336: 577 tokens (CMMD's tower)
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)                                               # HF OPENAI_CLIP_MEAN / _STD
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
