@@ -9,31 +9,7 @@ from tests import attention_wide_cases as WC
 
 pytestmark = pytest.mark.gpu
 
-PAD = 16                 # ld = C + PAD elements, the padding filled with NaN
-CANARY_ROWS = 4
-CANARY = 0x4b4b          # bf16 13 303 808: never a result
-
-
-def _padded(x, ld):
-    """bf16 [rows, C] -> device buffer [rows, ld] with NaN behind column C."""
-    buf = torch.full((x.shape[0], ld), float("nan"), dtype=torch.bfloat16)
-    buf[:, : x.shape[1]] = x
-    return buf.cuda()
-
-
-def run(q, k, v, B, N, C, scale, pad=PAD):
-    """The kernel on host operands -> out bf16 [B * N, C] on the host.  Operands with leading dimension C + pad and NaN padding; ``out``
-    with the same padding and CANARY_ROWS more rows, all pre-filled with CANARY: whatever the kernel does not own must still hold it."""
-    from uspace_amd import _hip
-    ld = C + pad
-    dq, dk, dv = (_padded(x, ld) for x in (q, k, v))
-    out = torch.full((B * N + CANARY_ROWS, ld), CANARY, dtype=torch.int16).cuda()
-    _hip.attention_wide(dq, dk, dv, B, N, C, scale, ld=ld, out=out, ld_out=ld)
-    torch.cuda.synchronize()
-    o = out.cpu()
-    assert bool((o[B * N:] == CANARY).all()), "rows behind out were written"
-    assert bool((o[:, C:] == CANARY).all()), "columns behind C were written"
-    return o[: B * N, :C].contiguous().view(torch.bfloat16)
+run = WC.run             # ld = C + 16 with NaN padding, canaries behind ``out``: shared with tests/attention_stream_cases.py
 
 
 def _threads():

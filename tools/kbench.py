@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at the BASELINE shapes (run on the GPU box): GEMMs, attention, LayerNorm.
-``--long``: the long-sequence attention kernel alone (profiles/attention_long.md)."""
+``--long``: the two streaming attention kernels alone, long and wide (profiles/attention_long.md, profiles/attention_stream.md)."""
 import argparse
 import os
 import sys
@@ -27,9 +27,20 @@ def timeit(fn, reps=20, warm=3):
 BF16_NOMINAL = 2.5e15       # dense bf16 MFMA rate of the MI355X, FLOP/s
 
 
+MIN_WINDOW = 0.1            # seconds a row of --long is timed over, at the least
+
+
+def timeit_window(fn):
+    """timeit over as many launches as fill MIN_WINDOW (a pilot of 50 gives the count; 1.2 x so that a faster second pass still fills it)."""
+    t = timeit(fn, reps=50, warm=5)
+    return timeit(fn, reps=max(50, int(1.2 * MIN_WINDOW / t) + 1), warm=0)
+
+
 def attention_long_rows():
-    """The streaming attention kernel (uspace_attention_long_bf16) at 64 x 64 latents -- L = 1 025 (unconditional) and 1 102 (T2I) at
-    B * H = 16 and 1 024 -- and at L = 334 beside the resident kernel: time, TFLOP/s (4 L^2 64 per head) and the share of the nominal rate."""
+    """The streaming attention kernels.  The long form (attention_long.hip, uspace_attention_long_bf16) at 64 x 64 latents -- L = 1 025
+    (unconditional) and 1 102 (T2I) at B * H = 16 and 1 024 -- and at L = 334 beside the resident kernel: time, TFLOP/s (4 L^2 64 per
+    head) and the share of the nominal rate.  The wide form (attention_wide.hip, uspace_attention_wide_bf16) at C = 512, N = 4 096 and B = 1, 2, 8: the
+    plan's 1-, 2- and 4-wave branches, 4 N^2 C per image."""
     H = 16
     print("| kernel | B x H | L | key_scale | us | TFLOP/s | of 2.5 PF |\n|---|---|---|---|---|---|---|")
     for L in (1025, 1102, 334):
@@ -39,9 +50,15 @@ def attention_long_rows():
                 ks = torch.exp(torch.rand(B, L, device="cuda") * 2 - 1) if scaled else None
                 forms = [("long", _hip.attention_long)] + ([("resident", _hip.attention)] if L <= 336 else [])
                 for name, fn in forms:
-                    t = timeit(lambda: fn(qkv, B, L, H, key_scale=ks), reps=50, warm=5)
+                    t = timeit_window(lambda: fn(qkv, B, L, H, key_scale=ks))
                     fl = 4.0 * L * L * 64 * B * H
                     print(f"| {name} | {B} x {H} | {L} | {'yes' if scaled else 'no'} | {t * 1e6:.1f} | {fl / t / 1e12:.1f} | {fl / t / BF16_NOMINAL:.3f} |")
+    N, C = 4096, 512
+    for B in (1, 2, 8):
+        q, k, v = (torch.randn(B * N, C, device="cuda").to(torch.bfloat16) for _ in range(3))
+        t = timeit_window(lambda: _hip.attention_wide(q, k, v, B, N, C, C ** -0.5))
+        fl = 4.0 * N * N * C * B
+        print(f"| wide C={C} | {B} x 1 | {N} | no | {t * 1e6:.1f} | {fl / t / 1e12:.1f} | {fl / t / BF16_NOMINAL:.3f} |")
 
 
 def main():
