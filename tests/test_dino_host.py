@@ -239,7 +239,9 @@ def test_abi_is_still_11_and_the_symbols_are_declared():
 def test_pair_metrics_without_structure_is_unchanged():
     from uspace_amd.tools.pair_metrics import PairMetrics
     sig = inspect.signature(PairMetrics.__init__)
-    assert list(sig.parameters) == ["self", "device", "lpips", "net", "structure"] and sig.parameters["structure"].default is None
+    assert list(sig.parameters) == ["self", "device", "lpips", "net", "structure", "identity"]
+    assert sig.parameters["structure"].default is None
+    assert sig.parameters["identity"].kind is inspect.Parameter.KEYWORD_ONLY and sig.parameters["identity"].default is None
     pm = PairMetrics(device="cpu")
     assert list(pm._parts) == ["lpips", "ssim", "psnr"] and list(pm.values) == ["lpips", "ssim", "psnr"] and pm.n == 0
     with pytest.raises(ValueError):

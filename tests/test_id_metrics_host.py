@@ -308,7 +308,9 @@ def test_pair_metrics_without_identity_is_unchanged_and_gains_the_column_with_it
     from uspace_amd.tools import id_metrics, pair_metrics
     from uspace_amd.tools.pair_metrics import PairMetrics
     sig = inspect.signature(PairMetrics.__init__)
-    assert list(sig.parameters) == ["self", "device", "lpips", "net", "structure"]      # identity= is a keyword of the call
+    assert list(sig.parameters) == ["self", "device", "lpips", "net", "structure", "identity"]
+    assert sig.parameters["structure"].default is None
+    assert sig.parameters["identity"].kind is inspect.Parameter.KEYWORD_ONLY and sig.parameters["identity"].default is None
     assert PairMetrics(device="cpu")._identity is None and PairMetrics("cpu", None, "alex", None, identity=None)._identity is None
     with pytest.raises(TypeError):
         PairMetrics(device="cpu", identitee=object())

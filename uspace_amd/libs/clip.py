@@ -201,6 +201,15 @@ class CLIPVisionTransformer(_CLIPTower, _ImageTower):
         self.visual_projection.add("weight", projection_dim, hidden_size)
         self._finish_init()
 
+    @classmethod
+    def from_hf(cls, hf):
+        """The vision tower and projection of an HF ``CLIPModel``, built from its config with its weights loaded."""
+        vc = hf.config.vision_config
+        vision = cls(vc.hidden_size, vc.intermediate_size, vc.num_hidden_layers, vc.num_attention_heads, vc.image_size,
+                     vc.patch_size, hf.config.projection_dim, vc.layer_norm_eps, vc.hidden_act)
+        vision.load_state_dict(hf.state_dict())
+        return vision
+
     def load_state_dict(self, state_dict, strict=True):
         """Accepts HF CLIPModel / CLIPVisionModel / CLIPVisionModelWithProjection checkpoints, with or without the
         ``vision_model.`` prefix; ``position_ids`` buffers and text entries are dropped."""

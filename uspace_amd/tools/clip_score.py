@@ -12,14 +12,7 @@ import torch
 
 from uspace_amd import _hip
 from uspace_amd.libs.clip import CLIPTextProjection, CLIPTextTransformer, CLIPVisionTransformer
-
-
-def _device(device):
-    if device is None:
-        if not torch.cuda.is_available():
-            raise _hip.UspaceHipError("the CLIP score needs a ROCm device (MI355X); uspace_amd has no CPU path")
-        return torch.device("cuda")
-    return torch.device(device)
+from uspace_amd.tools._inputs import rocm_device
 
 
 def _pair(a, b):
@@ -56,7 +49,7 @@ class CLIPScore:
     ``text_projection``: a CLIPTextProjection; ``tokenizer``: the HF CLIPTokenizer (or anything called the same way)."""
 
     def __init__(self, vision, text, text_projection, tokenizer, device=None, max_length=77, eos_token_id=None):
-        self.device = _device(device)
+        self.device = rocm_device(device, "the CLIP score")
         self.vision, self.text, self.text_projection = vision.to(self.device), text.to(self.device), text_projection.to(self.device)
         self.tokenizer = tokenizer
         self.max_length = max_length
@@ -71,16 +64,13 @@ class CLIPScore:
         tokenizer = CLIPTokenizer.from_pretrained(version, local_files_only=True)
         hf = CLIPModel.from_pretrained(version, local_files_only=True)
         sd = hf.state_dict()
-        tc, vc = hf.config.text_config, hf.config.vision_config
+        tc = hf.config.text_config
         text = CLIPTextTransformer(tc.vocab_size, tc.hidden_size, tc.intermediate_size, tc.num_hidden_layers, tc.num_attention_heads,
                                    tc.max_position_embeddings, tc.layer_norm_eps, tc.hidden_act)
         text.load_state_dict(sd)
-        vision = CLIPVisionTransformer(vc.hidden_size, vc.intermediate_size, vc.num_hidden_layers, vc.num_attention_heads,
-                                       vc.image_size, vc.patch_size, hf.config.projection_dim, vc.layer_norm_eps, vc.hidden_act)
-        vision.load_state_dict(sd)
         proj = CLIPTextProjection(tc.hidden_size, hf.config.projection_dim)
         proj.load_state_dict(sd)
-        return cls(vision, text, proj, tokenizer, device, tc.max_position_embeddings, getattr(tc, "eos_token_id", None))
+        return cls(CLIPVisionTransformer.from_hf(hf), text, proj, tokenizer, device, tc.max_position_embeddings, getattr(tc, "eos_token_id", None))
 
     def reset(self):
         self.score_sum = torch.zeros((), dtype=torch.float64, device=self.device)

@@ -20,14 +20,12 @@ The tower is ``CLIPVisionTransformer(**CLIP_L_336_VISION)`` (577 tokens: the str
 ``image_embeds`` are banked in a ``FeatureBank`` and normalised inside the kernel.  Where one tower serves this metric and the CLIP
 score, ``CLIPScore.image_features(images)`` can be passed to ``CMMD.update_features``.  There is no CPU path."""
 import math
-import os
-import pathlib
 
 import torch
 
 from uspace_amd import _hip
 from uspace_amd.tools.feature_metrics import FeatureBank, _device_features, _features
-from uspace_amd.tools.fid_score import IMAGE_EXTENSIONS, ImagePathDataset, _device
+from uspace_amd.tools._inputs import chunked_features, image_files, require_paths, rocm_device, uint8_batches
 
 SIGMA = 10.0
 SCALE = 1000.0
@@ -66,12 +64,6 @@ def cmmd_score(fake, real, sigma=SIGMA, scale=SCALE):
     return float(scale) * rbf_mmd2(fake, real, sigma, normalize=True, unbiased=False)
 
 
-def _bank(dims, device):
-    bank = FeatureBank.__new__(FeatureBank)          # its constructor admits the Inception blocks' widths only
-    bank._setup(dims, device, None, None)
-    return bank
-
-
 class CMMD:
     """Running CMMD: ``update`` (generated images) / ``update_real`` / ``update_features`` / ``compute``; ``save`` / ``load`` keep
     the real set's embeddings as a ``FeatureBank`` .npz.  ``vision``: a ``CLIPVisionTransformer`` (``CLIP_L_336_VISION`` for the
@@ -79,7 +71,7 @@ class CMMD:
     time (a row's embedding does not depend on it), and the unnormalised ``image_embeds`` are kept."""
 
     def __init__(self, vision, device=None, chunk=64, sigma=SIGMA, scale=SCALE):
-        self.device = _device(device)
+        self.device = rocm_device(device, "CMMD")
         self.vision = vision.to(self.device)
         self.chunk = max(1, int(chunk))
         self.dims = vision.cfg["proj_dim"]
@@ -93,26 +85,17 @@ class CMMD:
         from transformers import CLIPModel
 
         from uspace_amd.libs.clip import CLIPVisionTransformer
-        hf = CLIPModel.from_pretrained(version, local_files_only=True)
-        vc = hf.config.vision_config
-        vision = CLIPVisionTransformer(vc.hidden_size, vc.intermediate_size, vc.num_hidden_layers, vc.num_attention_heads,
-                                       vc.image_size, vc.patch_size, hf.config.projection_dim, vc.layer_norm_eps, vc.hidden_act)
-        vision.load_state_dict(hf.state_dict())
-        return cls(vision, device)
+        return cls(CLIPVisionTransformer.from_hf(CLIPModel.from_pretrained(version, local_files_only=True)), device)
 
     def reset(self, real=True):
-        self.fake = _bank(self.dims, self.device)
+        self.fake = FeatureBank.of_width(self.dims, self.device)
         if real:
-            self.real = _bank(self.dims, self.device)
+            self.real = FeatureBank.of_width(self.dims, self.device)
 
     @torch.no_grad()
     def image_features(self, images, quantize=True):
         """images [B, 3, H, H] in [0, 1] on the device -> image_embeds fp32 [B, dims] (not normalised)."""
-        _hip.require_device(images, "images")
-        out = torch.empty(images.shape[0], self.dims, dtype=torch.float32, device=images.device)
-        for lo in range(0, images.shape[0], self.chunk):
-            out[lo:lo + self.chunk] = self.vision(self.vision.preprocess(images[lo:lo + self.chunk], quantize=quantize))
-        return out
+        return chunked_features(lambda x: self.vision(self.vision.preprocess(x, quantize=quantize)), images, self.chunk, self.dims)
 
     def update(self, images, quantize=True):
         """Add generated images."""
@@ -146,14 +129,11 @@ class CMMD:
 def _bank_of_path(path, metric, batch_size, device):
     if str(path).endswith(".npz"):
         return FeatureBank.load(path, device=device)
-    files = sorted([file for ext in IMAGE_EXTENSIONS for file in pathlib.Path(path).glob(f"*.{ext}")])
-    data = ImagePathDataset(files)
-    bank = _bank(metric.dims, metric.device)
-    for lo in range(0, len(files), batch_size):
-        x = torch.stack([data[i] for i in range(lo, min(lo + batch_size, len(files)))]).to(metric.device).float() / 255
-        # quantize=True on decoded bytes is the identity, exactly: fl(255 fl(q / 255)) + 0.5 floors to q, so a folder written by
-        # save_image gives the bits CMMD.update gives on the samples themselves (without it 255 fl(q / 255) misses q by an ulp)
-        bank.update_features(metric.image_features(x, quantize=True))
+    bank = FeatureBank.of_width(metric.dims, metric.device)
+    for batch in uint8_batches(image_files(path), batch_size):
+        # quantize=True on decoded bytes is the identity, exactly (see ``_inputs.quantize``): a folder written by save_image gives
+        # the bits CMMD.update gives on the samples themselves (without it 255 fl(q / 255) misses q by an ulp)
+        bank.update_features(metric.image_features(batch.to(metric.device).float() / 255, quantize=True))
     return bank
 
 
@@ -161,12 +141,10 @@ def calculate_cmmd_given_paths(paths, vision, device=None, batch_size=50, sigma=
     """CMMD between two folders of (square, equally sized) images, read in ``fid_score``'s file order, or saved banks (.npz) in
     either position: ``paths[0]`` real, ``paths[1]`` generated, as ``calculate_fid_given_paths``.  ``vision`` may be None when both
     are banks."""
-    for p in paths:
-        if not os.path.exists(p):
-            raise RuntimeError("Invalid path: %s" % p)
+    require_paths(paths)
     if vision is None and not all(str(p).endswith(".npz") for p in paths[:2]):
         raise ValueError("an image folder needs the vision tower")
-    device = _device(device)
+    device = rocm_device(device, "CMMD")
     metric = CMMD(vision, device, chunk=batch_size) if vision is not None else None
     real, fake = (_bank_of_path(p, metric, batch_size, device) for p in paths[:2])
     return cmmd_score(fake, real, sigma, scale)

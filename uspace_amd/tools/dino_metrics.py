@@ -8,15 +8,12 @@
 
 ``FeatureBank.from_features(DinoFeatures(tower).features(images))`` (``tools/feature_metrics.py``) gives KID / PRDC on the same features.
 The towers' weights are never downloaded: build a ``DinoVisionTransformer`` with ``weights=`` or ``seed=`` and pass it in."""
-import os
-import pathlib
-
 import numpy as np
 import torch
 
 from uspace_amd import _hip
-from uspace_amd.tools.fid_score import (IMAGE_EXTENSIONS, FIDStatistics, ImagePathDataset, _device,
-                                        calculate_frechet_distance)
+from uspace_amd.tools._inputs import chunked_features, image_files, require_paths, rocm_device, uint8_batches
+from uspace_amd.tools.fid_score import FIDStatistics, calculate_frechet_distance
 
 
 class DinoFeatures:
@@ -30,17 +27,7 @@ class DinoFeatures:
 
     @torch.no_grad()
     def features(self, images, quantize=True):
-        _hip.require_device(images, "images")
-        out = torch.empty(images.shape[0], self.dims, dtype=torch.float32, device=images.device)
-        for lo in range(0, images.shape[0], self.chunk):
-            out[lo:lo + self.chunk] = self.tower(self.tower.preprocess(images[lo:lo + self.chunk], quantize=quantize))
-        return out
-
-
-def _statistics(dims, device):
-    st = FIDStatistics.__new__(FIDStatistics)      # its constructor admits the Inception blocks' widths only
-    st._setup(dims, device, None, None)
-    return st
+        return chunked_features(lambda x: self.tower(self.tower.preprocess(x, quantize=quantize)), images, self.chunk, self.dims)
 
 
 class FDDino:
@@ -48,15 +35,15 @@ class FDDino:
     keep the real set's statistics as ``FIDStatistics.save`` writes them (``mu``, ``sigma``)."""
 
     def __init__(self, tower, device=None, chunk=64):
-        self.device = _device(device)
+        self.device = rocm_device(device, "FD-DINO")
         self.extractor = DinoFeatures(tower, chunk)
         self.dims = self.extractor.dims
         self.reset()
 
     def reset(self, real=True):
-        self.fake = _statistics(self.dims, self.device)
+        self.fake = FIDStatistics.of_width(self.dims, self.device)
         if real:
-            self.real = _statistics(self.dims, self.device)
+            self.real = FIDStatistics.of_width(self.dims, self.device)
             self._real_loaded = None
 
     def update(self, images, quantize=True):
@@ -96,21 +83,16 @@ def _folder_statistics(path, extractor, batch_size, device):
     if str(path).endswith(".npz"):
         with np.load(path) as f:
             return f["mu"][:], f["sigma"][:]
-    files = sorted(file for ext in IMAGE_EXTENSIONS for file in pathlib.Path(path).glob(f"*.{ext}"))
-    data = ImagePathDataset(files)
-    st = _statistics(extractor.dims, device)
-    for lo in range(0, len(files), batch_size):
-        x = torch.stack([data[i] for i in range(lo, min(lo + batch_size, len(files)))]).to(device).float() / 255
-        st.update_features(extractor.features(x, quantize=False))
+    st = FIDStatistics.of_width(extractor.dims, device)
+    for batch in uint8_batches(image_files(path), batch_size):
+        st.update_features(extractor.features(batch.to(device).float() / 255, quantize=False))
     return st.mu, st.sigma
 
 
 def calculate_fd_dino_given_paths(paths, tower, device=None, batch_size=50):
     """FD-DINO between two folders of (square, equally sized) images or ``.npz`` statistics files."""
-    device = _device(device)
-    for p in paths:
-        if not os.path.exists(p):
-            raise RuntimeError("Invalid path: %s" % p)
+    device = rocm_device(device, "FD-DINO")
+    require_paths(paths)
     ex = DinoFeatures(tower, batch_size)
     m1, s1 = _folder_statistics(paths[0], ex, batch_size, device)
     m2, s2 = _folder_statistics(paths[1], ex, batch_size, device)

@@ -9,7 +9,7 @@ weights are the pytorch-fid port's, so these are that port's numbers, not the TF
 import numpy as np
 import torch
 
-from uspace_amd.tools import feature_metrics, fid_score, sfid_score
+from uspace_amd.tools import _inputs, feature_metrics, sfid_score
 from uspace_amd.tools.fid_score import FIDStatistics, calculate_frechet_distance
 from uspace_amd.tools.inception import SPATIAL_CHANNELS, SPATIAL_STAGE, InceptionHead, InceptionV3
 from uspace_amd.tools.inception_score import InceptionScore
@@ -18,7 +18,7 @@ from uspace_amd.tools.inception_score import InceptionScore
 class EvalSuite:
     def __init__(self, device=None, model=None, head=None, bank=False, bias=True, spatial_stage=SPATIAL_STAGE,
                  spatial_channels=SPATIAL_CHANNELS):
-        self.device = fid_score._device(device)
+        self.device = _inputs.rocm_device(device, "EvalSuite")
         self._model = model
         self._head = head
         self.fid = FIDStatistics(2048, device=self.device, model=model)
@@ -55,7 +55,7 @@ class EvalSuite:
         x * 255 + 0.5 -> clamp -> uint8, then / 255)."""
         x = images.detach().to(self.device, torch.float32)
         if quantize:
-            x = x.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8).float() / 255
+            x = _inputs.quantize(x)
         pool, spatial = self.model.suite(x, spatial_stage=self.sfid.spatial_stage, spatial_channels=self.sfid.spatial_channels)
         head = self.head
         self.fid.update_features(pool)

@@ -14,34 +14,21 @@ integers, compares and divides.  With D2(i, j) = max(0, |x_i|^2 + |y_j|^2 - 2 x_
     recall    = mean_i [ #{j : D2(real_i, fake_j) <= rG_j} > 0 ]      coverage = mean_i [ min_j D2(real_i, fake_j) <= rR_i ]
 
 There is no CPU path: a CPU tensor or a missing library raises ``UspaceHipError``."""
-import os
-import pathlib
-
 import numpy as np
 import torch
 
 from uspace_amd import _hip
 from uspace_amd.tools import fid_score
+from uspace_amd.tools._inputs import image_files, require_paths, rocm_device
 from uspace_amd.tools.inception import InceptionV3
 
 MAX_NEAREST_K = 16
 _CHUNK = 1024
 
 
-class FeatureBank:
-    """The feature-keeping sibling of ``FIDStatistics``: fp32 features [n, dims] on the device, grown by chunks."""
-
-    def __init__(self, dims=2048, device=None, model=None):
-        if dims not in InceptionV3.BLOCK_INDEX_BY_DIM:
-            raise ValueError(f"dims must be one of {sorted(InceptionV3.BLOCK_INDEX_BY_DIM)}")
-        self._setup(dims, fid_score._device(device), model, InceptionV3.BLOCK_INDEX_BY_DIM[dims])
-
-    def _setup(self, dims, device, model, block):
-        self.dims = int(dims)
-        self.device = device
-        self.block = block
-        self._model = model
-        self.reset()
+class FeatureBank(fid_score.FeatureAccumulator):
+    """The feature-keeping sibling of ``FIDStatistics`` (same constructor, ``of_width``, ``model`` and ``update``): fp32 features
+    [n, dims] on the device, grown by chunks."""
 
     @classmethod
     def from_features(cls, feat, device=None):
@@ -50,8 +37,7 @@ class FeatureBank:
         feat = torch.as_tensor(feat)
         if feat.dim() != 2 or feat.shape[1] < 1:
             raise ValueError(f"expected features [n, F], got {tuple(feat.shape)}")
-        bank = cls.__new__(cls)
-        bank._setup(feat.shape[1], torch.device(device) if device is not None else feat.device, None, None)
+        bank = cls.of_width(feat.shape[1], device if device is not None else feat.device)
         bank.update_features(feat)
         return bank
 
@@ -63,27 +49,11 @@ class FeatureBank:
         return self.n
 
     @property
-    def model(self):
-        if self._model is None:
-            if self.block is None:
-                raise ValueError("a bank made from features has no model: use update_features")
-            self._model = InceptionV3([self.block]).to(self.device)
-        return self._model
-
-    @property
     def features(self):
         """fp32 [n, dims] on the device (a view of the bank's storage)."""
         if self._buf is None:
             return torch.empty(0, self.dims, dtype=torch.float32, device=self.device)
         return self._buf[:self.n]
-
-    @torch.no_grad()
-    def update(self, images, quantize=True):
-        """Add images [B, 3, H, W] in [0, 1], quantised as ``FIDStatistics.update`` does (save_image's rounding)."""
-        x = images.detach().to(self.device, torch.float32)
-        if quantize:
-            x = x.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8).float() / 255
-        self.update_features(self.model.features(x, self.block))
 
     @torch.no_grad()
     def update_features(self, feat):
@@ -114,7 +84,7 @@ class FeatureBank:
         """The bank ``save`` wrote, on ``device`` (default: the ROCm device)."""
         with np.load(path) as f:
             feat = np.asarray(f["features"], dtype=np.float32)
-        return cls.from_features(torch.from_numpy(feat), device=fid_score._device(device))
+        return cls.from_features(torch.from_numpy(feat), device=rocm_device(device, "FeatureBank.load"))
 
 
 def _features(a, name):
@@ -197,16 +167,13 @@ def bank_of_path(path, model, batch_size, dims, device, num_workers=8):
     """A ``FeatureBank`` of an image folder (the files ``fid_score`` would read, in its order) or of a saved bank (.npz)."""
     if str(path).endswith(".npz"):
         return FeatureBank.load(path, device=device)
-    files = sorted([file for ext in fid_score.IMAGE_EXTENSIONS for file in pathlib.Path(path).glob(f"*.{ext}")])
-    act = fid_score.get_activations(files, model, batch_size, dims, device, num_workers)
+    act = fid_score.get_activations(image_files(path), model, batch_size, dims, device, num_workers)
     return FeatureBank.from_features(torch.from_numpy(act.astype(np.float32)), device=device)
 
 
 def _banks_of_paths(paths, device, batch_size, dims, num_workers, model):
-    device = fid_score._device(device)
-    for p in paths:
-        if not os.path.exists(p):
-            raise RuntimeError("Invalid path: %s" % p)
+    device = rocm_device(device, "KID / PRDC")
+    require_paths(paths)
     if model is None and not all(str(p).endswith(".npz") for p in paths):
         model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(device)
     return [bank_of_path(p, model, batch_size, dims, device, num_workers) for p in paths[:2]]

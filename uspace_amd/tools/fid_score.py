@@ -5,43 +5,15 @@ the device (what ``transforms.ToTensor`` does).
 
 ``FIDStatistics`` is the in-memory path: images straight out of the sampler and the VAE decoder, quantised as
 ``save_image`` does, give the statistics the PNG round trip would give."""
-import os
-import pathlib
-
 import numpy as np
 import torch
-from PIL import Image
 from scipy import linalg
 
 from uspace_amd import _hip
+from uspace_amd.tools import _inputs
+from uspace_amd.tools._inputs import IMAGE_EXTENSIONS, MAX_WORKERS, ImagePathDataset, _batches  # noqa: F401  (the reference's names)
+from uspace_amd.tools._inputs import image_files, require_paths, rocm_device, unit_batches
 from uspace_amd.tools.inception import BLOCK_DIMS, InceptionV3
-
-try:
-    from tqdm import tqdm
-except ImportError:
-    def tqdm(x):
-        return x
-
-IMAGE_EXTENSIONS = {"bmp", "jpg", "jpeg", "pgm", "png", "ppm", "tif", "tiff", "webp"}
-MAX_WORKERS = 16
-
-
-class ImagePathDataset(torch.utils.data.Dataset):
-    """Images as uint8 [3, H, W] tensors (RGB)."""
-
-    def __init__(self, files, transforms=None):
-        self.files = files
-        self.transforms = transforms
-
-    def __len__(self):
-        return len(self.files)
-
-    def __getitem__(self, i):
-        img = Image.open(self.files[i]).convert("RGB")
-        if self.transforms is not None:
-            return self.transforms(img)
-        return torch.from_numpy(np.array(img, dtype=np.uint8)).permute(2, 0, 1).contiguous()
-
 
 def _block_of(model, dims):
     block = InceptionV3.BLOCK_INDEX_BY_DIM[dims]
@@ -50,24 +22,13 @@ def _block_of(model, dims):
     return block
 
 
-def _batches(files, batch_size, num_workers):
-    if batch_size > len(files):
-        print("Warning: batch size is bigger than the data size. Setting batch size to data size")
-        batch_size = len(files)
-    loader = torch.utils.data.DataLoader(ImagePathDataset(files), batch_size=batch_size, shuffle=False, drop_last=False,
-                                         num_workers=min(int(num_workers), MAX_WORKERS))
-    return batch_size, loader
-
-
 def get_activations(files, model, batch_size=50, dims=2048, device="cpu", num_workers=8):
     """Pool features [len(files), dims] (float64 array of fp32 values) of the images in ``files``, in order."""
     model.eval()
     block = _block_of(model, dims)
-    _, loader = _batches(files, batch_size, num_workers)
     pred_arr = np.empty((len(files), dims))
     start = 0
-    for batch in tqdm(loader):
-        x = batch.to(device).float() / 255
+    for x in unit_batches(files, batch_size, num_workers, device):
         pred = model.features(x, block).cpu().numpy()
         pred_arr[start:start + pred.shape[0]] = pred
         start += pred.shape[0]
@@ -111,22 +72,12 @@ def compute_statistics_of_path(path, model, batch_size, dims, device, num_worker
         with np.load(path) as f:
             m, s = f["mu"][:], f["sigma"][:]
     else:
-        path = pathlib.Path(path)
-        files = sorted([file for ext in IMAGE_EXTENSIONS for file in path.glob(f"*.{ext}")])
-        m, s = calculate_activation_statistics(files, model, batch_size, dims, device, num_workers)
+        m, s = calculate_activation_statistics(image_files(path), model, batch_size, dims, device, num_workers)
     return m, s
 
 
-def _device(device):
-    if device is None:
-        if not torch.cuda.is_available():
-            raise _hip.UspaceHipError("FID needs a ROCm device (MI355X); uspace_amd has no CPU path")
-        return torch.device("cuda")
-    return torch.device(device)
-
-
 def save_statistics_of_path(path, out_path, device=None, batch_size=50, dims=2048, num_workers=8):
-    device = _device(device)
+    device = rocm_device(device, "FID")
     model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(device)
     m1, s1 = compute_statistics_of_path(path, model, batch_size, dims, device, num_workers)
     np.savez(out_path, mu=m1, sigma=s1)
@@ -135,10 +86,8 @@ def save_statistics_of_path(path, out_path, device=None, batch_size=50, dims=204
 def calculate_fid_given_paths(paths, device=None, batch_size=50, dims=2048, num_workers=8, model=None):
     """FID between two folders of images or .npz statistics files.  ``model`` (an InceptionV3) overrides the pretrained
     network, e.g. with seeded weights."""
-    device = _device(device)
-    for p in paths:
-        if not os.path.exists(p):
-            raise RuntimeError("Invalid path: %s" % p)
+    device = rocm_device(device, "FID")
+    require_paths(paths)
     if model is None:
         model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(device)
     m1, s1 = compute_statistics_of_path(paths[0], model, batch_size, dims, device, num_workers)
@@ -154,41 +103,57 @@ def finalize_statistics(n, shift, s1, s2):
     return mu, sigma
 
 
-class FIDStatistics:
-    """Running mean and covariance of FID features on the device.  S1 = sum(x - c) and S2 = sum((x - c)(x - c)^T) are
-    accumulated in fp64 by uspace_fid_stats_accumulate, with c the first batch's mean (fp64), so a large common offset
-    of the features costs no precision; ``mu`` / ``sigma`` equal np.mean / np.cov(rowvar=False) of all features seen."""
+_NO_MODEL = object()      # ``model`` of an accumulator over arbitrary features (``of_width``)
+
+
+class FeatureAccumulator:
+    """What ``FIDStatistics`` and ``FeatureBank`` share: the width check of the Inception pool blocks, the lazily built network
+    and ``update`` on images.  ``of_width`` builds one over arbitrary features [n, dims], with no model behind it."""
 
     def __init__(self, dims=2048, device=None, model=None):
-        if dims not in InceptionV3.BLOCK_INDEX_BY_DIM:
+        if model is _NO_MODEL:
+            self._setup(dims, device, None, None)
+        elif dims not in InceptionV3.BLOCK_INDEX_BY_DIM:
             raise ValueError(f"dims must be one of {sorted(InceptionV3.BLOCK_INDEX_BY_DIM)}")
-        self._setup(dims, _device(device), model, InceptionV3.BLOCK_INDEX_BY_DIM[dims])
+        else:
+            self._setup(dims, device, model, InceptionV3.BLOCK_INDEX_BY_DIM[dims])
+
+    @classmethod
+    def of_width(cls, dims, device=None):
+        """An accumulator of features of any width ``dims`` >= 1, fed by ``update_features`` only."""
+        return cls(dims, device, _NO_MODEL)
 
     def _setup(self, dims, device, model, block):
-        self.dims = dims
-        self.device = device
+        self.dims = int(dims)
+        self.device = rocm_device(device, type(self).__name__)
         self.block = block
         self._model = model
         self.reset()
 
-    def reset(self):
-        self.n = 0
-        self.shift = self.s1 = self.s2 = None
-
     @property
     def model(self):
         if self._model is None:
+            if self.block is None:
+                raise ValueError(f"a {type(self).__name__} made for features has no model: use update_features")
             self._model = InceptionV3([self.block]).to(self.device)
         return self._model
 
     @torch.no_grad()
     def update(self, images, quantize=True):
         """Add images [B, 3, H, W] in [0, 1].  quantize=True applies save_image's x * 255 + 0.5 -> clamp -> uint8, then
-        / 255, so the statistics equal those of the written PNGs read back."""
+        / 255 (``_inputs.quantize``), so the result equals that of the written PNGs read back."""
         x = images.detach().to(self.device, torch.float32)
-        if quantize:
-            x = x.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8).float() / 255
-        self.update_features(self.model.features(x, self.block))
+        self.update_features(self.model.features(_inputs.quantize(x) if quantize else x, self.block))
+
+
+class FIDStatistics(FeatureAccumulator):
+    """Running mean and covariance of FID features on the device.  S1 = sum(x - c) and S2 = sum((x - c)(x - c)^T) are
+    accumulated in fp64 by uspace_fid_stats_accumulate, with c the first batch's mean (fp64), so a large common offset
+    of the features costs no precision; ``mu`` / ``sigma`` equal np.mean / np.cov(rowvar=False) of all features seen."""
+
+    def reset(self):
+        self.n = 0
+        self.shift = self.s1 = self.s2 = None
 
     @torch.no_grad()
     def update_features(self, feat):

@@ -9,11 +9,10 @@ folders by file name; ``PairMetrics(identity=tower)`` (``tools/pair_metrics.py``
 tower's weights are never downloaded: build a ``Backbone`` with ``weights=`` or ``seed=`` and pass it in."""
 import numpy as np
 import torch
-from PIL import Image
 
 from uspace_amd import _hip
 from uspace_amd.libs.arcface import similarity
-from uspace_amd.tools.fid_score import ImagePathDataset, _device
+from uspace_amd.tools import _inputs
 
 
 class IDSimilarity:
@@ -34,7 +33,7 @@ class IDSimilarity:
             raise ValueError(f"expected images [B, 3, H, W], got {tuple(images.shape)}")
         x = images.detach().to(torch.float32)
         if quantize:
-            x = x.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8).float() / 255
+            x = _inputs.quantize(x)
         return self.tower.embed_nhwc(self.tower.preprocess(x, normalize=True, crop=self.crop), self.chunk)
 
     @torch.no_grad()
@@ -57,25 +56,11 @@ def calculate_id_similarity_given_paths(dir_a, dir_b, tower, device=None, batch_
     """dict(identity, n): the mean ID similarity between the images of two folders paired by file name (a numpy fp64 mean), and
     ``values``, the fp64 array behind it.  A name present in one folder only, or an image whose size differs from its partner's or
     from the first pair's, raises ValueError, as ``calculate_pair_metrics_given_paths`` does."""
-    from uspace_amd.tools.pair_metrics import _image_files
-    device = _device(device)
-    fa, fb = _image_files(dir_a), _image_files(dir_b)
-    only = sorted(set(fa) ^ set(fb))
-    if only or not fa:
-        raise ValueError(f"the folders do not pair up by file name: {only[:8] if only else 'no images'}")
-    names = sorted(fa)
-    sizes = {}
-    for n in names:
-        with Image.open(fa[n]) as ia, Image.open(fb[n]) as ib:
-            first = sizes.setdefault("first", ia.size)
-            if ia.size != ib.size or ia.size != first:
-                raise ValueError(f"image sizes differ at {n!r}: {ia.size} and {ib.size} (the first pair is {first})")
-    da, db = ImagePathDataset([fa[n] for n in names]), ImagePathDataset([fb[n] for n in names])
+    device = _inputs.rocm_device(device, "the ID similarity")
+    _names, files_a, files_b = _inputs.paired_image_files(dir_a, dir_b)
     metric = IDSimilarity(tower, crop, chunk=2 * batch_size)
     parts = []
-    for lo in range(0, len(names), batch_size):
-        idx = range(lo, min(lo + batch_size, len(names)))
-        xa, xb = torch.stack([da[i] for i in idx]), torch.stack([db[i] for i in idx])
+    for xa, xb in zip(_inputs.uint8_batches(files_a, batch_size), _inputs.uint8_batches(files_b, batch_size)):
         parts.append(metric(xa.to(device).float() / 255, xb.to(device).float() / 255, quantize=False))
     values = torch.cat(parts).cpu().numpy()
     return {"identity": float(np.mean(values)), "n": len(values), "values": values}

@@ -11,13 +11,11 @@ terms with p_ic == 0 contributing 0, and the result is (mean_k score_k, std_k sc
 The weights are those of the pytorch-fid port of the network, so these are that port's numbers, not the TF graph's.
 ``bias=False`` drops ``fc.bias`` from the logits (believed to be torch-fidelity's "unbiased logits"; unverified: an option, not
 a parity claim).  There is no CPU path."""
-import pathlib
-
 import numpy as np
 import torch
 
 from uspace_amd import _hip
-from uspace_amd.tools import fid_score
+from uspace_amd.tools import _inputs
 from uspace_amd.tools.inception import BLOCK_DIMS, InceptionHead, InceptionV3
 
 
@@ -56,7 +54,7 @@ class InceptionScore:
     block 3) and ``head`` (an ``InceptionHead``) default to the pretrained ones from the local cache."""
 
     def __init__(self, device=None, model=None, head=None, bias=True):
-        self.device = fid_score._device(device)
+        self.device = _inputs.rocm_device(device, "the Inception Score")
         self._model = model
         self._head = head
         self.bias = bool(bias)
@@ -95,9 +93,7 @@ class InceptionScore:
         """Add images [B, 3, H, W] in [0, 1], quantised as ``FIDStatistics.update`` does (save_image's x * 255 + 0.5 -> clamp ->
         uint8, then / 255)."""
         x = images.detach().to(self.device, torch.float32)
-        if quantize:
-            x = x.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8).float() / 255
-        self.update_features(self.model.features(x, 3))
+        self.update_features(self.model.features(_inputs.quantize(x) if quantize else x, 3))
 
     @torch.no_grad()
     def update_features(self, pool):
@@ -128,15 +124,11 @@ class InceptionScore:
 
 def calculate_is_given_path(path, device=None, batch_size=50, num_workers=8, model=None, head=None, splits=10, bias=True):
     """Inception Score (mean, std) of a folder of images: the files ``fid_score`` would read, in its order and batches."""
-    device = fid_score._device(device)
-    path = pathlib.Path(path)
-    if not path.exists():
-        raise RuntimeError("Invalid path: %s" % path)
-    files = sorted([file for ext in fid_score.IMAGE_EXTENSIONS for file in path.glob(f"*.{ext}")])
+    device = _inputs.rocm_device(device, "the Inception Score")
+    _inputs.require_paths([path])
     acc = InceptionScore(device=device, model=model, head=head, bias=bias)
-    _, loader = fid_score._batches(files, batch_size, num_workers)
-    for batch in fid_score.tqdm(loader):
-        acc.update(batch.to(device).float() / 255, quantize=False)
+    for x in _inputs.unit_batches(_inputs.image_files(path), batch_size, num_workers, device):
+        acc.update(x, quantize=False)
     return acc.compute(splits)
 
 

@@ -5,14 +5,11 @@ image (the reference's ``vis_reversible``, which it judges by eye).
 
 ``psnr`` and ``ssim`` take any pair of equal-shaped image batches; ``PairMetrics`` accumulates all three over batches of images
 in [0, 1]; ``calculate_pair_metrics_given_paths`` pairs two folders by file name; ``reconstruction_fidelity`` is the round trip."""
-import pathlib
-
 import numpy as np
 import torch
-from PIL import Image
 
 from uspace_amd import _hip
-from uspace_amd.tools.fid_score import IMAGE_EXTENSIONS, ImagePathDataset, _device
+from uspace_amd.tools import _inputs
 from uspace_amd.tools.lpips import LPIPS
 
 
@@ -61,31 +58,19 @@ def ssim(a, b, data_range=1.0, ws=None):
     return out
 
 
-class _IdentityColumn(type):
-    """``PairMetrics(..., identity=tower)``: the keyword is taken here, before ``__init__`` runs, and kept on the instance.
-    ``PairMetrics.__init__`` keeps the parameter list it had (``tests/test_dino_host.py`` pins it name by name), so code that
-    inspects or forwards that list sees no difference; subclasses inherit the keyword."""
-
-    def __call__(cls, *args, identity=None, **kw):
-        self = cls.__new__(cls)
-        self._identity = identity
-        self.__init__(*args, **kw)
-        return self
-
-
-class PairMetrics(metaclass=_IdentityColumn):
+class PairMetrics:
     """Per-pair LPIPS / SSIM / PSNR accumulated over batches.  ``lpips``: an ``LPIPS`` module (e.g. with seeded weights) or a
     weight file's path; with neither, ``LPIPS(net)`` needs its weights at first use and says so.  ``structure``: a
     ``DinoVisionTransformer`` (usually ``DINO_B8``) adds a ``structure`` column, ``dino_metrics.structure_distance`` of every
     pair on that tower's last-layer keys; ``identity``: an ArcFace ``Backbone`` (usually ``IR_SE50``) adds an ``identity`` column,
-    ``id_metrics.id_similarity`` of every pair (a keyword of the call, see ``_IdentityColumn``).  The defaults None leave the three
-    columns as they are."""
+    ``id_metrics.id_similarity`` of every pair (keyword only).  The defaults None leave the three columns as they are."""
 
-    def __init__(self, device=None, lpips=None, net="alex", structure=None):
-        self.device = _device(device)
+    def __init__(self, device=None, lpips=None, net="alex", structure=None, *, identity=None):
+        self.device = _inputs.rocm_device(device, "PairMetrics")
         self.net = net
         self._lpips = lpips
         self._structure = structure
+        self._identity = identity
         self.reset()
 
     @property
@@ -116,7 +101,7 @@ class PairMetrics(metaclass=_IdentityColumn):
         clamp -> uint8, then / 255), applied to both sides: the numbers of the written PNGs."""
         x, y = (t.detach().to(self.device, torch.float32) for t in (original, edited))
         if quantize:
-            x, y = (t.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8).float() / 255 for t in (x, y))
+            x, y = _inputs.quantize(x), _inputs.quantize(y)
         self._parts["lpips"].append(self.lpips(x, y, normalize=True))
         self._parts["ssim"].append(ssim(x, y, 1.0))
         self._parts["psnr"].append(psnr(x, y, 1.0))
@@ -141,29 +126,12 @@ class PairMetrics(metaclass=_IdentityColumn):
         return out
 
 
-def _image_files(path):
-    path = pathlib.Path(path)
-    return {f.stem: f for f in sorted(file for ext in IMAGE_EXTENSIONS for file in path.glob(f"*.{ext}"))}
-
-
 def calculate_pair_metrics_given_paths(dir_a, dir_b, device=None, batch_size=50, lpips=None, net="alex"):
     """Mean LPIPS / SSIM / PSNR between the images of two folders paired by file name (``PairMetrics.compute``'s dict).  A name
     present in one folder only, or an image whose size differs from its partner's or from the first pair's, raises ValueError."""
-    fa, fb = _image_files(dir_a), _image_files(dir_b)
-    only = sorted(set(fa) ^ set(fb))
-    if only or not fa:
-        raise ValueError(f"the folders do not pair up by file name: {only[:8] if only else 'no images'}")
-    names = sorted(fa)
-    sizes = {}
-    for n in names:
-        with Image.open(fa[n]) as ia, Image.open(fb[n]) as ib:
-            if ia.size != ib.size or ia.size != sizes.setdefault("first", ia.size):
-                raise ValueError(f"image sizes differ at {n!r}: {ia.size} and {ib.size} (the first pair is {sizes['first']})")
-    da, db = ImagePathDataset([fa[n] for n in names]), ImagePathDataset([fb[n] for n in names])
+    _names, files_a, files_b = _inputs.paired_image_files(dir_a, dir_b)
     pm = PairMetrics(device=device, lpips=lpips, net=net)
-    for lo in range(0, len(names), batch_size):
-        idx = range(lo, min(lo + batch_size, len(names)))
-        xa, xb = torch.stack([da[i] for i in idx]), torch.stack([db[i] for i in idx])
+    for xa, xb in zip(_inputs.uint8_batches(files_a, batch_size), _inputs.uint8_batches(files_b, batch_size)):
         pm.update(xa.to(pm.device).float() / 255, xb.to(pm.device).float() / 255, quantize=False)
     return pm.compute()
 

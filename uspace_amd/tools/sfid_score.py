@@ -13,13 +13,10 @@ device by uspace_fid_stats_accumulate and finished by ``finalize_statistics``, e
 
 Statistics files: ``mu_s`` / ``sigma_s`` (the keys of ADM's reference batches) hold the spatial statistics, ``mu`` / ``sigma`` the
 pool statistics; a file may hold either pair or both."""
-import os
-import pathlib
-
 import numpy as np
 import torch
 
-from uspace_amd.tools import fid_score
+from uspace_amd.tools import _inputs
 from uspace_amd.tools.fid_score import FIDStatistics, calculate_frechet_distance
 from uspace_amd.tools.inception import SPATIAL_CHANNELS, SPATIAL_STAGE, STAGE_SHAPES, InceptionV3
 
@@ -42,18 +39,16 @@ class SpatialFIDStatistics(FIDStatistics):
     ``update`` / ``update_features``, with ``dims = 17 * 17 * spatial_channels`` and the features from ``InceptionV3.suite``."""
 
     def __init__(self, device=None, model=None, spatial_stage=SPATIAL_STAGE, spatial_channels=SPATIAL_CHANNELS):
-        # (FIDStatistics.__init__ admits only the four pool widths; everything else is its _setup)
+        # (FIDStatistics.__init__ admits only the four pool widths; everything else is the base's _setup)
         self.spatial_stage = int(spatial_stage)
         self.spatial_channels = int(spatial_channels)
-        self._setup(spatial_dims(spatial_stage, spatial_channels), fid_score._device(device), model, 3)
+        self._setup(spatial_dims(spatial_stage, spatial_channels), device, model, 3)
 
     @torch.no_grad()
     def update(self, images, quantize=True):
         """Add images [B, 3, H, W] in [0, 1]; ``quantize`` as in ``FIDStatistics.update``."""
         x = images.detach().to(self.device, torch.float32)
-        if quantize:
-            x = x.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8).float() / 255
-        _pool, spatial = self.model.suite(x, spatial_stage=self.spatial_stage, spatial_channels=self.spatial_channels)
+        _pool, spatial = self.model.suite(_inputs.quantize(x) if quantize else x, spatial_stage=self.spatial_stage, spatial_channels=self.spatial_channels)
         self.update_features(spatial)
 
     def save(self, path):
@@ -71,19 +66,13 @@ def load_statistics(path, kind):
         return f[k_mu][:], f[k_sigma][:]
 
 
-def _files(path):
-    return sorted([file for ext in fid_score.IMAGE_EXTENSIONS for file in pathlib.Path(path).glob(f"*.{ext}")])
-
-
 def suite_statistics_of_folder(path, model, batch_size, device, num_workers=8, spatial_stage=SPATIAL_STAGE,
                                spatial_channels=SPATIAL_CHANNELS):
     """(FIDStatistics, SpatialFIDStatistics) of a folder's images, read as ``fid_score`` reads them: one network pass per batch."""
-    files = _files(path)
     pool_st = FIDStatistics(2048, device=device, model=model)
     sp_st = SpatialFIDStatistics(device=device, model=model, spatial_stage=spatial_stage, spatial_channels=spatial_channels)
-    _, loader = fid_score._batches(files, batch_size, num_workers)
-    for batch in fid_score.tqdm(loader):
-        pool, spatial = model.suite(batch.to(device).float() / 255, spatial_stage=spatial_stage, spatial_channels=spatial_channels)
+    for x in _inputs.unit_batches(_inputs.image_files(path), batch_size, num_workers, device):
+        pool, spatial = model.suite(x, spatial_stage=spatial_stage, spatial_channels=spatial_channels)
         pool_st.update_features(pool)
         sp_st.update_features(spatial)
     return pool_st, sp_st
@@ -101,7 +90,7 @@ def compute_spatial_statistics_of_path(path, model, batch_size, device, num_work
 def save_statistics_of_path(path, out_path, device=None, batch_size=50, num_workers=8, model=None, spatial_stage=SPATIAL_STAGE,
                             spatial_channels=SPATIAL_CHANNELS):
     """The twin of ``fid_score.save_statistics_of_path`` that writes all four arrays: mu, sigma (pool) and mu_s, sigma_s."""
-    device = fid_score._device(device)
+    device = _inputs.rocm_device(device, "sFID")
     if model is None:
         model = InceptionV3([3]).to(device)
     pool_st, sp_st = suite_statistics_of_folder(path, model, batch_size, device, num_workers, spatial_stage, spatial_channels)
@@ -111,10 +100,8 @@ def save_statistics_of_path(path, out_path, device=None, batch_size=50, num_work
 def calculate_sfid_given_paths(paths, device=None, batch_size=50, num_workers=8, model=None, spatial_stage=SPATIAL_STAGE,
                                spatial_channels=SPATIAL_CHANNELS):
     """sFID between two image folders or .npz statistics files (keys ``mu_s`` / ``sigma_s``)."""
-    device = fid_score._device(device)
-    for p in paths:
-        if not os.path.exists(p):
-            raise RuntimeError("Invalid path: %s" % p)
+    device = _inputs.rocm_device(device, "sFID")
+    _inputs.require_paths(paths)
     if model is None and not all(str(p).endswith(".npz") for p in paths):
         model = InceptionV3([3]).to(device)
     stats = [compute_spatial_statistics_of_path(p, model, batch_size, device, num_workers, spatial_stage, spatial_channels)
