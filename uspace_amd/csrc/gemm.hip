@@ -93,8 +93,9 @@ __device__ __forceinline__ int lds_off(int r, int c) { return r * ROW_BYTES + ((
 // rows each own one strip besides their BM x BN tile -- one more 16-row MFMA tile shared by the waves -- so a row
 // count like 64*257 = 64*256 + 64 costs four of the 64 tile rows 1/16 more matrix work instead of a nearly empty extra
 // round of workgroups (wave quantisation: 65 x 4 = 260 tiles on 256 CUs is 2 rounds, 64 x 4 is 1).  The strip owners
-// are spread over the XCDs (tile rows 0, 8, 16, ...); the other workgroups skip the strip work (wave-uniform branches
-// at the scheduling barriers of the K loop).  Round 1 gave every workgroup ceil(64/64) = 1 row, i.e. 15/16 of an MFMA
+// are spread over the XCDs (tile rows 0, 8, 16, ...); the other workgroups skip the strip work -- in the two-stage 256 x 256 form they
+// run a body compiled without it (gemm_kernel: role bodies), in the other forms wave-uniform branches at the scheduling barriers of
+// the K loop.  Round 1 gave every workgroup ceil(64/64) = 1 row, i.e. 15/16 of an MFMA
 // tile wasted in each of them: +6 % matrix work everywhere.
 // ------------------------------------------------------------------------------------------
 // counted wait for this wave's LDS-DMA of the next tile AND for its outstanding LDS fragment reads: the raw s_barrier
@@ -104,10 +105,21 @@ __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
 
-template <int BM, int BN, int WM, int WN, int FLAGS, bool XTRA, int NST = 2, bool SK = false>
-// (second launch bound = waves per SIMD: the 4-wave 128x128 form shares a CU with a second workgroup, so its waves must
-// fit 256 registers; one instantiation had grown to 264)
-__global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 64)) ? 2 : 1) void gemm_kernel(const GemmArgs g) {
+// bytes of one LDS stage (activation tile, weight tile, the strip's 16 rows) and of the parked per-row values behind the stages
+constexpr int stage_bytes(int BM, int BN, bool xtra) { return (BM + BN + (xtra ? 16 : 0)) * ROW_BYTES; }
+constexpr int rowv_bytes(int BM, int flags) { return (flags & (USPACE_EPI_LN_IN | USPACE_EPI_CEN_OUT)) ? (BM + 16) * 8 : 0; }
+// strip index of a tile row (it owns a strip when the index is below n_strip): tile rows 0, 8, 16, ... come first so the owners land on different XCDs
+__device__ __forceinline__ int strip_of_tile_row(int tile_m, int tiles_m) {
+    return (tiles_m & 7) == 0 ? (tile_m & 7) * (tiles_m >> 3) + (tile_m >> 3) : tile_m;
+}
+
+// One workgroup's tile, from the first LDS-DMA to the last store.  XTRA: strip code is compiled in; OWNER: this workgroup is known to own
+// a strip (has_x is a constant: no test of it anywhere) -- the two role bodies of a launch with remainder rows are <true, true> and
+// <false, false>, see gemm_kernel.  `smem` is the kernel's one LDS object.
+template <int BM, int BN, int WM, int WN, int FLAGS, bool XTRA, int NST, bool SK, bool OWNER>
+__device__ __forceinline__ void gemm_tile(const GemmArgs& g, char* const smem, const int tile_m, const int tile_n, const int sk_tile,
+                                          const int sk_split) {
+    static_assert(!OWNER || (XTRA && NST == 2 && !SK), "a strip owner's body has the strips and is a two-stage whole-tile form");
     constexpr int THREADS = 64 * WM * WN;
     constexpr int TM = BM / WM / 16;            // 16-row activation sub-tiles per wave
     constexpr int TN = BN / WN / 16;            // 16-col weight sub-tiles per wave
@@ -134,8 +146,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
     // LDS store makes the backend guard every fragment read of the K loop with s_waitcnt vmcnt(0) against the
     // in-flight LDS-DMA (measured: fc1 +28 us), which undoes the load / compute overlap the loop is built on.
     constexpr bool ROWV = (FLAGS & (USPACE_EPI_LN_IN | USPACE_EPI_CEN_OUT)) != 0;
-    constexpr int ROWV_BYTES = ROWV ? (BM + 16) * 8 : 0;
-    __shared__ __attribute__((aligned(16))) char smem[NST * STAGE_BYTES + ROWV_BYTES];
+    static_assert(STAGE_BYTES == stage_bytes(BM, BN, XTRA), "the kernel sizes the LDS object with stage_bytes");
     const uint32_t rowv_lds = (uint32_t)(uintptr_t)(US_LDS char*)(smem + NST * STAGE_BYTES);
 
     const int tid = threadIdx.x;
@@ -144,50 +155,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
     const int wm = wave / WN;
     const int wn = wave % WN;
 
-    // ---- XCD-aware tile id.  Block b runs on XCD b%8 (observed; speed only).  When the grid splits into
-    //      super-tiles of 8 x 4 tiles (one round of an XCD's 32 CUs) each XCD walks whole super-tiles, so
-    //      its 32 resident workgroups share 8 A panels + 4 W panels in its private L2 (12 panel streams
-    //      instead of 18 for a 2 x 16 strip) and keeps its A row-block across rounds.
-    const int nwg = g.tiles_m * g.tiles_n;
-    int tile_m, tile_n;
-    // SK: blocks >= sk_first share tiles -- sk_S of them per tile, each over its own K range.  Block sk_first + u works on tile
-    // sk_first + 8 * ((u >> 3) / S) + (u & 7), K part (u >> 3) % S: the S parts of a tile are 8 block ids apart, i.e. (block b runs on
-    // XCD b % 8 -- observed, speed only) they exchange their partial sums inside one XCD; the last group of 8 tiles may be padding.
-    int sk_tile = -1, sk_split = 0;
-    {
-        int b = blockIdx.x;
-        if constexpr (SK) {
-            if (b >= g.sk_first) {
-                const int u = b - g.sk_first, v = u >> 3;
-                sk_split = v % g.sk_S;
-                sk_tile = (v / g.sk_S) * 8 + (u & 7);
-                b = g.sk_first + sk_tile;
-                if (b >= nwg) return;
-            }
-        }
-        const int xcd = b & 7, idx = b >> 3;
-        const int n_super = nwg >> 5;
-        if ((g.tiles_m & 7) == 0 && (g.tiles_n & 3) == 0 && (n_super & 7) == 0) {
-            const int mb_count = g.tiles_m >> 3;
-            const int sup = xcd + 8 * (idx >> 5);
-            const int t = idx & 31;
-            tile_m = (sup % mb_count) * 8 + (t >> 2);
-            tile_n = (sup / mb_count) * 4 + (t & 3);
-        } else {
-            const int q = nwg >> 3, r = nwg & 7;
-            const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-            tile_m = tile / g.tiles_n;
-            tile_n = tile % g.tiles_n;
-        }
-    }
     const int m0 = tile_m * BM;
     const int n0 = tile_n * BN;
-    const int m_lim = XTRA ? g.m_main : g.M;     // rows >= m_lim belong to the extra strips
-    // strip index of this tile row: tile rows 0, 8, 16, ... come first so the owners land on different XCDs
-    const int sk = (g.tiles_m & 7) == 0 ? (tile_m & 7) * (g.tiles_m >> 3) + (tile_m >> 3) : tile_m;
+    // rows >= m_lim belong to the extra strips (a strip-free body inside a launch with strips: every tile row ends at or below m_main)
+    const int m_lim = XTRA ? g.m_main : g.M;
+    const int sk = strip_of_tile_row(tile_m, g.tiles_m);
     const int x0 = g.m_main + sk * 16;           // first extra row of this workgroup
     const int xr = (XTRA && sk < g.n_strip) ? (g.M - x0 < 16 ? g.M - x0 : 16) : 0;   // its extra rows
-    const bool has_x = xr > 0;                   // workgroup-uniform
+    const bool has_x = OWNER || xr > 0;          // workgroup-uniform; a constant in a role body
 
     // ---- per-lane staging sources: 32-bit BYTE offsets from wave-uniform bases (row clamped into
     //      range; invalid rows are never stored).  Both K slabs share the row stride (checked on host).
@@ -426,7 +401,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
         __syncthreads();
     }
     if constexpr (ROWV) {
-        if (tid < BM + 16) {
+        if (tid < BM + (XTRA ? 16 : 0)) {
             float2 v = make_float2(0.f, 1.f);
             if (rv_m >= 0) {
                 if constexpr ((FLAGS & USPACE_EPI_LN_IN) != 0) {
@@ -665,8 +640,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
         static_assert(NST <= 8, "tail steps are written out up to NST = 8");
         KTILE_R(kt, buf, 0, false, false, 0)
     } else {
-        // steady state is branch-free; the last two K tiles are peeled (no further prefetch / barrier).  Two copies: 15 of 16 workgroups
-        // of a launch with remainder strips own none, and their loop has no strip branches at all
+        // steady state is branch-free; the last two K tiles are peeled (no further prefetch / barrier).  Forms without role bodies
+        // (gemm_kernel) that have strips: two copies -- 15 of 16 workgroups of a launch with remainder strips own none, and their loop has
+        // no strip branches at all
         auto kloop = [&](auto xon) __attribute__((always_inline)) {
             constexpr bool X_ON = decltype(xon)::value;
             int kt = 0;
@@ -674,7 +650,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
             if (kt + 1 < nk) { KTILE(kt, true, false) ++kt; }
             KTILE(kt, false, false)
         };
-        if constexpr (XTRA && (FLAGS & USPACE_EPI_RESIDUAL) == 0) {
+        if constexpr (OWNER) {
+            kloop(std::true_type{});
+        } else if constexpr (XTRA && (FLAGS & USPACE_EPI_RESIDUAL) == 0) {
             if (has_x) kloop(std::true_type{});
             else kloop(std::false_type{});
         } else if constexpr (XTRA) {
@@ -846,21 +824,35 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
     // the K loop had a single tile and therefore no barrier of its own -- the per-row values parked above are visible
     if constexpr (ROWV) __syncthreads();
     // this lane's per-row values: TM main rows (sub-tile i -> row wm*(BM/WM) + i*16 + fr) and the strip row BM + fr
-    float2 rv[ROWV ? TM + 1 : 1];
+    // (a body without strips fetches no strip row)
+    float2 rv[ROWV ? TM + (XTRA ? 1 : 0) : 1];
     if constexpr (ROWV) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
             asm volatile("ds_read_b64 %0, %1" : "=v"(rv[i]) : "v"(rowv_lds + (uint32_t)(wm * (BM / WM) + i * 16 + fr) * 8u) : "memory");
-        asm volatile("ds_read_b64 %0, %1" : "=v"(rv[TM]) : "v"(rowv_lds + (uint32_t)(BM + fr) * 8u) : "memory");
+        if constexpr (XTRA) asm volatile("ds_read_b64 %0, %1" : "=v"(rv[TM]) : "v"(rowv_lds + (uint32_t)(BM + fr) * 8u) : "memory");
         // one wait for all of them; the operands are tied so nothing is consumed (or moved) before it
-        if constexpr (TM == 8)
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rv[0]), "+v"(rv[1]), "+v"(rv[2]), "+v"(rv[3]), "+v"(rv[4]), "+v"(rv[5]), "+v"(rv[6]), "+v"(rv[7]), "+v"(rv[8]));
-        else if constexpr (TM == 6)
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rv[0]), "+v"(rv[1]), "+v"(rv[2]), "+v"(rv[3]), "+v"(rv[4]), "+v"(rv[5]), "+v"(rv[6]));
-        else if constexpr (TM == 4)
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rv[0]), "+v"(rv[1]), "+v"(rv[2]), "+v"(rv[3]), "+v"(rv[4]));
-        else
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rv[0]), "+v"(rv[1]), "+v"(rv[2]));
+#define RV_WAIT(...) asm volatile("s_waitcnt lgkmcnt(0)" : __VA_ARGS__)
+#define RV2 "+v"(rv[0]), "+v"(rv[1])
+#define RV4 RV2, "+v"(rv[2]), "+v"(rv[3])
+#define RV6 RV4, "+v"(rv[4]), "+v"(rv[5])
+#define RV8 RV6, "+v"(rv[6]), "+v"(rv[7])
+        if constexpr (XTRA) {
+            if constexpr (TM == 8) RV_WAIT(RV8, "+v"(rv[TM]));
+            else if constexpr (TM == 6) RV_WAIT(RV6, "+v"(rv[TM]));
+            else if constexpr (TM == 4) RV_WAIT(RV4, "+v"(rv[TM]));
+            else RV_WAIT(RV2, "+v"(rv[TM]));
+        } else {
+            if constexpr (TM == 8) RV_WAIT(RV8);
+            else if constexpr (TM == 6) RV_WAIT(RV6);
+            else if constexpr (TM == 4) RV_WAIT(RV4);
+            else RV_WAIT(RV2);
+        }
+#undef RV_WAIT
+#undef RV2
+#undef RV4
+#undef RV6
+#undef RV8
         static_assert(!ROWV || TM == 8 || TM == 6 || TM == 4 || TM == 2, "row-value fetch is written for TM = 8 / 6 / 4 / 2");
     }
     auto row_begin = [&](int ri) {            // ri: index into rv (sub-tile i, or TM for the strip row)
@@ -946,7 +938,58 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
             row_end(m, vrow, wm * (BM / WM) + i * 16 + fr, wn);
         }
     }
-    if constexpr (XTRA) {
+    if constexpr (OWNER && !CEN) {
+        // The owner's strip: the XN vectors of the strip row go through the activation together and, where the interior path's
+        // conditions hold for the columns, leave as 16-byte widened bf16 stores like the main rows; per-value arithmetic as `emit` below.
+        // (Not for LayerNorm producers: their strip partial sums came out with other bits from this form -- the compiler contracts the sums of
+        // squares differently -- so their strip rows go through `emit`, one vector at a time, as before.)
+        static_assert(!OWNER || XN % 2 == 0, "the strip's sub-tiles are widened in pairs");
+        const int m = x0 + fr;
+        const bool vrow = fr < xr;               // (xr = min(16, M - x0): the row exists)
+        row_begin(TM);
+        f32x4 v[XN];
+#pragma unroll
+        for (int j = 0; j < XN; ++j) {
+            f32x4 csx = cs4[0];
+            if constexpr (CSV) csx = pick_b<WM, XN>(cs4, wm, j);
+            v[j] = emit_pre(xacc[j], pick_b<WM, XN>(bias4, wm, j), csx);
+        }
+        if constexpr (FLAGS & USPACE_EPI_GELU) gelu_erf_batch<XN>(v);
+        const int nx = n0 + wn * (BN / WN) + wm * XN * 16;    // first column of this wave's strip sub-tiles
+        if (n0 + BN <= g.N && g.wide) {                       // workgroup-uniform
+            uint2 pk[XN];
+#pragma unroll
+            for (int j = 0; j < XN; ++j) {
+                if constexpr (FLAGS & USPACE_EPI_OUT_BF16) {
+                    pk[j].x = pack_bf2(v[j][0], v[j][1]);
+                    pk[j].y = pack_bf2(v[j][2], v[j][3]);
+                }
+            }
+            // (the lane exchange of widen_pair runs with every lane active; only the stores are predicated on the row)
+            uint4 wk[XN / 2];
+#pragma unroll
+            for (int j = 0; j < XN; j += 2) {
+                if constexpr (FLAGS & USPACE_EPI_OUT_BF16) wk[j / 2] = widen_pair(pk[j], pk[j + 1]);
+            }
+            if (vrow) {
+                const int nw = nx + (fq & 1) * 16 + (fq >> 1) * 8;
+#pragma unroll
+                for (int j = 0; j < XN; ++j)
+                    if constexpr ((FLAGS & USPACE_EPI_OUT_F32) != 0) *(f32x4*)(out_f32 + (size_t)m * g.ld_f32 + nx + j * 16 + fq * 4) = v[j];
+#pragma unroll
+                for (int j = 0; j < XN; j += 2) {
+                    if constexpr (FLAGS & USPACE_EPI_OUT_BF16) *(uint4*)(g.out_bf16 + (size_t)m * g.ld_bf16 + nw + j * 16) = wk[j / 2];
+                }
+            }
+        } else if (vrow) {
+#pragma unroll
+            for (int j = 0; j < XN; ++j) {
+                const int n = nx + j * 16 + fq * 4;
+                if (n < g.N) emit_post(v[j], m, n);
+            }
+        }
+        row_end(m, vrow, BM + fr, wm == 0 ? wn : -(wm * WN + wn) - 1);
+    } else if constexpr (XTRA) {
         const int m = x0 + fr;
         const bool vrow = fr < xr && m < g.M && own_x;
         row_begin(TM);
@@ -988,6 +1031,64 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 6
             po[0] = a;
             po[1] = bq;
         }
+    }
+}
+
+// Role bodies.  In a launch with remainder strips 1 workgroup in 16 or fewer owns one.  The two-stage whole-tile 256 x 256 form -- the
+// headline launches -- compiles the tile twice and picks a body with one workgroup-uniform branch: strips on, no test of ownership
+// anywhere (the owner), and no strip code at all (everyone else: prologue, K loop, epilogue and row-value fetch of a launch without
+// remainder rows).  The bodies share nothing but the LDS object and the tile id, so neither is scheduled under the other's register
+// needs.  Every flag set fits (no scratch, <= 256 VGPRs).  Measured (profiles/strip_roles.md): no single launch leaves its A/A spread
+// in an interleaved A/B of repeated launches, the U-ViT-L forward at 64 x 257 rows is 2.2 % shorter.  The K-split tail (SK) and the
+// other tile forms keep one body with the run-time test.
+constexpr bool role_bodies(int BM, int BN, bool xtra, int nst, bool sk) { return xtra && BM == 256 && BN == 256 && nst == 2 && !sk; }
+
+template <int BM, int BN, int WM, int WN, int FLAGS, bool XTRA, int NST = 2, bool SK = false>
+// (second launch bound = waves per SIMD: the 4-wave 128x128 form shares a CU with a second workgroup, so its waves must
+// fit 256 registers; one instantiation had grown to 264)
+__global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && (NST == 2 || BM == 64)) ? 2 : 1) void gemm_kernel(const GemmArgs g) {
+    __shared__ __attribute__((aligned(16))) char smem[NST * stage_bytes(BM, BN, XTRA) + rowv_bytes(BM, FLAGS)];
+    // ---- XCD-aware tile id.  Block b runs on XCD b%8 (observed; speed only).  When the grid splits into
+    //      super-tiles of 8 x 4 tiles (one round of an XCD's 32 CUs) each XCD walks whole super-tiles, so
+    //      its 32 resident workgroups share 8 A panels + 4 W panels in its private L2 (12 panel streams
+    //      instead of 18 for a 2 x 16 strip) and keeps its A row-block across rounds.
+    const int nwg = g.tiles_m * g.tiles_n;
+    int tile_m, tile_n;
+    // SK: blocks >= sk_first share tiles -- sk_S of them per tile, each over its own K range.  Block sk_first + u works on tile
+    // sk_first + 8 * ((u >> 3) / S) + (u & 7), K part (u >> 3) % S: the S parts of a tile are 8 block ids apart, i.e. (block b runs on
+    // XCD b % 8 -- observed, speed only) they exchange their partial sums inside one XCD; the last group of 8 tiles may be padding.
+    int sk_tile = -1, sk_split = 0;
+    {
+        int b = blockIdx.x;
+        if constexpr (SK) {
+            if (b >= g.sk_first) {
+                const int u = b - g.sk_first, v = u >> 3;
+                sk_split = v % g.sk_S;
+                sk_tile = (v / g.sk_S) * 8 + (u & 7);
+                b = g.sk_first + sk_tile;
+                if (b >= nwg) return;
+            }
+        }
+        const int xcd = b & 7, idx = b >> 3;
+        const int n_super = nwg >> 5;
+        if ((g.tiles_m & 7) == 0 && (g.tiles_n & 3) == 0 && (n_super & 7) == 0) {
+            const int mb_count = g.tiles_m >> 3;
+            const int sup = xcd + 8 * (idx >> 5);
+            const int t = idx & 31;
+            tile_m = (sup % mb_count) * 8 + (t >> 2);
+            tile_n = (sup / mb_count) * 4 + (t & 3);
+        } else {
+            const int q = nwg >> 3, r = nwg & 7;
+            const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+            tile_m = tile / g.tiles_n;
+            tile_n = tile % g.tiles_n;
+        }
+    }
+    if constexpr (role_bodies(BM, BN, XTRA, NST, SK)) {
+        if (strip_of_tile_row(tile_m, g.tiles_m) < g.n_strip) gemm_tile<BM, BN, WM, WN, FLAGS, true, NST, SK, true>(g, smem, tile_m, tile_n, sk_tile, sk_split);
+        else gemm_tile<BM, BN, WM, WN, FLAGS, false, NST, SK, false>(g, smem, tile_m, tile_n, sk_tile, sk_split);
+    } else {
+        gemm_tile<BM, BN, WM, WN, FLAGS, XTRA, NST, SK, false>(g, smem, tile_m, tile_n, sk_tile, sk_split);
     }
 }
 
