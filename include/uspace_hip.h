@@ -316,7 +316,7 @@ typedef struct uspace_uvit_config {
     int img_size;      /* 32 */
     int patch_size;    /* 2 */
     int in_chans;      /* 4 */
-    int embed_dim;     /* D: multiple of 64 */
+    int embed_dim;     /* D: multiple of 64, at most 2048 (the output head keeps its D x 16 weight image in LDS) */
     int depth;         /* even; depth/2 in-blocks, 1 mid, depth/2 out-blocks */
     int num_heads;     /* embed_dim / 64 */
     int mlp_hidden;    /* 4*D */

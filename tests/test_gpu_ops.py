@@ -480,12 +480,18 @@ def test_groupnorm_on_zero_bordered_map(hip, B, C_, H, silu):
     assert float(border.abs().max()) == 0.0                       # zero border = the next conv's padding
 
 
-@pytest.mark.parametrize("B,D,n_extra,time_first", [(3, 128, 0, 1), (2, 512, 1, 0), (2, 1024, 77, 1), (2, 64, 0, 1)])
-def test_embed_tokens_matches_oracle(hip, B, D, n_extra, time_first):
+# (B, D, n_extra, time_first, S, p, C): the first four keep their ids; then the 16-token form of the register-weight kernel
+# (B * 16 >= 512 blocks) and the per-token kernel -- 9 patches (16-byte weight loads), 12 pixels, 3 pixels (scalar weight loop)
+EMBED_CASES = [pytest.param(*c, 32, 2, 4, id="-".join(str(v) for v in c)) for c in [(3, 128, 0, 1), (2, 512, 1, 0), (2, 1024, 77, 1), (2, 64, 0, 1)]]
+EMBED_CASES += [(33, 64, 2, 0, 32, 2, 4), (3, 136, 2, 1, 6, 2, 4), (3, 136, 0, 0, 6, 2, 4), (2, 64, 2, 0, 8, 2, 3), (2, 1028, 2, 1, 4, 1, 3)]
+
+
+@pytest.mark.parametrize("B,D,n_extra,time_first,S,p,Cc", EMBED_CASES)
+def test_embed_tokens_matches_oracle(hip, B, D, n_extra, time_first, S, p, Cc):
     """PatchEmbed + timestep_embedding + [label | context] tokens + pos_embed (libs/uvit.py:26-46,171-179,315-327;
-    libs/uvit_t2i.py:320-324), fp32 rows and their bf16 copy; D % 1024 != 0 and the register-weight patch kernel."""
+    libs/uvit_t2i.py:320-324), fp32 rows and their bf16 copy; D % 1024 != 0, both forms of the register-weight patch kernel
+    (C p p == 16) and the per-token kernel every other patch takes."""
     rng = np.random.default_rng(D + n_extra)
-    S, p, Cc = 32, 2, 4
     g = S // p
     L = 1 + n_extra + g * g
     img = _rand(rng, B, Cc, S, S)
@@ -509,13 +515,19 @@ def test_embed_tokens_matches_oracle(hip, B, D, n_extra, time_first):
     assert torch.equal(tokb, tok.to(torch.bfloat16))
 
 
-@pytest.mark.parametrize("B,D,extras", [(3, 128, 1), (2, 512, 78), (5, 1024, 1), (2, 64, 2), (1, 1536, 1)])
-def test_output_head_matches_oracle(hip, B, D, extras):
-    """norm + decoder_pred + token slice + unpatchify + final 3x3 conv (libs/uvit.py:56-63,342-347): the LDS-weight
-    kernel (D % 128 == 0, D <= 1024) and the per-token kernel."""
+# (B, D, extras, S, p, C): the first five keep their ids (all D % 32 == 0: the matrix-core kernel); then the per-token kernel at 1, 2
+# and 8 float4 per lane (D % 32 != 0; 27 tokens: a partial last block) and 3 channels (PD = 12: zero weight rows, the general conv)
+HEAD_CASES = [pytest.param(*c, 32, 2, 4, id="-".join(str(v) for v in c)) for c in [(3, 128, 1), (2, 512, 78), (5, 1024, 1), (2, 64, 2), (1, 1536, 1)]]
+HEAD_CASES += [(3, 72, 1, 6, 2, 4), (3, 264, 2, 6, 2, 4), (3, 1028, 1, 6, 2, 4), (2, 128, 2, 8, 2, 3), (3, 72, 1, 6, 2, 3)]
+
+
+@pytest.mark.parametrize("B,D,extras,S,p,Cc", HEAD_CASES)
+def test_output_head_matches_oracle(hip, B, D, extras, S, p, Cc):
+    """norm + decoder_pred + token slice + unpatchify + final 3x3 conv (libs/uvit.py:56-63,342-347): the matrix-core kernel with the
+    weight image in LDS (D % 32 == 0, D <= 2048), the per-token kernel (every other D % 4 == 0) and both 3x3 conv kernels (C == 4 and
+    the general one)."""
     import ctypes
     rng = np.random.default_rng(D + extras)
-    S, p, Cc = 32, 2, 4
     g = S // p
     L = extras + g * g
     x = (_rand(rng, B, L, D, scale=1.5) + 0.3).astype(np.float32)

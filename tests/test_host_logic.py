@@ -84,6 +84,22 @@ def test_config_queries_without_gpu():
     assert L.uspace_uvit_weight_bytes(ctypes.byref(bad)) == 0
 
 
+def test_config_rejects_widths_the_output_head_cannot_run():
+    """The head keeps its weight image in LDS up to embed_dim 2048: a wider model is refused by the size queries, before anything is
+    packed or enqueued, and by the module."""
+    from uspace_amd import _hip
+    from uspace_amd.tools.utils_uvit import get_nnet
+    L = _hip.lib()
+    for D, ok in ((2048, True), (2112, False)):
+        cfg = _hip.UvitConfig(32, 2, 4, D, 2, D // 64, 4 * D, 0, 0, 0)
+        assert (L.uspace_uvit_num_params(ctypes.byref(cfg)) > 0) == ok
+        assert (L.uspace_uvit_workspace_bytes(ctypes.byref(cfg), 4) > 0) == ok
+        assert (L.uspace_uvit_weight_bytes(ctypes.byref(cfg)) > 0) == ok
+    with pytest.raises(NotImplementedError):
+        get_nnet("uvit", img_size=32, patch_size=2, in_chans=4, embed_dim=2112, depth=2, num_heads=33, mlp_ratio=4, qkv_bias=False,
+                 mlp_time_embed=False, num_classes=-1)
+
+
 def test_product_never_imports_oracle():
     for dirpath, _dirs, files in os.walk(os.path.join(ROOT, "uspace_amd")):
         for f in files:

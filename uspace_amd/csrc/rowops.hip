@@ -1,6 +1,8 @@
 // HBM-bound row / elementwise kernels of the U-ViT forward for gfx950:
 // LayerNorm, token assembly, output head, u-space add, casts and the ODE state arithmetic.
 // All are one-pass over their input with 16-byte accesses per lane (coalesced along rows).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -175,6 +177,20 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(bf16_t* __restrict__ x,
 // ------------------------------------------------------------------------------------------
 // Token assembly. grid = B*L blocks; each block writes one token row of D floats.
 // ------------------------------------------------------------------------------------------
+// Columns d .. d + 3 of token row `row` (of B * L), position l: + pos_embed, the fp32 store, the bf16 copy if asked for.  D % 4 == 0:
+// 16-byte stores.
+__device__ __forceinline__ void put_token4(f32x4 v, const float* pos, int l, float* tok,
+                                           bf16_t* tok_bf16, size_t row, int D, int d) {
+    v += *(const f32x4*)(pos + (size_t)l * D + d);
+    *(f32x4*)(tok + row * D + d) = v;
+    if (tok_bf16) {
+        uint2 q;
+        q.x = pack_bf2(v[0], v[1]);
+        q.y = pack_bf2(v[2], v[3]);
+        *(uint2*)(tok_bf16 + row * D + d) = q;
+    }
+}
+
 // Time / label / context token l of sample b (the tokens in front of the patch tokens): one block per row.  extra_bstride: floats
 // from one sample's extra tokens to the next one's (n_extra * D; 0: every sample reads the same tokens).
 __device__ __forceinline__ void embed_special_row(const float* __restrict__ t, int t_stride, const float* __restrict__ extra, int n_extra,
@@ -220,29 +236,12 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ im
                                                     const float* __restrict__ extra, int n_extra, long extra_bstride, int time_first,
                                                     const float* __restrict__ pw, const float* __restrict__ pb,
                                                     const float* __restrict__ pos, float* __restrict__ tok,
-                                                    bf16_t* __restrict__ tok_bf16, int C, int S, int p, int D,
-                                                    int only_special) {
+                                                    bf16_t* __restrict__ tok_bf16, int C, int S, int p, int D) {
     const int g = S / p;
     const int L = 1 + n_extra + g * g;
-    const int per = only_special ? 1 + n_extra : L;     // tokens of a sample this launch covers (the leading ones)
-    const int b = blockIdx.x / per;
-    const int l = blockIdx.x % per;
-    const int time_pos = time_first ? 0 : n_extra;
-    const int extra_pos = time_first ? 1 : 0;
-    float* out = tok + ((size_t)b * L + l) * D;
-    bf16_t* outb = tok_bf16 ? tok_bf16 + ((size_t)b * L + l) * D : nullptr;
-    const float* posr = pos + (size_t)l * D;
-    auto put4 = [&](int d, f32x4 v) {   // D % 4 == 0: 16-byte stores
-        v += *(const f32x4*)(posr + d);
-        *(f32x4*)(out + d) = v;
-        if (outb) {
-            uint2 q;
-            q.x = pack_bf2(v[0], v[1]);
-            q.y = pack_bf2(v[2], v[3]);
-            *(uint2*)(outb + d) = q;
-        }
-    };
-    if (l == time_pos || (l >= extra_pos && l < extra_pos + n_extra)) {
+    const int b = blockIdx.x / L;
+    const int l = blockIdx.x % L;
+    if (l < 1 + n_extra) {
         embed_special_row(t, t_stride, extra, n_extra, extra_bstride, time_first, pos, tok, tok_bf16, b, l, L, D);
     } else {
         // PatchEmbed conv k = s = p (libs/uvit.py:171-178): pixels consumed in (c, i, j) order
@@ -279,7 +278,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ im
                     v[e] = s;
                 }
             }
-            put4(d, v);
+            put_token4(v, pos, l, tok, tok_bf16, blockIdx.x, D, d);
         }
     }
 }
@@ -656,34 +655,33 @@ inline void launch_conv3x3(const float* in, const float* w, const float* bias, f
 }
 
 // x[b, i] += scale_b * delta[i] (scale_b = scale * row_scale[b] when row_scale != NULL); optional bf16 copy
-// refresh. per_sample % 4 == 0.
+// refresh.  W floats per thread and step: 4 (per_sample % 4 == 0, 16-byte accesses) or 1; per_sample and total count W-float groups.
+template <int W>
+using vec_of = typename std::conditional<W == 4, f32x4, float>::type;
+
+template <int W>
 __global__ __launch_bounds__(256) void add_bcast_kernel(float* __restrict__ x, bf16_t* __restrict__ xb,
                                                         const float* __restrict__ delta, float scale,
                                                         const float* __restrict__ row_scale,
-                                                        long per_sample4, long total4) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
-        const long j = i % per_sample4;
-        f32x4 v = ((f32x4*)x)[i];
-        const f32x4 d = ((const f32x4*)delta)[j];
-        const float sc = row_scale ? scale * row_scale[i / per_sample4] : scale;
-        v += d * sc;
-        ((f32x4*)x)[i] = v;
-        if (xb) {
-            uint2 p;
-            p.x = pack_bf2(v[0], v[1]);
-            p.y = pack_bf2(v[2], v[3]);
-            ((uint2*)xb)[i] = p;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void add_bcast_tail_kernel(float* x, bf16_t* xb, const float* delta, float scale,
-                                                             const float* row_scale, long per_sample, long total) {
+                                                        long per_sample, long total) {
+    using vec = vec_of<W>;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long j = i % per_sample;
+        vec v = ((vec*)x)[i];
+        const vec d = ((const vec*)delta)[j];
         const float sc = row_scale ? scale * row_scale[i / per_sample] : scale;
-        const float v = x[i] + sc * delta[i % per_sample];
-        x[i] = v;
-        if (xb) xb[i] = f2bf(v);
+        v += d * sc;
+        ((vec*)x)[i] = v;
+        if (xb) {
+            if constexpr (W == 4) {
+                uint2 p;
+                p.x = pack_bf2(v[0], v[1]);
+                p.y = pack_bf2(v[2], v[3]);
+                ((uint2*)xb)[i] = p;
+            } else {
+                xb[i] = f2bf(v);
+            }
+        }
     }
 }
 
@@ -716,25 +714,23 @@ __global__ __launch_bounds__(256) void cast_bcast_kernel(const float* __restrict
 // turn a -0 into +0).
 __device__ __forceinline__ float cfg_guided(float c, float u, float sb) { return sb == 0.f ? c : __builtin_fmaf(sb, c - u, c); }
 
+template <int W>   // as add_bcast_kernel: 4 floats per thread and step (aligned, per_sample % 4 == 0) or 1
 __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ pair, const float* __restrict__ row_scale, float scale,
-                                                          float* __restrict__ out, long per_sample4, long total4) {
-    const f32x4* __restrict__ cond = (const f32x4*)pair;
-    const f32x4* __restrict__ unc = cond + total4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
-        const float sb = row_scale ? scale * row_scale[i / per_sample4] : scale;
-        const f32x4 c = cond[i], u = unc[i];
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = cfg_guided(c[e], u[e], sb);
-        ((f32x4*)out)[i] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void cfg_combine_tail_kernel(const float* __restrict__ pair, const float* __restrict__ row_scale,
-                                                               float scale, float* __restrict__ out, long per_sample, long total) {
+                                                          float* __restrict__ out, long per_sample, long total) {
+    using vec = vec_of<W>;
+    const vec* __restrict__ cond = (const vec*)pair;
+    const vec* __restrict__ unc = cond + total;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const float sb = row_scale ? scale * row_scale[i / per_sample] : scale;
-        out[i] = cfg_guided(pair[i], pair[total + i], sb);
+        const vec c = cond[i], u = unc[i];
+        vec v;
+        if constexpr (W == 4) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = cfg_guided(c[e], u[e], sb);
+        } else {
+            v = cfg_guided(c, u, sb);
+        }
+        ((vec*)out)[i] = v;
     }
 }
 
@@ -777,6 +773,15 @@ struct KPtrs {
     float c[8];
     int n;
 };
+inline KPtrs make_kptrs(const float* const* k, const float* coef, int n_k) {   // the unused entries: NULL and 0
+    KPtrs kp;
+    kp.n = n_k;
+    for (int i = 0; i < 8; ++i) {
+        kp.k[i] = i < n_k ? k[i] : nullptr;
+        kp.c[i] = i < n_k ? coef[i] : 0.f;
+    }
+    return kp;
+}
 
 __global__ __launch_bounds__(256) void ode_combine_kernel(float* __restrict__ out, const float* __restrict__ y, KPtrs kp, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -833,37 +838,39 @@ inline int grid_for(long n_items, int cap = 2048) {
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+// The one-wave-per-row kernels keep a row as NV float4 per lane: f(std::integral_constant<int, NV>) with the smallest NV of 1, 2, 4, 8,
+// 16 that holds D <= NV * 256 columns (D <= MAX_NV * 256 is the caller's check).
+template <int MAX_NV = 16, class F>
+inline void with_row_nv(int D, F&& f) {
+    if (D <= 256) f(std::integral_constant<int, 1>{});
+    else if (D <= 512) f(std::integral_constant<int, 2>{});
+    else if (D <= 1024) f(std::integral_constant<int, 4>{});
+    else if (D <= 2048 || MAX_NV == 8) f(std::integral_constant<int, 8>{});
+    else if constexpr (MAX_NV == 16) f(std::integral_constant<int, 16>{});
+}
+
+template <bool F32OUT>
+int launch_layernorm(const float* x, const float* gamma, const float* beta, void* y, int M, int D, float eps, hipStream_t s) {
+    if (!x || !gamma || !beta || !y || M <= 0 || D <= 0 || (D & 3) || D > 4096) return USPACE_ERR_ARG;
+    with_row_nv(D, [&](auto nv) {
+        hipLaunchKernelGGL((layernorm_kernel<decltype(nv)::value, F32OUT>), dim3(us_cdiv(M, 4)), dim3(256), 0, s, x, gamma, beta, (bf16_t*)y, M, D, eps);
+    });
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
 }  // namespace
 
 extern "C" int uspace_abi_version(void) { return USPACE_ABI_VERSION; }
 
 extern "C" int uspace_layernorm_f32_bf16(const float* x, const float* gamma, const float* beta, uint16_t* y,
                                          int M, int D, float eps, uspace_stream_t stream) {
-    if (!x || !gamma || !beta || !y || M <= 0 || D <= 0 || (D & 3) || D > 4096) return USPACE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = us_cdiv(M, 4);
-    if (D <= 256) hipLaunchKernelGGL(layernorm_kernel<1>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, M, D, eps);
-    else if (D <= 512) hipLaunchKernelGGL(layernorm_kernel<2>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, M, D, eps);
-    else if (D <= 1024) hipLaunchKernelGGL(layernorm_kernel<4>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, M, D, eps);
-    else if (D <= 2048) hipLaunchKernelGGL(layernorm_kernel<8>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, M, D, eps);
-    else hipLaunchKernelGGL(layernorm_kernel<16>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, M, D, eps);
-    US_CHECK_LAUNCH();
-    return USPACE_OK;
+    return launch_layernorm<false>(x, gamma, beta, y, M, D, eps, (hipStream_t)stream);
 }
 
 extern "C" int uspace_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int M, int D,
                                     float eps, uspace_stream_t stream) {
-    if (!x || !gamma || !beta || !y || M <= 0 || D <= 0 || (D & 3) || D > 4096) return USPACE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = us_cdiv(M, 4);
-    bf16_t* yy = (bf16_t*)y;
-    if (D <= 256) hipLaunchKernelGGL((layernorm_kernel<1, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, yy, M, D, eps);
-    else if (D <= 512) hipLaunchKernelGGL((layernorm_kernel<2, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, yy, M, D, eps);
-    else if (D <= 1024) hipLaunchKernelGGL((layernorm_kernel<4, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, yy, M, D, eps);
-    else if (D <= 2048) hipLaunchKernelGGL((layernorm_kernel<8, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, yy, M, D, eps);
-    else hipLaunchKernelGGL((layernorm_kernel<16, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, yy, M, D, eps);
-    US_CHECK_LAUNCH();
-    return USPACE_OK;
+    return launch_layernorm<true>(x, gamma, beta, y, M, D, eps, (hipStream_t)stream);
 }
 
 extern "C" int uspace_fold_layernorm(const float* W, const float* gamma, const float* beta, const float* bias, uint16_t* Wf,
@@ -883,13 +890,9 @@ int us_rowsum_bf16(const float* W, int ld, int col0, int ncols, float* out, int 
 
 extern "C" int uspace_center_rows(const float* x, uint16_t* xc, float* c, float* part, int M, int D, uspace_stream_t stream) {
     if (!x || !xc || !c || !part || M <= 0 || D <= 0 || (D & 3) || D > 4096) return USPACE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = us_cdiv(M, 4);
-    if (D <= 256) hipLaunchKernelGGL(center_stats_kernel<1>, dim3(grid), dim3(256), 0, s, x, xc, c, part, M, D);
-    else if (D <= 512) hipLaunchKernelGGL(center_stats_kernel<2>, dim3(grid), dim3(256), 0, s, x, xc, c, part, M, D);
-    else if (D <= 1024) hipLaunchKernelGGL(center_stats_kernel<4>, dim3(grid), dim3(256), 0, s, x, xc, c, part, M, D);
-    else if (D <= 2048) hipLaunchKernelGGL(center_stats_kernel<8>, dim3(grid), dim3(256), 0, s, x, xc, c, part, M, D);
-    else hipLaunchKernelGGL(center_stats_kernel<16>, dim3(grid), dim3(256), 0, s, x, xc, c, part, M, D);
+    with_row_nv(D, [&](auto nv) {
+        hipLaunchKernelGGL(center_stats_kernel<decltype(nv)::value>, dim3(us_cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x, xc, c, part, M, D);
+    });
     US_CHECK_LAUNCH();
     return USPACE_OK;
 }
@@ -936,7 +939,7 @@ int us_embed_tokens_rows(const float* img, const float* t, int t_stride, const f
                                tok, tok_bf16, C, S, p, D, L, 1 + n_extra, t, t_stride, extra, extra_bstride, time_first, B);
     } else {
         hipLaunchKernelGGL(embed_kernel, dim3(B * L), dim3(256), 0, s, img, t, t_stride, extra, n_extra, extra_bstride,
-                           time_first, patch_w, patch_b, pos, tok, tok_bf16, C, S, p, D, 0);
+                           time_first, patch_w, patch_b, pos, tok, tok_bf16, C, S, p, D);
     }
     US_CHECK_LAUNCH();
     return USPACE_OK;
@@ -950,31 +953,43 @@ extern "C" int uspace_embed_tokens(const float* img, const float* t, int t_strid
                                 B, B, C, S, p, D, (hipStream_t)stream);
 }
 
-extern "C" int uspace_output_head(const float* tok, int L, int extras, const float* norm_g, const float* norm_b,
-                                  const float* dec_w, const float* dec_b, const float* conv_w, const float* conv_b,
-                                  float* scratch, float* out, int B, int C, int S, int p, int D, float eps,
-                                  uspace_stream_t stream) {
-    if (!tok || !norm_g || !norm_b || !dec_w || !dec_b || !conv_w || !conv_b || !scratch || !out) return USPACE_ERR_ARG;
-    if (B <= 0 || (D & 3) || D > 2048 || S % p || p * p * C > 16) return USPACE_ERR_ARG;
-    const int g = S / p;
-    if (extras + g * g != L) return USPACE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 hgrid(us_cdiv(B * g * g, 4)), hblock(256);
-    if ((D & 31) == 0 && D <= 2048) {
-        const size_t lds = (size_t)64 * D + (64 + 16) * 4;
-        static std::atomic<uint64_t> lds_ok{0};
-        US_TRY(us_opt_in_lds((const void*)head_pred_mfma_kernel<8, false>, 140 * 1024, lds_ok));
-        hipLaunchKernelGGL((head_pred_mfma_kernel<8, false>), dim3(us_cdiv(B * g * g, 64)), dim3(256), lds, s, tok, L, extras, norm_g,
-                           norm_b, dec_w, dec_b, scratch, B, C, S, p, D, eps);
-    } else if (D <= 256) hipLaunchKernelGGL(head_pred_kernel<1>, hgrid, hblock, 0, s, tok, L, extras, norm_g, norm_b, dec_w, dec_b, scratch, B, C, S, p, D, eps);
-    else if (D <= 512) hipLaunchKernelGGL(head_pred_kernel<2>, hgrid, hblock, 0, s, tok, L, extras, norm_g, norm_b, dec_w, dec_b, scratch, B, C, S, p, D, eps);
-    else if (D <= 1024) hipLaunchKernelGGL(head_pred_kernel<4>, hgrid, hblock, 0, s, tok, L, extras, norm_g, norm_b, dec_w, dec_b, scratch, B, C, S, p, D, eps);
-    else if (D <= 2048) hipLaunchKernelGGL(head_pred_kernel<8>, hgrid, hblock, 0, s, tok, L, extras, norm_g, norm_b, dec_w, dec_b, scratch, B, C, S, p, D, eps);
-    else return USPACE_ERR_ARG;
+namespace {
+// What uspace_output_head and us_output_head_packed share: the checks (d_mask: 3, or 31 for the matrix-core kernel), the LDS bytes of
+// the weight image with its reduction scratch, and stage 2 behind the launch of stage 1.
+inline bool head_args_ok(const float* tok, const float* conv_w, const float* conv_b, const float* scratch, const float* out, int L, int extras,
+                         int B, int C, int S, int p, int D, int d_mask) {
+    if (!tok || !conv_w || !conv_b || !scratch || !out) return false;
+    if (B <= 0 || (D & d_mask) || D > 2048 || S % p || p * p * C > 16) return false;
+    return extras + (S / p) * (S / p) == L;
+}
+inline size_t head_lds_bytes(int D) { return (size_t)64 * D + (64 + 16) * 4; }
+inline int head_conv(const float* scratch, const float* conv_w, const float* conv_b, float* out, int B, int C, int S, hipStream_t s) {
     US_CHECK_LAUNCH();
     launch_conv3x3(scratch, conv_w, conv_b, out, B, C, S, s);
     US_CHECK_LAUNCH();
     return USPACE_OK;
+}
+}  // namespace
+
+extern "C" int uspace_output_head(const float* tok, int L, int extras, const float* norm_g, const float* norm_b,
+                                  const float* dec_w, const float* dec_b, const float* conv_w, const float* conv_b,
+                                  float* scratch, float* out, int B, int C, int S, int p, int D, float eps,
+                                  uspace_stream_t stream) {
+    if (!norm_g || !norm_b || !dec_w || !dec_b || !head_args_ok(tok, conv_w, conv_b, scratch, out, L, extras, B, C, S, p, D, 3)) return USPACE_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int ntok = B * (S / p) * (S / p);
+    if ((D & 31) == 0) {
+        static std::atomic<uint64_t> lds_ok{0};
+        US_TRY(us_opt_in_lds((const void*)head_pred_mfma_kernel<8, false>, 140 * 1024, lds_ok));
+        hipLaunchKernelGGL((head_pred_mfma_kernel<8, false>), dim3(us_cdiv(ntok, 64)), dim3(256), head_lds_bytes(D), s, tok, L, extras, norm_g,
+                           norm_b, dec_w, dec_b, scratch, B, C, S, p, D, eps);
+    } else {
+        with_row_nv<8>(D, [&](auto nv) {
+            hipLaunchKernelGGL(head_pred_kernel<decltype(nv)::value>, dim3(us_cdiv(ntok, 4)), dim3(256), 0, s, tok, L, extras, norm_g, norm_b, dec_w,
+                               dec_b, scratch, B, C, S, p, D, eps);
+        });
+    }
+    return head_conv(scratch, conv_w, conv_b, out, B, C, S, s);
 }
 
 // Pack-time half of the output head's fast path (uvit.hip keeps the image in the weight blob): see head_weight_image.
@@ -991,26 +1006,20 @@ int us_head_pack(const float* norm_g, const float* norm_b, const float* dec_w, c
 // uspace_output_head with the weight image of us_head_pack instead of norm / decoder_pred parameters
 int us_output_head_packed(const float* tok, int L, int extras, const float* image, const float* conv_w, const float* conv_b,
                           float* scratch, float* out, int B, int C, int S, int p, int D, float eps, hipStream_t s) {
-    if (!tok || !image || !conv_w || !conv_b || !scratch || !out) return USPACE_ERR_ARG;
-    if (B <= 0 || (D & 31) || D > 2048 || S % p || p * p * C > 16) return USPACE_ERR_ARG;
-    const int g = S / p;
-    if (extras + g * g != L) return USPACE_ERR_ARG;
-    const size_t lds = (size_t)64 * D + (64 + 16) * 4;
+    if (!image || !head_args_ok(tok, conv_w, conv_b, scratch, out, L, extras, B, C, S, p, D, 31)) return USPACE_ERR_ARG;
+    const int ntok = B * (S / p) * (S / p);
     static std::atomic<uint64_t> lds_ok{0};
-    if (B * g * g <= 4096 && (D & 127) == 0) {      // up to 256 blocks of 16 tokens: k range cut over the waves
+    if (ntok <= 4096 && (D & 127) == 0) {      // up to 256 blocks of 16 tokens: k range cut over the waves
         static std::atomic<uint64_t> lds_ok_k{0};
         US_TRY(us_opt_in_lds((const void*)head_pred_mfma_kernel<8, true, true>, 140 * 1024, lds_ok_k));
-        hipLaunchKernelGGL((head_pred_mfma_kernel<8, true, true>), dim3(us_cdiv(B * g * g, 16)), dim3(256), lds, s, tok, L, extras, nullptr,
-                           nullptr, image, nullptr, scratch, B, C, S, p, D, eps);
+        hipLaunchKernelGGL((head_pred_mfma_kernel<8, true, true>), dim3(us_cdiv(ntok, 16)), dim3(256), head_lds_bytes(D), s, tok, L, extras,
+                           nullptr, nullptr, image, nullptr, scratch, B, C, S, p, D, eps);
     } else {
         US_TRY(us_opt_in_lds((const void*)head_pred_mfma_kernel<8, true>, 140 * 1024, lds_ok));
-        hipLaunchKernelGGL((head_pred_mfma_kernel<8, true>), dim3(us_cdiv(B * g * g, 64)), dim3(256), lds, s, tok, L, extras, nullptr,
+        hipLaunchKernelGGL((head_pred_mfma_kernel<8, true>), dim3(us_cdiv(ntok, 64)), dim3(256), head_lds_bytes(D), s, tok, L, extras, nullptr,
                            nullptr, image, nullptr, scratch, B, C, S, p, D, eps);
     }
-    US_CHECK_LAUNCH();
-    launch_conv3x3(scratch, conv_w, conv_b, out, B, C, S, s);
-    US_CHECK_LAUNCH();
-    return USPACE_OK;
+    return head_conv(scratch, conv_w, conv_b, out, B, C, S, s);
 }
 
 extern "C" int uspace_add_broadcast(float* x, uint16_t* x_bf16, const float* delta, float scale, int B,
@@ -1024,10 +1033,10 @@ extern "C" int uspace_add_broadcast_rows(float* x, uint16_t* x_bf16, const float
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)B * per_sample;
     if ((per_sample & 3) == 0) {
-        hipLaunchKernelGGL(add_bcast_kernel, dim3(grid_for(total >> 2)), dim3(256), 0, s, x, x_bf16, delta, scale,
+        hipLaunchKernelGGL(add_bcast_kernel<4>, dim3(grid_for(total >> 2)), dim3(256), 0, s, x, x_bf16, delta, scale,
                            row_scale, per_sample >> 2, total >> 2);
     } else {
-        hipLaunchKernelGGL(add_bcast_tail_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, x_bf16, delta, scale,
+        hipLaunchKernelGGL(add_bcast_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, x, x_bf16, delta, scale,
                            row_scale, per_sample, total);
     }
     US_CHECK_LAUNCH();
@@ -1068,10 +1077,10 @@ extern "C" int uspace_cfg_combine(const float* pair, const float* row_scale, flo
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)B * per_sample;
     if ((per_sample & 3) == 0 && !(((uintptr_t)pair | (uintptr_t)out) & 15)) {
-        hipLaunchKernelGGL(cfg_combine_kernel, dim3(grid_for(total >> 2)), dim3(256), 0, s, pair, row_scale, scale, out,
+        hipLaunchKernelGGL(cfg_combine_kernel<4>, dim3(grid_for(total >> 2)), dim3(256), 0, s, pair, row_scale, scale, out,
                            per_sample >> 2, total >> 2);
     } else {
-        hipLaunchKernelGGL(cfg_combine_tail_kernel, dim3(grid_for(total)), dim3(256), 0, s, pair, row_scale, scale, out, per_sample,
+        hipLaunchKernelGGL(cfg_combine_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, pair, row_scale, scale, out, per_sample,
                            total);
     }
     US_CHECK_LAUNCH();
@@ -1081,13 +1090,7 @@ extern "C" int uspace_cfg_combine(const float* pair, const float* row_scale, flo
 extern "C" int uspace_ode_combine(float* out, const float* y, const float* const* k, const float* coef, int n_k,
                                   long n, uspace_stream_t stream) {
     if (!out || !y || n <= 0 || n_k < 0 || n_k > 8 || (n_k > 0 && (!k || !coef))) return USPACE_ERR_ARG;
-    KPtrs kp;
-    kp.n = n_k;
-    for (int i = 0; i < 8; ++i) {
-        kp.k[i] = i < n_k ? k[i] : nullptr;
-        kp.c[i] = i < n_k ? coef[i] : 0.f;
-    }
-    hipLaunchKernelGGL(ode_combine_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, out, y, kp, n);
+    hipLaunchKernelGGL(ode_combine_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, out, y, make_kptrs(k, coef, n_k), n);
     US_CHECK_LAUNCH();
     return USPACE_OK;
 }
@@ -1096,15 +1099,9 @@ extern "C" int uspace_ode_error_norm(const float* y0, const float* y1, const flo
                                      int n_k, float rtol, float atol, long n, float* scratch, float* result,
                                      uspace_stream_t stream) {
     if (!y0 || !y1 || !k || !coef || !scratch || !result || n <= 0 || n_k <= 0 || n_k > 8) return USPACE_ERR_ARG;
-    KPtrs kp;
-    kp.n = n_k;
-    for (int i = 0; i < 8; ++i) {
-        kp.k[i] = i < n_k ? k[i] : nullptr;
-        kp.c[i] = i < n_k ? coef[i] : 0.f;
-    }
     const int nblk = grid_for(n, 1024);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ode_err_partial_kernel, dim3(nblk), dim3(256), 0, s, y0, y1, kp, rtol, atol, n, scratch);
+    hipLaunchKernelGGL(ode_err_partial_kernel, dim3(nblk), dim3(256), 0, s, y0, y1, make_kptrs(k, coef, n_k), rtol, atol, n, scratch);
     US_CHECK_LAUNCH();
     hipLaunchKernelGGL(ode_err_finish_kernel, dim3(1), dim3(256), 0, s, scratch, nblk, n, result);
     US_CHECK_LAUNCH();

@@ -27,7 +27,7 @@ struct Model {
     int pos, pw, pb, cw = -1, cb = -1;
     std::vector<BlockIdx> blk;
     int ng, nb, dw, db, convw, convb;
-    int head_img = -1;   // derived: the output head's weight image (rowops.hip head_weight_image), when the fast path applies
+    int head_img;        // derived: the output head's weight image (rowops.hip head_weight_image)
     int L, extras, npatch, nblocks;
 };
 
@@ -36,6 +36,7 @@ bool valid_cfg(const uspace_uvit_config* c) {
     if (c->img_size <= 0 || c->patch_size <= 0 || c->img_size % c->patch_size) return false;
     if (c->in_chans <= 0 || c->in_chans * c->patch_size * c->patch_size > 16) return false;
     if (c->embed_dim <= 0 || c->embed_dim % 64 || c->num_heads * 64 != c->embed_dim) return false;
+    if (c->embed_dim > 2048) return false;           // the output head keeps its weight image in LDS (rowops.hip, us_head_pack)
     if (c->depth <= 0 || (c->depth & 1)) return false;
     if (c->mlp_hidden <= 0 || c->mlp_hidden % 64) return false;
     if (c->n_extra < 0 || c->clip_dim < 0 || (c->clip_dim % 64)) return false;
@@ -96,7 +97,7 @@ Model build_model(const uspace_uvit_config& c) {
         b.fc1_cs = m.lay.add(Hd, P_F32);
         if (b.skip_w >= 0) b.skip_cs2 = m.lay.add(D, P_F32);
     }
-    if ((D & 31) == 0 && D <= 2048) m.head_img = m.lay.add((long)us_head_image_floats((int)D), P_F32);
+    m.head_img = m.lay.add((long)us_head_image_floats((int)D), P_F32);
     return m;
 }
 
@@ -179,10 +180,8 @@ extern "C" int uspace_uvit_pack_weights(const uspace_uvit_config* cfg, const flo
                                      (float*)at(b.fc1_fb), (float*)at(b.fc1_cs), Hd, D, stream));
         if (b.skip_cs2 >= 0) US_TRY(us_rowsum_bf16(params[b.skip_w], 2 * D, D, D, (float*)at(b.skip_cs2), D, s));
     }
-    if (m.head_img >= 0)
-        US_TRY(us_head_pack(params[m.ng], params[m.nb], params[m.dw], params[m.db], cfg->patch_size * cfg->patch_size * cfg->in_chans, D,
-                            (float*)at(m.head_img), s));
-    return USPACE_OK;
+    return us_head_pack(params[m.ng], params[m.nb], params[m.dw], params[m.db], cfg->patch_size * cfg->patch_size * cfg->in_chans, D,
+                        (float*)at(m.head_img), s);
 }
 
 namespace {
@@ -223,10 +222,21 @@ namespace {
 // ([2 Bs, C, S, S]) instead of io->out.
 struct MapWindow { int q0, nq, k0, nk; };
 struct PairArgs { const float* uncond; bool batched; float* pred; };
+struct ForwardOpts {             // what the exported forms add to the product forward; each fills only what it uses
+    int stop_after = -1;
+    float* dump = nullptr;
+    float* maps = nullptr;
+    MapWindow mw{0, 0, 0, 0};
+    const PairArgs* pair = nullptr;
+};
 int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes, const uspace_uvit_io* io,
-                 int Bs, int stop_after, float* dump, uspace_stream_t stream, float* maps = nullptr, MapWindow mw = MapWindow{0, 0, 0, 0},
-                 const PairArgs* pair = nullptr) {
+                 int Bs, uspace_stream_t stream, const ForwardOpts& opt) {
     if (!valid_cfg(cfg) || !blob || !workspace || !io || Bs <= 0) return USPACE_ERR_ARG;
+    const int stop_after = opt.stop_after;
+    float* const dump = opt.dump;
+    float* const maps = opt.maps;
+    const MapWindow mw = opt.mw;
+    const PairArgs* const pair = opt.pair;
     const int B = pair ? 2 * Bs : Bs;
     if (stop_after >= 0 && (!dump || stop_after > cfg->depth + 1)) return USPACE_ERR_ARG;
     if (!io->x || !io->t || !io->out) return USPACE_ERR_ARG;
@@ -322,115 +332,90 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
     if (stop_after == 0) return tap();
 
     const int half = c.depth / 2;
+    // The two LayerNorm modes differ in how "norm then GEMM" is issued for qkv and fc1 and in what the producers of x get.
+    // Separate: a LayerNorm launch into h, then a plain GEMM; the producers write x and, where a later GEMM reads it, its bf16 copy.
+    // Folded through the GEMMs (include/uspace_hip.h, uspace_gemm_ext): every producer of x that a norm follows (skip_linear, proj,
+    // fc2 of the in-blocks) also leaves a centred bf16 copy and per-row partial sums; qkv and fc1 read that copy with gamma-folded
+    // weights and finish the normalisation in their epilogues.  No LayerNorm launch except the first centring pass; the residual
+    // stream x itself is unchanged (fp32).
+    // The long skips are then kept as the CENTRED bf16 copies the in-blocks' fc2 writes for the next norm anyway (round 4: the raw bf16
+    // copy beside it was one more 2 M D-byte store per in-block): in-block i's fc2 centres by cskip[i] -- the row means its own
+    // fc1 published there instead of into cbuf -- and writes straight into skip slot i, which is also what the next block's qkv
+    // reads.  skip_linear(cat([x, skip])) = x W1^T + (skip_c + cskip) W2^T: the second term's constant part is the rank-1 epilogue
+    // term cskip[m] * rowsum(W2)[n] (USPACE_EPI_RANK1; libs/uvit.py:158-159).
+    constexpr int C_ = USPACE_EPI_CEN_OUT, L_ = USPACE_EPI_LN_IN, K_ = USPACE_EPI_RANK1;
+    float* const cskip = (float*)(ws + w.cskip);
+    int slots_skip = 0, slots_proj = 0, slots_fc2 = 0;   // partial-sum slots per row of each producer (the 64-wide tile form of short-K launches writes more of them)
+    int np = 1;                                   // partial-sum slots of whoever wrote the centred copy last
+    const uint16_t* cen_in = xc;                  // the centred copy the next consumer reads
+    const float* c_in = cbuf;                     // ... and the constants it was centred by
+    uspace_gemm_ext prod{};                       // folded producers: centre by cbuf, write xc + part
     if (fold) {
-        // LayerNorm folded through the GEMMs around it (include/uspace_hip.h, uspace_gemm_ext): every producer of x
-        // (skip_linear, proj, fc2 before a norm) also leaves a centred bf16 copy xc and per-row partial sums; qkv and fc1
-        // read xc with gamma-folded weights and finish the normalisation in their epilogues.  No LayerNorm launch
-        // except the first centring pass; the residual stream x itself is unchanged (fp32).
-        constexpr int C_ = USPACE_EPI_CEN_OUT, L_ = USPACE_EPI_LN_IN;
-        // partial-sum slots per row of each producer (the 64-wide tile form of short-K launches writes more of them)
-        const int slots_skip = us_gemm_part_slots_k(M, D, 2 * D, sk_on), slots_proj = us_gemm_part_slots_k(M, D, D, sk_on),
-                  slots_fc2 = us_gemm_part_slots_k(M, D, Hd, sk_on);
+        slots_skip = us_gemm_part_slots_k(M, D, 2 * D, sk_on), slots_proj = us_gemm_part_slots_k(M, D, D, sk_on);
+        slots_fc2 = us_gemm_part_slots_k(M, D, Hd, sk_on);
         if (slots_skip <= 0 || slots_proj <= 0 || slots_fc2 <= 0) return USPACE_ERR_ARG;
-        auto PFx = [&](int idx) { return (const float*)(wb + m.lay.p[idx].offset); };
         US_TRY(uspace_center_rows(x, xc, cbuf, part, M, D, stream));
-        int np = 1;                                   // partial-sum slots of whoever wrote the centred copy last
-        uspace_gemm_ext prod{};                       // producers: centre by cbuf, write xc + part
         prod.row_c = cbuf; prod.out_cen = xc; prod.ld_cen = D; prod.part_out = part; prod.norm_dim = D; prod.eps = 1e-5f;
         prod.split_ws = plain.split_ws; prod.split_ws_bytes = plain.split_ws_bytes;
-        // The long skips are kept as the CENTRED bf16 copies the in-blocks' fc2 writes for the next norm anyway (round 4: the raw bf16
-        // copy beside it was one more 2 M D-byte store per in-block): in-block i's fc2 centres by cskip[i] -- the row means its own
-        // fc1 published there instead of into cbuf -- and writes straight into skip slot i, which is also what the next block's qkv
-        // reads.  skip_linear(cat([x, skip])) = x W1^T + (skip_c + cskip) W2^T: the second term's constant part is the rank-1 epilogue
-        // term cskip[m] * rowsum(W2)[n] (USPACE_EPI_RANK1; libs/uvit.py:158-159).
-        constexpr int K_ = USPACE_EPI_RANK1;
-        float* const cskip = (float*)(ws + w.cskip);
-        const uint16_t* cen_in = xc;                  // the centred copy the next consumer reads
-        const float* c_in = cbuf;                     // ... and the constants it was centred by
-        for (int i = 0; i < m.nblocks; ++i) {
-            const BlockIdx& b = m.blk[i];
-            const bool is_in = i < half, is_out = i > half, is_last = i == m.nblocks - 1;
-            if (is_out) {
-                const int si = m.nblocks - 1 - i;     // LIFO (libs/uvit.py:159,340)
-                uspace_gemm_ext pskip = prod;
-                pskip.row_add = cskip + (size_t)si * M;
-                pskip.col_add = PFx(b.skip_cs2);
-                US_TRY(us_gemm_bf16_ext(xb, D, skips + (size_t)si * MD, D, D, PH(b.skip_w), 2 * D, M, D, 2 * D, K_ | C_ | B_ | F_, PF(b.skip_b),
-                                        nullptr, 0, x, D, nullptr, 0, sk_ptr(pskip), sk_on, stream));
-                np = slots_skip;
-                cen_in = xc;
-                c_in = cbuf;
-            }
+    }
+    // norm1 -> qkv (fc1 = false) or norm2 -> fc1: folded, one consumer GEMM on the copy `cen` centred by `cen_c`, which publishes the
+    // row means into c_out; separate, LayerNorm of x into h and a plain GEMM
+    auto norm_gemm = [&](const BlockIdx& b, bool fc1, const uint16_t* cen, const float* cen_c, float* c_out) {
+        const int N = fc1 ? Hd : 3 * D, act = fc1 ? G_ : 0;
+        uint16_t* const out = fc1 ? f : qkv;
+        if (fold) {
             uspace_gemm_ext cons{};
-            cons.row_c = c_in; cons.c_out = cbuf; cons.part_in = part; cons.np_in = np; cons.norm_dim = D; cons.eps = 1e-5f;
-            cons.colsum = PFx(b.qkv_cs);
-            US_TRY(us_gemm_bf16_ext(cen_in, D, nullptr, 0, D, PH(b.qkv_f), D, M, 3 * D, D, L_ | B_ | H_, PFx(b.qkv_fb), nullptr, 0,
-                                    nullptr, 0, qkv, 3 * D, &cons, sk_on, stream));
-            if (maps) US_TRY(uspace_attention_map_bf16(qkv, maps + (size_t)i * map_stride, B, L, H, mw.q0, mw.nq, mw.k0, mw.nk, stream));
-            const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
-            US_TRY(us_attention_any(qkv, ks, h, B, L, H, stream));
-            US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, C_ | B_ | R_ | F_, PF(b.projb), x, D, x, D,
-                                    nullptr, 0, sk_ptr(prod), sk_on, stream));
-            np = slots_proj;
-            cons.row_c = cbuf;
-            cons.np_in = np;
-            cons.colsum = PFx(b.fc1_cs);
-            if (is_in) cons.c_out = cskip + (size_t)i * M;      // the row means at norm2 of an in-block stay with its skip
-            US_TRY(us_gemm_bf16_ext(xc, D, nullptr, 0, D, PH(b.fc1_f), D, M, Hd, D, L_ | B_ | G_ | H_, PFx(b.fc1_fb), nullptr, 0,
-                                    nullptr, 0, f, Hd, &cons, sk_on, stream));
-            if (is_in) {
-                // the next block starts with a norm: centred copy + partials -- written into the skip slot
-                uspace_gemm_ext pin = prod;
-                pin.row_c = cskip + (size_t)i * M;
-                pin.out_cen = skips + (size_t)i * MD;
-                US_TRY(us_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, C_ | B_ | R_ | F_, PF(b.fc2b), x, D,
-                                        x, D, nullptr, 0, sk_ptr(pin), sk_on, stream));
-                np = slots_fc2;
-                cen_in = skips + (size_t)i * MD;
-                c_in = cskip + (size_t)i * M;
-            } else {
-                // mid / out blocks: the next consumer is skip_linear (raw bf16 xb) or the head (its own norm)
-                uint16_t* copy = is_last ? nullptr : xb;
-                US_TRY(us_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, copy ? (B_ | R_ | F_ | H_) : (B_ | R_ | F_),
-                                        PF(b.fc2b), x, D, x, D, copy, D, sk_ptr(plain), sk_on, stream));
-            }
-            if (i == half) {
-                if (io->mid_tap) {
-                    if (hipMemcpyAsync(io->mid_tap, x, MD * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-                        return USPACE_ERR_LAUNCH;
-                }
-                if (io->mid_delta)
-                    US_TRY(uspace_add_broadcast_rows(x, xb, io->mid_delta, io->mid_scale, io->mid_row_scale, B, (long)L * D, stream));
-            }
-            if (i + 1 == stop_after && !is_last) return tap();
+            cons.row_c = cen_c; cons.c_out = c_out; cons.part_in = part; cons.np_in = np; cons.norm_dim = D; cons.eps = 1e-5f;
+            cons.colsum = PF(fc1 ? b.fc1_cs : b.qkv_cs);
+            return us_gemm_bf16_ext(cen, D, nullptr, 0, D, PH(fc1 ? b.fc1_f : b.qkv_f), D, M, N, D, L_ | B_ | act | H_,
+                                    PF(fc1 ? b.fc1_fb : b.qkv_fb), nullptr, 0, nullptr, 0, out, N, &cons, sk_on, stream);
         }
-    } else {
+        US_TRY(uspace_layernorm_f32_bf16(x, PF(fc1 ? b.n2w : b.n1w), PF(fc1 ? b.n2b : b.n1b), h, M, D, 1e-5f, stream));
+        return us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(fc1 ? b.fc1w : b.qkv), D, M, N, D, fc1 ? (B_ | act | H_) : H_,
+                                fc1 ? PF(b.fc1b) : nullptr, nullptr, 0, nullptr, 0, out, N, nullptr, sk_on, stream);
+    };
     for (int i = 0; i < m.nblocks; ++i) {
         const BlockIdx& b = m.blk[i];
         const bool is_in = i < half, is_out = i > half, is_last = i == m.nblocks - 1;
         if (is_out) {
             // x = skip_linear(cat([x, skip]))  -- two K slabs, skips popped LIFO (libs/uvit.py:159,340)
-            const uint16_t* skip = skips + (size_t)(m.nblocks - 1 - i) * MD;
-            US_TRY(us_gemm_bf16_ext(xb, D, skip, D, D, PH(b.skip_w), 2 * D, M, D, 2 * D, B_ | F_, PF(b.skip_b),
-                                    nullptr, 0, x, D, nullptr, 0, sk_ptr(plain), sk_on, stream));
+            const int si = m.nblocks - 1 - i;
+            uspace_gemm_ext e = fold ? prod : plain;
+            if (fold) {
+                e.row_add = cskip + (size_t)si * M;
+                e.col_add = PF(b.skip_cs2);
+            }
+            US_TRY(us_gemm_bf16_ext(xb, D, skips + (size_t)si * MD, D, D, PH(b.skip_w), 2 * D, M, D, 2 * D, (fold ? K_ | C_ : 0) | B_ | F_,
+                                    PF(b.skip_b), nullptr, 0, x, D, nullptr, 0, sk_ptr(e), sk_on, stream));
+            np = slots_skip;
+            cen_in = xc;
+            c_in = cbuf;
         }
         // x += proj(attn(norm1(x)))
-        US_TRY(uspace_layernorm_f32_bf16(x, PF(b.n1w), PF(b.n1b), h, M, D, 1e-5f, stream));
-        US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.qkv), D, M, 3 * D, D, H_, nullptr, nullptr, 0, nullptr, 0,
-                                qkv, 3 * D, nullptr, sk_on, stream));
+        US_TRY(norm_gemm(b, false, cen_in, c_in, cbuf));
         if (maps) US_TRY(uspace_attention_map_bf16(qkv, maps + (size_t)i * map_stride, B, L, H, mw.q0, mw.nq, mw.k0, mw.nk, stream));
         const float* ks = io->key_scale ? io->key_scale + (size_t)i * B * L : nullptr;
         US_TRY(us_attention_any(qkv, ks, h, B, L, H, stream));
-        US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, B_ | R_ | F_, PF(b.projb), x, D, x, D,
-                                nullptr, 0, sk_ptr(plain), sk_on, stream));
-        // x += fc2(gelu(fc1(norm2(x))))
-        US_TRY(uspace_layernorm_f32_bf16(x, PF(b.n2w), PF(b.n2b), h, M, D, 1e-5f, stream));
-        US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.fc1w), D, M, Hd, D, B_ | G_ | H_, PF(b.fc1b), nullptr, 0,
-                                nullptr, 0, f, Hd, nullptr, sk_on, stream));
-        // bf16 copy of the block output: the skip (in-blocks) or the next skip_linear's first K slab
+        US_TRY(us_gemm_bf16_ext(h, D, nullptr, 0, D, PH(b.projw), D, M, D, D, (fold ? C_ : 0) | B_ | R_ | F_, PF(b.projb), x, D, x, D,
+                                nullptr, 0, sk_ptr(fold ? prod : plain), sk_on, stream));
+        np = slots_proj;
+        // x += fc2(gelu(fc1(norm2(x)))); folded, the row means at norm2 of an in-block stay with its skip
+        float* const c2 = fold && is_in ? cskip + (size_t)i * M : cbuf;
+        US_TRY(norm_gemm(b, true, xc, cbuf, c2));
+        // bf16 copy of the block output: the skip (in-blocks) or the next skip_linear's first K slab; none ahead of the head (its own
+        // norm).  Folded, an in-block's copy is the centred one with its partial sums: the next block starts with a norm
         uint16_t* copy = is_in ? skips + (size_t)i * MD : (is_last ? nullptr : xb);
-        US_TRY(us_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, copy ? (B_ | R_ | F_ | H_) : (B_ | R_ | F_),
-                                PF(b.fc2b), x, D, x, D, copy, D, sk_ptr(plain), sk_on, stream));
+        uspace_gemm_ext e = plain;
+        if (fold && is_in) {
+            e = prod;
+            e.row_c = c_in = c2;
+            e.out_cen = copy;
+            cen_in = copy;
+            copy = nullptr;
+            np = slots_fc2;
+        }
+        US_TRY(us_gemm_bf16_ext(f, Hd, nullptr, 0, Hd, PH(b.fc2w), Hd, M, D, Hd, (fold && is_in ? C_ : 0) | B_ | R_ | F_ | (copy ? H_ : 0),
+                                PF(b.fc2b), x, D, x, D, copy, D, sk_ptr(e), sk_on, stream));
         if (i == half) {
             if (io->mid_tap) {
                 if (hipMemcpyAsync(io->mid_tap, x, MD * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
@@ -441,14 +426,9 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
         }
         if (i + 1 == stop_after && !is_last) return tap();
     }
-    }
-    float* const pred = pair ? pair->pred : io->out;
-    if (m.head_img >= 0)     // decoder weights with the last LayerNorm folded in, prepared by uspace_uvit_pack_weights
-        US_TRY(us_output_head_packed(x, L, m.extras, PF(m.head_img), PF(m.convw), PF(m.convb), (float*)(ws + w.head), pred, B,
-                                     c.in_chans, c.img_size, c.patch_size, D, 1e-5f, (hipStream_t)stream));
-    else
-        US_TRY(uspace_output_head(x, L, m.extras, PF(m.ng), PF(m.nb), PF(m.dw), PF(m.db), PF(m.convw), PF(m.convb),
-                                  (float*)(ws + w.head), pred, B, c.in_chans, c.img_size, c.patch_size, D, 1e-5f, stream));
+    // the head: decoder weights with the last LayerNorm folded in, prepared by uspace_uvit_pack_weights
+    US_TRY(us_output_head_packed(x, L, m.extras, PF(m.head_img), PF(m.convw), PF(m.convb), (float*)(ws + w.head), pair ? pair->pred : io->out,
+                                 B, c.in_chans, c.img_size, c.patch_size, D, 1e-5f, (hipStream_t)stream));
     if (stop_after == m.nblocks) return tap();
     return USPACE_OK;
 }
@@ -456,20 +436,26 @@ int forward_impl(const uspace_uvit_config* cfg, const void* blob, void* workspac
 
 extern "C" int uspace_uvit_forward(const uspace_uvit_config* cfg, const void* blob, void* workspace,
                                    size_t workspace_bytes, const uspace_uvit_io* io, int B, uspace_stream_t stream) {
-    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, -1, nullptr, stream);
+    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, stream, ForwardOpts{});
 }
 
 extern "C" int uspace_uvit_forward_tap(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
                                        const uspace_uvit_io* io, int B, int stop_after, float* dump, uspace_stream_t stream) {
     if (stop_after < 0) return USPACE_ERR_ARG;
-    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, stop_after, dump, stream);
+    ForwardOpts opt;
+    opt.stop_after = stop_after;
+    opt.dump = dump;
+    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, stream, opt);
 }
 
 extern "C" int uspace_uvit_forward_maps(const uspace_uvit_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
                                         const uspace_uvit_io* io, int B, int q0, int nq, int k0, int nk, float* maps,
                                         uspace_stream_t stream) {
     if (!maps) return USPACE_ERR_ARG;
-    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, -1, nullptr, stream, maps, MapWindow{q0, nq, k0, nk});
+    ForwardOpts opt;
+    opt.maps = maps;
+    opt.mw = MapWindow{q0, nq, k0, nk};
+    return forward_impl(cfg, blob, workspace, workspace_bytes, io, B, stream, opt);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -499,7 +485,9 @@ extern "C" int uspace_uvit_forward_cfg(const uspace_uvit_config* cfg, const void
     if (!base || workspace_bytes < base + pair_pred_bytes(*cfg, B)) return USPACE_ERR_WORKSPACE;
     float* pred = pair_out ? pair_out : (float*)((char*)workspace + base);
     const PairArgs pair{uncond, uncond_batched != 0, pred};
-    US_TRY(forward_impl(cfg, blob, workspace, base, io, B, -1, nullptr, stream, nullptr, MapWindow{0, 0, 0, 0}, &pair));
+    ForwardOpts opt;
+    opt.pair = &pair;
+    US_TRY(forward_impl(cfg, blob, workspace, base, io, B, stream, opt));
     return uspace_cfg_combine(pred, row_scale, scale, io->out, B, (long)cfg->in_chans * cfg->img_size * cfg->img_size, stream);
 }
 

@@ -57,6 +57,8 @@ class UViTBase(nn.Module):
                 "mlp_time_embed=False, conv=True, skip=True (configs/*.py)")
         if embed_dim % num_heads or embed_dim // num_heads != 64:
             raise NotImplementedError("head_dim must be 64 (every reference config: 512/8, 1024/16)")
+        if embed_dim > 2048:
+            raise NotImplementedError("embed_dim must be at most 2048 (the output head keeps its weight image in LDS; 1536 in the largest reference config)")
         if depth % 2:
             raise NotImplementedError("depth must be even")
         self.num_features = self.embed_dim = embed_dim
@@ -251,6 +253,24 @@ class UViTBase(nn.Module):
         return out if out_dtype == torch.float32 else out.to(out_dtype)
 
     # ------------------------------------------------------------------ the single HIP call
+    def _prepare_io(self, x, timesteps, context, mid_delta, mid_scale, mid_tap, key_scale, mid_row_scale, out):
+        """What ``_run`` and ``_tap`` share: x as contiguous fp32, the timesteps as a device fp32 scalar (stride 0) or one per sample,
+        and the ``UvitIO`` over them -> (io, (xin, t)); the caller keeps the pair alive until the call is enqueued."""
+        B, dev = x.shape[0], x.device
+        xin = x.detach().to(torch.float32).contiguous()
+        t = torch.as_tensor(timesteps, dtype=torch.float32, device=dev).detach()
+        if t.dim() == 0:
+            t_stride = 0
+        else:
+            if t.shape[0] != B:
+                raise ValueError(f"timesteps must have {B} entries, got {tuple(t.shape)}")
+            t_stride = t.stride(0)
+            if t_stride not in (0, 1):
+                t = t.contiguous(); t_stride = 1
+        io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta), float(mid_scale),
+                         _hip.ptr(mid_tap), _hip.ptr(key_scale), _hip.ptr(out), _hip.ptr(mid_row_scale))
+        return io, (xin, t)
+
     def _run(self, x, timesteps, context=None, mid_delta=None, mid_scale=0.0, mid_tap=None, key_scale=None,
              mid_row_scale=None, keep_f32=False, attn_maps=None, cfg=None):
         """``keep_f32``: return the fp32 result even for a half-precision ``x`` (the caller still has fp32 work to do).
@@ -283,37 +303,20 @@ class UViTBase(nn.Module):
             if cfg is not None and cfg[4]:
                 return empty, torch.empty(0, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev)
             return empty
-        xin = x.detach().to(torch.float32).contiguous()
-        t = timesteps
-        if not torch.is_tensor(t):
-            t = torch.tensor(float(t), dtype=torch.float32, device=dev)
-        t = t.detach().to(device=dev, dtype=torch.float32)
-        if t.dim() == 0:
-            t_stride = 0
-        else:
-            if t.shape[0] != B:
-                raise ValueError(f"timesteps must have {B} entries, got {tuple(t.shape)}")
-            t_stride = t.stride(0)
-            if t_stride not in (0, 1):
-                t = t.contiguous(); t_stride = 1
-        plain = mid_delta is None and mid_tap is None and key_scale is None
-        if self.use_graph and plain and t_stride == 0 and attn_maps is None and cfg is None:
-            return self._run_graph(xin, t, context, B, dev, torch.float32 if keep_f32 else x.dtype)
         out = torch.empty(B, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev)
+        io, (xin, t) = self._prepare_io(x, timesteps, context, mid_delta, mid_scale, mid_tap, key_scale, mid_row_scale, out)
+        plain = mid_delta is None and mid_tap is None and key_scale is None
+        if self.use_graph and plain and io.t_stride == 0 and attn_maps is None and cfg is None:
+            return self._run_graph(xin, t, context, B, dev, torch.float32 if keep_f32 else x.dtype)
         blob = self._packed_blob(dev)
         if cfg is not None:
             uncond, batched, scale, row_scales, want_pair = cfg
             ws = self._cfg_workspace.take(B, dev, _hip.lib().uspace_uvit_cfg_workspace_bytes(ctypes.byref(self._cfg), B))
-            io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta), float(mid_scale), None,
-                             _hip.ptr(key_scale), _hip.ptr(out), _hip.ptr(mid_row_scale))
             pair = torch.empty(2 * B, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev) if want_pair else None
             _hip.uvit_forward_cfg(self._cfg, blob, ws, io, B, uncond, batched, scale, row_scale=row_scales, pair_out=pair)
             out = out if (keep_f32 or x.dtype == torch.float32) else out.to(x.dtype)
             return (out, pair) if want_pair else out
         ws = self._workspace_for(B, dev)
-        io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta),
-                         float(mid_scale), _hip.ptr(mid_tap), _hip.ptr(key_scale), _hip.ptr(out),
-                         _hip.ptr(mid_row_scale))
         if attn_maps is not None:
             maps = torch.empty(self.depth + 1, B, nq, nk, dtype=torch.float32, device=dev)
             _hip.check(_hip.lib().uspace_uvit_forward_maps(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
@@ -344,18 +347,12 @@ class UViTBase(nn.Module):
         _hip.require_device(x, "x")
         B = x.shape[0]
         dev = x.device
-        xin = x.detach().to(torch.float32).contiguous()
-        t = torch.as_tensor(timesteps, dtype=torch.float32, device=dev).detach()
-        t_stride = 0 if t.dim() == 0 else 1
-        t = t.contiguous()
         if out is None:
             out = torch.empty(B, self.in_chans, self.img_size, self.img_size, dtype=torch.float32, device=dev)
         dump = torch.empty(B, self.seq_len, self.embed_dim, dtype=torch.float32, device=dev)
         blob = self._packed_blob(dev)
         ws = self._workspace_for(B, dev) if workspace is None else workspace
-        io = _hip.UvitIO(_hip.ptr(xin), _hip.ptr(t), t_stride, _hip.ptr(context), _hip.ptr(mid_delta),
-                         float(mid_scale), _hip.ptr(mid_tap), _hip.ptr(key_scale), _hip.ptr(out),
-                         _hip.ptr(mid_row_scale))
+        io, _keep = self._prepare_io(x, timesteps, context, mid_delta, mid_scale, mid_tap, key_scale, mid_row_scale, out)
         _hip.check(_hip.lib().uspace_uvit_forward_tap(ctypes.byref(self._cfg), _hip.ptr(blob), _hip.ptr(ws), ws.numel(),
                                                       ctypes.byref(io), B, int(stage), _hip.ptr(dump), _hip.stream_ptr()),
                    "uspace_uvit_forward_tap")
