@@ -51,30 +51,43 @@ def quick_gelu(x):
     return x * torch.sigmoid(1.702 * x)
 
 
-def causal_attention(q, k, v, heads, tight):
+def causal_attention(q, k, v, heads, tight, fault=None):
     """q, k, v [B, L, D] float64 -> [B, L, D]: softmax(q k^T / 8 + causal mask) v per head (head_dim 64).  Tight: P is
-    rounded to bf16 and normalised by the sum of the rounded values; the output is rounded to bf16."""
+    rounded to bf16 and normalised by the sum of the rounded values; the output is rounded to bf16.  ``fault``: one of the
+    attention entries of FAULTS planted."""
     B, L, D = q.shape
     sh = lambda t: t.reshape(B, L, heads, D // heads).transpose(1, 2)
-    s = sh(q) @ sh(k).transpose(-1, -2) / 8.0
-    s = s.masked_fill(~torch.ones(L, L, dtype=torch.bool).tril(), float("-inf"))
+    s = sh(q) @ sh(k).transpose(-1, -2) / (65.0 ** 0.5 if fault == "scale_1/sqrt65" else 8.0)
+    if fault != "no_mask":
+        s = s.masked_fill(~torch.ones(L, L, dtype=torch.bool).tril(1 if fault == "mask_allows_next_token" else 0), float("-inf"))
     p = _bf(torch.exp(s - s.amax(-1, keepdim=True)), tight)
     o = (p @ sh(v)) / p.sum(-1, keepdim=True)
     return _bf(o.transpose(1, 2).reshape(B, L, D), tight)
 
 
-def layer(x, sd, i, mode, heads=12, eps=1e-5):
-    """One pre-LN block (layer i of ``sd``): x [B, L, D] -> x + attn(LN1 x) then + MLP(LN2 .), float64."""
+def _ln(x, w, b, eps, fault=None):
+    """LayerNorm in float64; ``unbiased_var``: the variance over D - 1, ``eps_1e-6``: eps 1e-6 whatever the argument."""
+    D = x.shape[-1]
+    if fault == "eps_1e-6":
+        eps = 1e-6
+    if fault == "unbiased_var":
+        return (x - x.mean(-1, keepdim=True)) / torch.sqrt(x.var(-1, unbiased=True, keepdim=True) + eps) * w + b
+    return F.layer_norm(x, (D,), w, b, eps)
+
+
+def layer(x, sd, i, mode, heads=12, eps=1e-5, fault=None):
+    """One pre-LN block (layer i of ``sd``): x [B, L, D] -> x + attn(LN1 x) then + MLP(LN2 .), float64.  ``fault``: one of the
+    layer entries of FAULTS planted."""
     t = mode == "tight"
     pre = f"encoder.layers.{i}."
     x = x.to(torch.float64)
-    D = x.shape[-1]
     lin = lambda a, n: a @ _w(sd, pre + n + ".weight", t).T + _v(sd, pre + n + ".bias")
-    h = _bf(F.layer_norm(x, (D,), _v(sd, pre + "layer_norm1.weight"), _v(sd, pre + "layer_norm1.bias"), eps), t)
+    h = _bf(_ln(x, _v(sd, pre + "layer_norm1.weight"), _v(sd, pre + "layer_norm1.bias"), eps, fault), t)
     q, k, v = (_bf(lin(h, f"self_attn.{n}_proj"), t) for n in "qkv")
-    x = x + lin(causal_attention(q, k, v, heads, t), "self_attn.out_proj")
-    h = _bf(F.layer_norm(x, (D,), _v(sd, pre + "layer_norm2.weight"), _v(sd, pre + "layer_norm2.bias"), eps), t)
-    h = _bf(quick_gelu(_bf(lin(h, "mlp.fc1"), t)), t)
+    x = x + lin(causal_attention(q, k, v, heads, t, fault), "self_attn.out_proj")
+    h = _bf(_ln(x, _v(sd, pre + "layer_norm2.weight"), _v(sd, pre + "layer_norm2.bias"), eps, fault), t)
+    f1 = _bf(lin(h, "mlp.fc1"), t)
+    h = _bf(F.gelu(f1) if fault == "erf_gelu" else quick_gelu(f1), t)
     return x + lin(h, "mlp.fc2")
 
 
@@ -84,23 +97,58 @@ def embed(ids, sd):
     return (sd["embeddings.token_embedding.weight"][ids] + sd["embeddings.position_embedding.weight"][:ids.shape[1]]).to(torch.float64)
 
 
-def final_norm(x, sd, eps=1e-5):
+def final_norm(x, sd, eps=1e-5, fault=None):
     x = x.to(torch.float64)
-    return F.layer_norm(x, (x.shape[-1],), _v(sd, "final_layer_norm.weight"), _v(sd, "final_layer_norm.bias"), eps)
+    if fault == "no_final_ln":
+        return x
+    fault = {"final_eps_1e-6": "eps_1e-6", "final_unbiased_var": "unbiased_var"}.get(fault, fault)
+    return _ln(x, _v(sd, "final_layer_norm.weight"), _v(sd, "final_layer_norm.bias"), eps, fault)
 
 
-def forward(ids, sd, mode, heads=12, eps=1e-5, taps=True, stop_after=None):
+def forward(ids, sd, mode, heads=12, eps=1e-5, taps=True, stop_after=None, fault=None):
     """ids [B, L] -> (last_hidden_state, [hidden state after k layers for k = 0 ..]) in float64; ``stop_after=k``: return the state
-    after k layers (HF hidden_states[k]) instead of the final-LN output."""
+    after k layers (HF hidden_states[k]) instead of the final-LN output.  ``fault``: one entry of FAULTS planted wherever it acts."""
     x = embed(ids, sd)
     hidden = [x] if taps else None
     n = n_layers(sd) if stop_after is None else stop_after
     for i in range(n):
-        x = layer(x, sd, i, mode, heads, eps)
+        x = layer(x, sd, i, mode, heads, eps, fault)
         if taps:
             hidden.append(x)
-    out = x if stop_after is not None else final_norm(x, sd, eps)
+    out = x if stop_after is not None else final_norm(x, sd, eps, fault)
     return out, hidden
+
+
+# ------------------------------------------------------------------------------------------------------------------ faults
+# name -> (metric that excludes the fault, what it does), in the convention of tests/dino_cases.py and tests/uvit_stages.py:
+#   "update_tight", "final_ln": TOL entries of tests/test_gpu_clip_parity.py -- the faulty float64 model lies FAULT_MARGIN bounds from
+#       the true one, layers measured one by one from the true previous state;
+#   "projection": the layer's residual projected onto the fault's direction (tests/util.py::fault_projection), bound PROJECTION_GPU
+#       on the GPU, within PROJECTION_HOST of 0 / of 1 without / with the fault on the CPU (workflow parameters: on the stress set
+#       the massive token's rounding correlates with the LayerNorm directions, c_f reaches 0.33 without a fault);
+#   UNIT_TESTS: besides, excluded by the GPU unit test named there, by FAULT_MARGIN of its bound.  The eps fault is a plain fault
+#       only on the "tiny" parameter set, in layer 0, whose rows have a variance of the order of eps
+#       (tests/test_gpu_clip_parity.py::test_layer_0_normalises_rows_at_eps): that pins the eps clip.hip hands on, the unit test the kernels.
+# tests/test_clip_faults_host.py proves every entry.  Beside the projection faults: the largest |c_f| an MI355X measured
+# (tests/test_gpu_clip_parity.py::test_no_planted_fault_explains_the_gpu_error, 12 layers, 4 prompts).
+# The text transformer does not pool: the pooled row is taken by the text head, whose suite has that fault
+# (tests/clip_vision_cases.py::pooled_index, tests/test_clip_vision_host.py::test_pooled_index_follows_hf), so none is planted here.
+FAULT_MARGIN = 10.0
+PROJECTION_HOST = 0.25
+PROJECTION_GPU = 0.5
+FAULTS = {
+    "mask_allows_next_token": ("update_tight", "causal mask one diagonal too wide"),
+    "no_mask": ("update_tight", "no causal mask"),
+    "erf_gelu": ("projection", "erf-GELU instead of quick-GELU"),                            # measured |c_f| 0.001
+    "scale_1/sqrt65": ("projection", "logits scaled by 1 / sqrt(65) instead of 1 / 8"),     # measured |c_f| 0.013
+    "unbiased_var": ("projection", "LayerNorm variance over D - 1 (layers and final norm)"),  # measured |c_f| 0.016
+    "eps_1e-6": ("update_tight", "LayerNorm eps 1e-6 instead of 1e-5 in the layers"),       # layer 0 of the tiny set (the eps clip.hip passes), and UNIT_TESTS
+    "final_eps_1e-6": ("final_ln", "final LayerNorm with eps 1e-6"),
+    "final_unbiased_var": ("final_ln", "final LayerNorm with the variance over D - 1"),
+    "no_final_ln": ("final_ln", "final LayerNorm omitted"),
+}
+UNIT_TESTS = {"eps_1e-6": ("tests/test_gpu_clip_parity.py::test_layernorm_kernels_at_d768",)}
+FAULT_IDS = (8, 201, (0, 1, 4, 7))        # prompt_ids(n, seed) and the sampled prompts: the empty one, the full one and two ragged ones
 
 
 # ------------------------------------------------------------------------------------------------------------------ parameters
@@ -110,7 +158,7 @@ def clip_params(kind="workflow", seed=0, vocab_size=49408, hidden_size=768, inte
     residual stream by roughly 0.1-1x its size; LN gamma / beta and every bias are non-trivial.  ``kind="stress"``: the same plus
     a massive first token (channels MASSIVE of position row 0 at +-64), an end-of-text table row with one channel at 40, head
     SINK_HEAD whose logits for key 0 (the massive token) exceed the others by about 20-40 in every layer, and head SHARP_HEAD with
-    4x sharper logits."""
+    4x sharper logits.  ``kind="tiny"``: the workflow set with the two tables at 0.003x (the eps of layer 0's norms shows)."""
     g = torch.Generator().manual_seed(seed)
     D, Fd, H = hidden_size, intermediate_size, num_attention_heads
     rn = lambda *s: torch.randn(*s, generator=g)
@@ -132,6 +180,9 @@ def clip_params(kind="workflow", seed=0, vocab_size=49408, hidden_size=768, inte
         sd[pre + "layer_norm2.bias"] = 0.1 * rn(D)
     sd["final_layer_norm.weight"] = 1.0 + 0.2 * rn(D)
     sd["final_layer_norm.bias"] = 0.1 * rn(D)
+    if kind == "tiny":          # workflow with both tables at 0.003x: layer 0 normalises rows with a variance of 2.6e-6, of the order of eps
+        sd["embeddings.token_embedding.weight"] *= 0.003
+        sd["embeddings.position_embedding.weight"] *= 0.003
     if kind == "stress":
         pos, tok = sd["embeddings.position_embedding.weight"], sd["embeddings.token_embedding.weight"]
         sign = torch.tensor([1.0, -1.0, 1.0, -1.0])[:len(MASSIVE)]

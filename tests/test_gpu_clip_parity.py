@@ -21,7 +21,8 @@ import pytest
 import torch
 
 from tests import clip_stages as S
-from tests.util import rel_l2
+from tests import unit_fault_cases as U
+from tests.util import fault_projection, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -81,6 +82,46 @@ def test_every_layer_against_float64_tight(models, kind, B):
     fe = rel_l2(out[rows].numpy(), S.final_norm(T[12][rows], sd).numpy())
     print(f"A {kind} B={B} final LN {fe:.2e}")
     assert fe < TOL["final_ln"]
+
+
+def test_no_planted_fault_explains_the_gpu_error(models):
+    """The update bound of A is 3x a layer's rounding noise; the projection faults of S.FAULTS move a layer by less than ten such
+    bounds.  So every layer's residual r = T_k - layer(T_{k-1}, tight) is projected onto each fault's direction d_f (the loose model
+    with and without the fault, from the GPU's own previous tap): c_f = <r, d_f> / <d_f, d_f> is 0 for a correct kernel and 1 for one
+    with the fault (tests/test_clip_faults_host.py: within 0.25 of either with the tight model in the GPU's place).  Bound: 0.5."""
+    sd, m = models["workflow"]
+    n, seed, rows = S.FAULT_IDS
+    rows = list(rows)
+    ids = S.prompt_ids(n, seed=seed)
+    T = [t[rows].double() for t in _taps(m, ids.cuda())]
+    faults = [f for f, (metric, _what) in S.FAULTS.items() if metric == "projection"]
+    worst = dict.fromkeys(faults, 0.0)
+    for k in range(12):
+        tight, true = S.layer(T[k], sd, k, "tight"), S.layer(T[k], sd, k, "loose")
+        for f in faults:
+            worst[f] = max(worst[f], abs(fault_projection(T[k + 1], tight, S.layer(T[k], sd, k, "loose", fault=f), true)))
+    print("A' workflow |c_f|", " ".join(f"{f} {v:.3f}" for f, v in worst.items()))
+    assert worst and max(worst.values()) < S.PROJECTION_GPU, worst
+
+
+def test_layer_0_normalises_rows_at_eps():
+    """On the workflow and stress sets no row a LayerNorm sees has a variance below 0.2, and an eps of 1e-6 moves a layer's update by
+    1e-5.  The "tiny" set (both tables at 0.003x, two layers) puts rows with a variance of 2.6e-6 in front of layer 0: there the eps
+    clip.hip hands to its LayerNorm launches moves the update by 0.62 (tests/test_clip_faults_host.py).  A's bound on both layers."""
+    from uspace_amd.libs.clip import CLIPTextTransformer, CLIP_L_TEXT
+    cfg = dict(CLIP_L_TEXT, num_hidden_layers=2)
+    sd = S.clip_params("tiny", seed=101, **cfg)
+    m = CLIPTextTransformer(**cfg)
+    m.load_state_dict(sd)
+    m = m.cuda()
+    n, seed, rows = S.FAULT_IDS
+    rows = list(rows)
+    dev = S.prompt_ids(n, seed=seed).cuda()
+    T = [m(dev, hidden_state=k).cpu()[rows].double() for k in range(3)]
+    assert float(T[0].var(-1).max()) < 1e-5
+    errs = [float((T[k + 1] - S.layer(T[k], sd, k, "tight")).norm() / (T[k + 1] - T[k]).norm()) for k in range(2)]
+    print("A' tiny update errors", ["%.2e" % e for e in errs])         # measured 1.2e-3
+    assert max(errs) < TOL["update_tight"], errs
 
 
 # ------------------------------------------------------------------------------------------------------------------ B
@@ -309,3 +350,20 @@ def test_layernorm_kernels_at_d768(M):
     print(f"G LN M={M} fp32 {e32:.2f} x 2^-24 scale, bf16 beyond one ulp {float(eb.max()):.2f}")
     assert e32 < TOL["ln_err"]
     assert float(eb.max()) < TOL["ln_err"]
+    # rows whose variance is of the order of eps (1e-6 ... 1e-4; the rows above have variances of 2 and more, on which no eps shows),
+    # in the same units against float64: an eps of 1e-6 lies 1e6 bounds away (tests/test_clip_faults_host.py).  Measured: 3.8 / 0.0
+    assert M in U.CLIP_LAYERNORM_M
+    xs, gs, bs = U.ln_eps_rows(64, D, seed=1100 + M)
+    ref = torch.from_numpy(U.layernorm_f64(xs, gs, bs))
+    scale = torch.from_numpy(U.ln_noise_scale(xs, gs, bs))
+    dx, dg, db = (torch.from_numpy(a).cuda() for a in (xs, gs, bs))
+    y32 = torch.empty(64, D, device="cuda")
+    _hip.check(L.uspace_layernorm_f32(_hip.ptr(dx), _hip.ptr(dg), _hip.ptr(db), _hip.ptr(y32), 64, D, ctypes.c_float(1e-5),
+                                      _hip.stream_ptr()), "layernorm_f32")
+    e32 = float(((y32.cpu().double() - ref).abs() / scale).max())
+    yb = torch.empty(64, D, dtype=torch.bfloat16, device="cuda")
+    _hip.check(L.uspace_layernorm_f32_bf16(_hip.ptr(dx), _hip.ptr(dg), _hip.ptr(db), _hip.ptr(yb), 64, D, ctypes.c_float(1e-5),
+                                           _hip.stream_ptr()), "layernorm_f32_bf16")
+    eb = ((yb.cpu().double() - ref).abs() - _bf16_ulp(ref)).clamp_min(0.0) / scale
+    print(f"G LN M={M} rows at eps: fp32 {e32:.2f} x 2^-24 scale, bf16 beyond one ulp {float(eb.max()):.2f}")
+    assert e32 < TOL["ln_err"] and float(eb.max()) < TOL["ln_err"]

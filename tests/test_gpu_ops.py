@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import _cops as C
+from tests import unit_fault_cases as U
 from tests.util import bf16_round, rel_l2, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -114,6 +115,16 @@ def test_gemm_epilogues(hip, big):
     ref = C.linear(A, W)
     err = np.abs(o16.float().cpu().numpy() - ref)
     assert (err <= BF16_EPS * np.abs(ref) * 1.01 + 1e-4).all()
+    # bias + GELU -> bf16 on GELU's negative tail (z = -4.5 ... -2.5), against float64 erf-GELU: the flat 1e-4 above is the size of the
+    # values there and of the whole difference between the erf and the tanh form; with the fp32 arithmetic's own floor in its place
+    # the tanh form lies 16 bounds away (tests/test_uvit_faults_host.py).  Measured here: 0.97 of the bound, the bf16 rounding itself
+    assert U.EPILOGUE_SHAPES[big] == (M, N, K)
+    A, W, b, rows = U.epilogue_gelu_tail_case(big)
+    hip.gemm(to_dev(A, torch.bfloat16), to_dev(W, torch.bfloat16), bias=to_dev(b), gelu=True, out_bf16=o16)
+    ref, bound = U.gelu_tail_reference(A, W, b, rows)
+    worst = float((np.abs(o16.float().cpu().numpy()[rows] - ref) / bound).max())
+    print(f"gemm_epilogues big={big} GELU tail: worst {worst:.2f} of the bound")
+    assert worst <= 1.0, worst
 
 
 def test_gemm_two_k_slabs_equal_concat(hip):
@@ -149,6 +160,16 @@ def test_layernorm(hip, M, D):
     got = hip.layernorm(to_dev(x), to_dev(g), to_dev(b)).float().cpu().numpy()
     err = np.abs(got - ref)
     assert (err <= BF16_EPS * np.abs(ref) * 1.01 + 2e-5).all(), err.max()
+    # rows whose variance is of the order of eps (1e-6 ... 1e-4): the rows above have a variance of 9, on which no eps shows.  Against
+    # float64, the same bound; an eps of 1e-6 lies 5000 bounds away (tests/test_uvit_faults_host.py).  Measured here: 0.98 of the bound,
+    # the bf16 rounding itself
+    assert (M, D) in U.LAYERNORM_SHAPES
+    xs, gs, bs = U.ln_eps_rows(64, D, seed=D + M)
+    ref = U.layernorm_f64(xs, gs, bs)
+    got = hip.layernorm(to_dev(xs), to_dev(gs), to_dev(bs)).float().cpu().numpy()
+    worst = float((np.abs(got - ref) / U.ln_bf16_bound(ref)).max())
+    print(f"layernorm M={M} D={D} rows at eps: worst {worst:.2f} of the bound")
+    assert worst <= 1.0, worst
 
 
 # (B * H <= 64 with at most 17 key tiles runs four workgroups per head, each on a quarter of the query tiles, B * H <= 128 two;
@@ -769,6 +790,54 @@ def test_layernorm_folded_through_gemms(hip, M, D, Kp, N2):
     # the plain entry point refuses the extended flags
     assert lib.uspace_gemm_bf16(hip.ptr(xc), D, None, 0, D, hip.ptr(dW2), D, M, N2, D, hip.EPI_OUT_BF16 | 64, None, None, 0,
                                 None, 0, hip.ptr(y), N2, hip.stream_ptr()) != 0
+
+
+@pytest.mark.parametrize("M,D,Kp,N2", U.FOLDED_EPS_CASES)
+def test_layernorm_folded_through_gemms_rows_at_eps(hip, M, D, Kp, N2):
+    """The producer / consumer pair of test_layernorm_folded_through_gemms with every fifth row a row whose variance is of the order
+    of eps (4e-6 ... 3.6e-5; tests/unit_fault_cases.py::folded_eps_case): there the rstd the consumer's epilogue builds from the partial
+    sums depends on the eps it is handed.  Those rows against float64 within that test's bound; an eps of 1e-6 lies 40 bounds away
+    (tests/test_uvit_faults_host.py).  Measured: 2.5e-3 of 4e-3 (the other rows 2.6e-3)."""
+    import ctypes
+    case = U.folded_eps_case(M, D, Kp, N2)
+    rows = case["rows"]
+    x_ref, y_ref = U.folded_reference(case, rows)
+    lib = hip.lib()
+    slots = lib.uspace_gemm_part_slots_k(M, D, Kp)
+    dA, dW, db = to_dev(case["A"], torch.bfloat16), to_dev(case["W"], torch.bfloat16), to_dev(case["b"])
+    x = to_dev(case["R"]).clone()
+    xc = torch.empty(M, D, dtype=torch.bfloat16, device="cuda")
+    part = torch.full((M, slots, 2), float("nan"), device="cuda")
+    dc = to_dev(case["c"])
+    ext = hip.GemmExt(hip.ptr(dc).value, hip.ptr(xc).value, D, hip.ptr(part).value, None, 0, None, None, D, 1e-5)
+    ws_bytes = lib.uspace_gemm_split_ws_bytes(M, D, Kp)
+    ws = torch.zeros(max(ws_bytes // 4, 4), device="cuda")
+    ext.split_ws, ext.split_ws_bytes = hip.ptr(ws).value, ws_bytes
+    flags = hip.EPI_BIAS | hip.EPI_RESIDUAL | hip.EPI_OUT_F32 | hip.EPI_CEN_OUT
+    rc = lib.uspace_gemm_bf16_ext(hip.ptr(dA), Kp, None, 0, Kp, hip.ptr(dW), Kp, M, D, Kp, flags, hip.ptr(db), hip.ptr(x), D,
+                                  hip.ptr(x), D, None, 0, ctypes.byref(ext), hip.stream_ptr())
+    assert rc == 0
+    # the eps rows of x are b + R in one fp32 add: to an fp32 ulp of the addends
+    xg = x.cpu().numpy()
+    assert np.abs(xg[rows] - x_ref).max() <= 2.0 ** -23 * np.abs(case["b"]).max()
+    assert torch.equal(xc, (x - dc[:, None]).to(torch.bfloat16))
+    W2g = bf16_round(case["W2"] * case["gam"][None, :])
+    bias2 = (case["b2"] + case["W2"] @ case["bet"]).astype(np.float32)
+    colsum = W2g.sum(axis=1).astype(np.float32)
+    y = torch.empty(M, N2, dtype=torch.bfloat16, device="cuda")
+    cout = torch.empty(M, device="cuda")
+    dW2, dbias2, dcs = to_dev(W2g, torch.bfloat16), to_dev(bias2), to_dev(colsum)
+    ext2 = hip.GemmExt(hip.ptr(dc).value, None, 0, None, hip.ptr(part).value, slots, hip.ptr(dcs).value, hip.ptr(cout).value, D,
+                       1e-5)
+    rc = lib.uspace_gemm_bf16_ext(hip.ptr(xc), D, None, 0, D, hip.ptr(dW2), D, M, N2, D, hip.EPI_BIAS | hip.EPI_OUT_BF16 | hip.EPI_LN_IN,
+                                  hip.ptr(dbias2), None, 0, None, 0, hip.ptr(y), N2, ctypes.byref(ext2), hip.stream_ptr())
+    assert rc == 0
+    yg = y.float().cpu().numpy()
+    e = rel_l2(yg[rows], y_ref)
+    others = np.setdiff1d(np.arange(M), rows)[:600]
+    eo = rel_l2(yg[others], U.folded_reference(case, others)[1])
+    print(f"folded LN at eps rows M={M} D={D}: eps rows {e:.2e}, other rows {eo:.2e}")
+    assert e < U.FOLDED_Y_TOL and eo < U.FOLDED_Y_TOL, (e, eo)
 
 
 @pytest.mark.parametrize("M,D", [(64 * 257, 1024), (32 * 257, 1024), (4 * 257, 512), (4 * 257, 1024), (515, 256), (64 * 334, 512)])

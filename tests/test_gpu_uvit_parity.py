@@ -10,6 +10,9 @@ A  every block against ``block(T_{k-1}, tight_<mode>)`` of the GPU's own previou
    ||T_k - ref_k|| / ||T_k - T_{k-1}|| -- the residual stream cannot hide a wrong branch; and against the loose float64 block.
    key_scale differs per block (L-t, S-t16): on the workflow set a block that reads its neighbour's slice moves its update by
    about 3e-2, ten times the bound.
+A' the planted faults of tests/uvit_stages.py::FAULTS that A's bound cannot see (most of them move a block by less than the bound):
+   on small nets, depth 4, the block's residual projected onto every such fault's direction, |c_f| < 0.5 (0: correct, 1: the
+   fault); and a "tiny" net whose block 0 normalises rows with a variance of the order of eps, under A's bound.
 B  the ends: stage 0 against the float64 embed (fp32-class), the output against the float64 head of T_{depth+1} (fp32-class:
    DESIGN.md 4.3, the hi+lo-split head).
 C  end to end against the loose float64 forward from the latents, with the error's growth block by block.
@@ -29,7 +32,7 @@ import pytest
 import torch
 
 from tests import uvit_stages as S
-from tests.util import rel_l2
+from tests.util import fault_projection, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -79,44 +82,21 @@ def _net(name, kind):
 def _inputs(spec, net, B, hooks, seed):
     """Latents, per-sample times and whatever the configuration and hook need, on the GPU (dict of _tap / _run keywords) and on
     the CPU (dict of S.forward keywords)."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, 4, 32, 32, generator=g)
-    t = 0.05 + 0.9 * torch.rand(B, generator=g)
-    gpu, cpu = dict(), dict()
+    x, t, cpu = S.inputs(spec, B, hooks, seed)          # (tests/uvit_stages.py: the host test of the planted faults builds the same)
+    gpu = dict()
     if spec.t2i:
-        ctx = torch.randn(B, spec.n_extra, spec.clip_dim, generator=g)
-        gpu["context"], cpu["context"] = ctx.cuda(), ctx
+        gpu["context"] = cpu["context"].cuda()
     elif spec.n_extra:
-        y = torch.randint(0, spec.num_classes, (B,), generator=g)
-        lab = net.label_emb.weight.detach()[y.cuda()].contiguous()
-        gpu["context"], cpu["y"] = lab, y
-    if hooks == "ks":            # a different attention-map edit per block: a third of the columns scaled by 0.1 ... 10, the rest by 1
-        ks = torch.ones(spec.nblocks, B, spec.L)
-        for i in range(spec.nblocks):
-            cols = torch.randperm(spec.L, generator=g)[:spec.L // 3]
-            ks[i][:, cols] = torch.exp(2.3 * (2 * torch.rand(B, cols.numel(), generator=g) - 1))
-        gpu["key_scale"], cpu["key_scale"] = ks.cuda(), ks
+        gpu["context"] = net.label_emb.weight.detach()[cpu["y"].cuda()].contiguous()
+    if hooks == "ks":
+        gpu["key_scale"] = cpu["key_scale"].cuda()
     if hooks == "mid":
-        delta = torch.randn(spec.L, spec.D, generator=g) * 0.5
-        rows = torch.linspace(-1.5, 2.0, B)
-        gpu.update(mid_delta=delta.cuda(), mid_scale=0.7, mid_row_scale=rows.cuda())
-        cpu["mid"] = (delta, 0.7, rows)
+        delta, scale, rows = cpu["mid"]
+        gpu.update(mid_delta=delta.cuda(), mid_scale=scale, mid_row_scale=rows.cuda())
     return x, t, gpu, cpu
 
 
-def _rows(cpu, rows):
-    """The CPU keywords restricted to the sampled samples."""
-    out = dict(cpu)
-    if "context" in out:
-        out["context"] = out["context"][rows]
-    if "y" in out:
-        out["y"] = out["y"][rows]
-    if "key_scale" in out:
-        out["key_scale"] = out["key_scale"][:, rows]
-    if "mid" in out:
-        d, s, r = out["mid"]
-        out["mid"] = (d, s, r[rows])
-    return out
+_rows = S.select_rows
 
 
 class _Mode:
@@ -203,6 +183,61 @@ def test_every_block_against_float64(case, fold):
         e = rel_l2(out.numpy(), ref.numpy())
         print(f"C {msg} out {e:.2e} growth", " ".join("%.1e" % g for g in growth))
         assert e < TOL["e2e"], (msg, e)
+
+
+# ------------------------------------------------------------------------------------------------------------------ A'
+def _fault_net(name):
+    key = ("fault", name)
+    if key not in _cache:
+        net, sd, spec, hooks, B = S.fault_net(name)
+        _cache[key] = (net.cuda(), sd, spec, hooks, B)
+    return _cache[key]
+
+
+@pytest.mark.parametrize("fold", [1, 0])
+@pytest.mark.parametrize("name", ["u512", "t2i512", "u1024", "stress512", "tiny512"])
+def test_no_planted_fault_explains_the_gpu_error(name, fold):
+    """The update bound of A is 3x the rounding noise of a block, and most planted faults of S.FAULTS move a block by less.  So the
+    block's residual r = T_k - block(T_{k-1}, tight_<mode>) is projected onto the direction d_f of every such fault (the loose model
+    with and without it, from the GPU's own previous tap): c_f = <r, d_f> / <d_f, d_f> is 0 for a correct kernel and 1 for one with
+    the fault; the noise is spread over L D elements and nearly orthogonal to d_f (tests/test_uvit_faults_host.py: within 0.25 of 0
+    and of 1 with the tight model in the GPU's place).  Bound: 0.5, the midpoint.  The same for the final LayerNorm's eps in the
+    head.  The stress net carries the omitted biases alone: every other direction drowns in the rounding of its massive channels.
+    The tiny net carries no projection: it is there for A's bound on block 0, where a wrong LayerNorm eps is a plain fault."""
+    net, sd, spec, hooks, B = _fault_net(name)
+    seed, rows = S.fault_case(name)
+    x, t, gpu, cpu = _inputs(spec, net, B, hooks, seed=seed)
+    with _Mode(fold):
+        folded = fold and _folds(spec, B)
+        assert folded == bool(fold)
+        T, out = _taps(net, spec, x, t, gpu, rows)
+    mode = "tight_fold" if folded else "tight_sep"
+    cr = _rows(cpu, rows)
+    kw = {k: cr[k] for k in ("key_scale", "mid") if k in cr}
+    T = [a.double() for a in T]
+    faults = [f for f, (metric, _what) in S.FAULTS.items() if metric == "projection" and name in S.fault_nets(f)]
+    worst = dict.fromkeys(faults, 0.0)
+    c, cskip, errs = None, [None] * spec.half, []
+    for i in range(spec.nblocks):
+        tight, c = S.step(spec, sd, T, i, mode, c=c, cskip=cskip, **kw)
+        if i < spec.half:
+            cskip[i] = c
+        errs.append(float((T[i + 1] - tight).norm() / (T[i + 1] - T[i]).norm()))
+        true = S.step(spec, sd, T, i, "loose", **kw)[0]
+        for f in faults:
+            if i in S.fault_blocks(spec, f):
+                cf = fault_projection(T[i + 1], tight, S.step(spec, sd, T, i, "loose", fault=f, **kw)[0], true)
+                worst[f] = max(worst[f], abs(cf))
+    if S.FAULTS["final_eps_1e-6"][0] == "projection_head" and name in S.fault_nets("final_eps_1e-6"):
+        ref = S.head(spec, sd, T[-1])
+        worst["final_eps_1e-6"] = abs(fault_projection(out, ref, S.head(spec, sd, T[-1], fault="final_eps_1e-6"), ref))
+    print(f"A' {name} B={B} {mode} update errors", " ".join("%.1e" % e for e in errs),
+          "|c_f|", " ".join(f"{f} {v:.3f}" for f, v in worst.items()))
+    # A's own bound on these nets: what excludes the plain faults of the table at depth 4, and, on the tiny net, whose block 0
+    # normalises rows with a variance of the order of eps, a wrong eps handed to either LayerNorm path (measured there: 6.0e-4; 1.2e-3 over these nets)
+    assert max(errs) < TOL["update_tight"], (name, mode, errs)
+    assert max(worst.values(), default=0.0) < S.PROJECTION_GPU, worst
+    assert worst or name == "tiny512"
 
 
 # ------------------------------------------------------------------------------------------------------------------ D
