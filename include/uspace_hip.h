@@ -616,7 +616,7 @@ USPACE_API int uspace_normalized_diff_f32(const float* a, const float* b, float*
  * owns 64 rows and walks the column tiles, the reductions fused.  No floating-point atomics: every output is bit-equal from
  * run to run.  workspace: uspace_metric_workspace_bytes(nx, ny, n_subsets, m) bytes (norms of both sets + the partial sums of
  * uspace_metric_poly_sums; pass ny = 0 for uspace_metric_knn_radius2, n_subsets = m = 0 where no sums are asked for); 0 on
- * invalid arguments.  The layout is one formula for all four consumers, norms first: uspace_metric_poly_sums computes no norms and
+ * invalid arguments.  The layout is one formula for all consumers, norms first: uspace_metric_poly_sums computes no norms and
  * leaves those (nx + ny) doubles untouched ahead of its partial sums (128 MiB per 2^24-row set, allocated and unused).
  * Nothing of the workspace is read before it is written.  These functions were added without a change
  * of USPACE_ABI_VERSION: they only add symbols.
@@ -650,6 +650,24 @@ USPACE_API int uspace_metric_poly_sums(const float* x, int nx, const float* y, i
  * 64-row block of the larger set); nothing of it is read before it is written.  Symbols only: USPACE_ABI_VERSION is unchanged. */
 USPACE_API int uspace_metric_rbf_sums(const float* x, int nx, const float* y, int ny, int F, double gamma, int normalize,
                                       double* sums, void* workspace, size_t workspace_bytes, uspace_stream_t stream);
+/* The k nearest rows of y for every row of x, with their indices (uspace_amd/tools/neighbors.py): d2 fp64 [nx, k] and idx int32
+ * [nx, k], each row ascending in the lexicographic order (d2, index).  1 <= k <= 16, F >= 1, nx, ny in 1 .. 2^24; k may exceed the
+ * number of eligible columns, and the tail of such a row is d2 = +inf, idx = -1.
+ *   Indices: idx holds index_base + j (y may be a shard of a larger bank; index_base >= 0 and index_base + ny - 1 <= INT_MAX).
+ *   self_base >= 0 leaves column j out for row i where index_base + j == self_base + i -- a set queried against itself, sharded
+ *   or not; self_base = -1 leaves nothing out.
+ *   Selection is by the engine's D2 above, which is accurate to an absolute 8 F u (|x|^2 + |y|^2), u = 2^-53: the k-th and the
+ *   (k + 1)-th candidate can be exchanged only where they lie within twice that ceiling of each other.  Equal rows of y give
+ *   bit-equal D2 and come out in index order.
+ *   Reported values are refined in the same call: each kept pair is recomputed as sum_f (x_if - y_jf)^2 with the differences formed
+ *   in fp64 from the fp32 values (one wave per pair, the summation order of the norms), so an exact copy reports exactly 0.0; each
+ *   row is then sorted again by (refined d2, index).  |d2 - exact| <= 4 F u d2.
+ * No atomics, one fixed order: a row's result is bit-equal from run to run and the same whether the row is alone or among others.
+ * workspace: uspace_metric_workspace_bytes(nx, ny, 0, 0) bytes, the two norm arrays.  USPACE_ERR_ARG (a NULL pointer, a size,
+ * k, F, index_base or self_base outside the ranges above) and USPACE_ERR_WORKSPACE are returned before any GPU work.  Symbols
+ * only: USPACE_ABI_VERSION is unchanged. */
+USPACE_API int uspace_metric_topk(const float* x, int nx, const float* y, int ny, int F, int k, int index_base, int self_base,
+                                  double* d2, int* idx, void* workspace, size_t workspace_bytes, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Inception Score and sFID (uspace_amd/tools/inception_score.py, sfid_score.py, eval_suite.py): the pool features, the

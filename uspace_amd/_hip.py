@@ -181,6 +181,7 @@ SIGNATURES = {
     "uspace_metric_manifold": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "uspace_metric_poly_sums": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _D, _D, _P, _P, _SZ, _P]),
     "uspace_metric_rbf_sums": (_I, [_P, _I, _P, _I, _I, _D, _I, _P, _P, _SZ, _P]),
+    "uspace_metric_topk": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "uspace_inception_forward_suite": (_I, [_P, _P, _SZ, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
     "uspace_inception_logits": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "uspace_inception_score_workspace_bytes": (_SZ, [_I, _I, _I]),
@@ -570,6 +571,26 @@ def metric_rbf_sums(x, y, gamma, normalize=False, ws=None):
     check(lib().uspace_metric_rbf_sums(ptr(x), nx, ptr(y), ny, x.shape[1], float(gamma), 1 if normalize else 0, ptr(sums), ptr(ws),
                                        ws.numel(), stream_ptr()), "uspace_metric_rbf_sums")
     return sums
+
+
+def metric_topk(x, y, k, index_base=0, self_base=-1, ws=None):
+    """(d2 fp64 [nx, k], idx int32 [nx, k]): the k nearest rows of ``y`` for every row of ``x`` in the order (d2, index), the
+    distances refined to sum (x - y)^2 in fp64; idx holds ``index_base`` + the row of ``y``; ``self_base`` >= 0 leaves out the column
+    with index_base + j == self_base + i.  A row with fewer than k eligible columns ends in (+inf, -1)."""
+    _metric_features(x, "x")
+    _metric_features(y, "y")
+    if x.shape[1] != y.shape[1]:
+        raise UspaceHipError(f"feature widths differ: {x.shape[1]} and {y.shape[1]}")
+    nx, F = x.shape
+    ny = y.shape[0]
+    if ws is None:
+        ws = metric_workspace(nx, ny, device=x.device)
+    k = int(k)
+    d2 = torch.empty(nx, max(k, 0), dtype=torch.float64, device=x.device)
+    idx = torch.empty(nx, max(k, 0), dtype=torch.int32, device=x.device)
+    check(lib().uspace_metric_topk(ptr(x), nx, ptr(y), ny, F, k, int(index_base), int(self_base), ptr(d2), ptr(idx), ptr(ws),
+                                   ws.numel(), stream_ptr()), "uspace_metric_topk")
+    return d2, idx
 
 
 def inception_logits(pool, weight, bias=None):

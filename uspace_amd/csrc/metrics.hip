@@ -1,7 +1,7 @@
-// Feature-set metrics (KID, precision / recall / density / coverage, RBF-kernel MMD / CMMD): reductions over the pairwise
+// Feature-set metrics (KID, precision / recall / density / coverage, RBF-kernel MMD / CMMD, nearest neighbours): reductions over the pairwise
 // quantities of two fp32 feature sets x [nx, F] and y [ny, F], computed in fp64 on v_mfma_f64_16x16x4_f64 and never stored as an nx x ny matrix.
 //
-// One tile engine, four consumers.  A workgroup (4 waves) owns 64 rows of x and walks every 128-column tile of y; wave w owns
+// One tile engine, five consumers.  A workgroup (4 waves) owns 64 rows of x and walks every 128-column tile of y; wave w owns
 // rows 16 w .. 16 w + 15 of the block against all 128 columns (8 MFMA tiles), so a row lives in ONE wave and every reduction along
 // a row is finished inside it: integer adds and minima (exact in any order), or fp64 sums in one fixed order.  No atomics.
 //   dot(i, j)  the fp64 MFMA over the fp32 values widened to fp64; k beyond F contributes exact zeros
@@ -16,6 +16,7 @@
 #include "common.h"
 
 #include <cfloat>
+#include <climits>
 
 namespace {
 
@@ -59,12 +60,13 @@ __device__ __forceinline__ float4 load4(const float* __restrict__ p, int k, int 
 
 // The engine.  C supplies: F, vec; n_cols(); row_a(r) / row_b(j): the fp32 row behind block-space index r / column j, or
 // nullptr beyond the set (staged as zeros); init(scratch); tile(acc, col0, scratch); finish(scratch).  acc[t][reg] of lane
-// (g = lane >> 4, c = lane & 15) is dot(row0 + 16 wave + g + 4 reg, col0 + 16 t + c).
+// (g = lane >> 4, c = lane & 15) is dot(row0 + 16 wave + g + 4 reg, col0 + 16 t + c).  scratch is kBM * kMaxK doubles of LDS, followed
+// by C::kIdxInts ints where the consumer declares any (TopkConsumer: the index lists; 0 leaves the array what it was).
 template <class C>
 __global__ __launch_bounds__(256, 2) void gram_kernel(C c) {
     __shared__ __attribute__((aligned(16))) float As[kBM * kLD];
     __shared__ __attribute__((aligned(16))) float Bs[kBN * kLD];
-    __shared__ double scratch[kBM * kMaxK];
+    __shared__ double scratch[kBM * kMaxK + C::kIdxInts / 2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, g = lane >> 4;
     const int row0 = blockIdx.x * kBM;
@@ -125,6 +127,7 @@ __global__ __launch_bounds__(256, 2) void gram_kernel(C c) {
 // the 16 lanes of a row one after the other in explicit turns (see tile()).  The kept multiset is the k smallest whatever
 // the order of insertion.
 struct KnnConsumer {
+    static constexpr int kIdxInts = 0;
     const float* x;
     const double* norm;
     double* radius2;
@@ -208,6 +211,7 @@ struct KnnConsumer {
 
 // ---- consumer 2: count[i] = #{j : D2(i, j) <= radius2_y[j]} and min_d2[i] = min_j D2(i, j)
 struct ManifoldConsumer {
+    static constexpr int kIdxInts = 0;
     const float *x, *y;
     const double *norm_x, *norm_y, *radius2_y;
     int* count;
@@ -266,6 +270,7 @@ struct ManifoldConsumer {
 // 0 x against x, 1 y against y (both without the positions p == q), 2 x against y.  Lane sums in tile order, a fixed xor tree per
 // wave, the four waves in order -> partial[(subset * 3 + which) * row_blocks + blockIdx.x]; poly_finish_kernel adds the row blocks.
 struct PolyConsumer {
+    static constexpr int kIdxInts = 0;
     const float *x, *y;
     const int *idx_x, *idx_y;
     double* partial;
@@ -325,6 +330,7 @@ struct PolyConsumer {
 // value.  A row block beyond the pair's rows walks no tile and writes a zero partial.  Summation as PolyConsumer:
 // partial[which * row_blocks + blockIdx.x], finished by poly_finish_kernel.
 struct RbfConsumer {
+    static constexpr int kIdxInts = 0;
     const float *x, *y;
     const double *norm_x, *norm_y;
     double* partial;
@@ -390,6 +396,166 @@ struct RbfConsumer {
             partial[(size_t)blockIdx.z * gridDim.x + blockIdx.x] = ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
     }
 };
+
+// ---- consumer 5: for every row i of x the k smallest D2(i, j) over the rows j of y WITH their indices: sorted lists of (d2, index)
+// pairs per row in LDS, the distances in scratch[row][k] as KnnConsumer keeps them, the indices in the kIdxInts ints behind them.
+// The order is lexicographic in (d2, global index), ascending, and the index comparison is written out in the insertion test: within
+// one lane's turn the columns arrive as col0 + 16 t + c16, and the turns go through c16, so the walk order is not the index order.
+// (The threshold test in front stays KnnConsumer's d < last: when a tile begins the list holds only earlier, hence smaller, columns,
+// and whatever this tile inserts is smaller than that threshold, so a candidate EQUAL to the list's last entry never displaces it.)
+// Equal rows of y give bit-equal D2 against any x_i (one norm kernel, one dot order), so exact duplicates come out by index.
+// index_base is added to every stored index; column j is left out for row i when index_base + j == self_base + i (self_base >= 0).
+// Unused tail entries stay (+inf, -1).
+//
+// Selection is by the Gram D2, which is accurate to an absolute 8 F u (|x|^2 + |y|^2): the k-th and the (k + 1)-th candidate can be
+// exchanged only where they lie within twice that ceiling of each other.  What is REPORTED is refined by topk_refine_kernel: every
+// kept pair recomputed as sum_f (x_if - y_jf)^2, the differences formed in fp64 from the fp32 values (exact), one wave per pair in
+// norms_kernel's order, so an exact copy reports exactly 0.0 and not the 1e-13 the cancellation leaves; then the row's k entries are
+// sorted again by (refined d2, index).
+struct TopkConsumer {
+    static constexpr int kIdxInts = kBM * kMaxK;
+    const float *x, *y;
+    const double *norm_x, *norm_y;
+    double* out_d2;
+    int* out_idx;
+    int nx, ny, F, k, index_base;
+    long long self_base;
+    bool vec;
+    double nr[4];
+    int grow[4], self_col[4];
+
+    __device__ int n_cols() const { return ny; }
+    __device__ const float* row_a(int r) const { return r < nx ? x + (size_t)r * F : nullptr; }
+    __device__ const float* row_b(int j) const { return j < ny ? y + (size_t)j * F : nullptr; }
+    __device__ void init(double* scratch) {
+        int* ilist = reinterpret_cast<int*>(scratch + kBM * kMaxK);
+        for (int i = threadIdx.x; i < kBM * kMaxK; i += 256) {
+            scratch[i] = __builtin_inf();
+            ilist[i] = -1;
+        }
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            grow[r] = blockIdx.x * kBM + wave * 16 + (lane >> 4) + 4 * r;
+            nr[r] = grow[r] < nx ? norm_x[grow[r]] : 0.0;
+            const long long sc = self_base + grow[r] - index_base;       // the column that is row grow[r] itself
+            self_col[r] = self_base >= 0 && sc >= 0 && sc < ny ? (int)sc : -1;
+        }
+        __syncthreads();
+    }
+    __device__ void tile(f64x4 (&acc)[kNT], int col0, double* scratch) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c16 = lane & 15, g = lane >> 4;
+        volatile double* list = scratch + (wave * 16 + g) * kMaxK;      // + 4 reg * kMaxK: the lists of row g + 4 reg
+        volatile int* ilist = reinterpret_cast<int*>(scratch + kBM * kMaxK) + (wave * 16 + g) * kMaxK;
+        double thr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) thr[r] = list[4 * r * kMaxK + k - 1];
+        bool pass = false;
+#pragma unroll
+        for (int t = 0; t < kNT; ++t) {
+            const int col = col0 + t * 16 + c16;
+            const double nyj = col < ny ? norm_y[col] : 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool valid = col < ny && grow[r] < nx && col != self_col[r];
+                const double d = valid ? dist2(nr[r], nyj, acc[t][r]) : __builtin_inf();
+                acc[t][r] = d;
+                pass |= d < thr[r];
+            }
+        }
+        if (!__any(pass)) return;
+        // KnnConsumer's turns: one lane of a row at a time, a turn ends with a wavefront-scope fence and a wave barrier
+#pragma unroll 1
+        for (int s = 0; s < 16; ++s) {
+            if (__ballot(c16 == s && pass) == 0) continue;       // wave-uniform: nobody holds a candidate in this turn
+            if (c16 == s && pass) {
+#pragma unroll
+                for (int t = 0; t < kNT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const double v = acc[t][r];
+                        const int vi = index_base + col0 + t * 16 + c16;
+                        volatile double* L = list + 4 * r * kMaxK;
+                        volatile int* I = ilist + 4 * r * kMaxK;
+                        const double last = L[k - 1];
+                        if (v < last || (v == last && vi < I[k - 1])) {      // (+inf never enters: the tail's -1 is below any index)
+                            int i = k - 1;
+                            while (i > 0) {
+                                const double u = L[i - 1];
+                                const int ui = I[i - 1];
+                                if (!(u > v || (u == v && ui > vi))) break;
+                                L[i] = u;
+                                I[i] = ui;
+                                --i;
+                            }
+                            L[i] = v;
+                            I[i] = vi;
+                        }
+                    }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    __device__ void finish(double* scratch) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if ((lane & 15) != 0) return;
+        volatile double* list = scratch + (wave * 16 + (lane >> 4)) * kMaxK;
+        volatile int* ilist = reinterpret_cast<int*>(scratch + kBM * kMaxK) + (wave * 16 + (lane >> 4)) * kMaxK;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (grow[r] < nx)
+                for (int i = 0; i < k; ++i) {
+                    out_d2[(size_t)grow[r] * k + i] = list[4 * r * kMaxK + i];
+                    out_idx[(size_t)grow[r] * k + i] = ilist[4 * r * kMaxK + i];
+                }
+    }
+};
+
+// The reported distances of TopkConsumer's pairs: a workgroup of k waves owns row i, wave w the pair (i, idx[i, w] - index_base):
+// lane l sums (x_if - y_jf)^2 over f = l, l + 64, ... in order, then wave_sum_f64's tree (norms_kernel's order); an empty slot
+// (idx -1) keeps +inf.  Thread 0 then sorts the row's k entries by (d2, index) and writes them back.
+__global__ __launch_bounds__(64 * kMaxK) void topk_refine_kernel(const float* __restrict__ x, const float* __restrict__ y, int F, int k,
+                                                                 int index_base, double* __restrict__ d2, int* __restrict__ idx) {
+    __shared__ double sd[kMaxK];
+    __shared__ int si[kMaxK];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const size_t row = blockIdx.x;
+    const int gi = idx[row * k + w];
+    double s = __builtin_inf();
+    if (gi >= 0) {
+        const float* px = x + row * F;
+        const float* py = y + (size_t)(gi - index_base) * F;
+        s = 0.0;
+        for (int f = lane; f < F; f += 64) {
+            const double v = (double)px[f] - (double)py[f];
+            s = __fma_rn(v, v, s);
+        }
+        s = wave_sum_f64(s);
+    }
+    if (lane == 0) {
+        sd[w] = s;
+        si[w] = gi;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int a = 1; a < k; ++a) {
+        const double v = sd[a];
+        const int vi = si[a];
+        int i = a;
+        while (i > 0 && (sd[i - 1] > v || (sd[i - 1] == v && si[i - 1] > vi))) {
+            sd[i] = sd[i - 1];
+            si[i] = si[i - 1];
+            --i;
+        }
+        sd[i] = v;
+        si[i] = vi;
+    }
+    for (int a = 0; a < k; ++a) {
+        d2[row * k + a] = sd[a];
+        idx[row * k + a] = si[a];
+    }
+}
 
 __global__ void poly_finish_kernel(const double* __restrict__ partial, int n_sums, int blocks, double* __restrict__ sums) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -519,6 +685,38 @@ extern "C" int uspace_metric_rbf_sums(const float* x, int nx, const float* y, in
     hipLaunchKernelGGL(gram_kernel<RbfConsumer>, dim3((unsigned)blocks, 1, 3), dim3(256), 0, st, c);
     US_CHECK_LAUNCH();
     hipLaunchKernelGGL(poly_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)c.partial, 3, blocks, sums);
+    US_CHECK_LAUNCH();
+    return USPACE_OK;
+}
+
+extern "C" int uspace_metric_topk(const float* x, int nx, const float* y, int ny, int F, int k, int index_base, int self_base,
+                                  double* d2, int* idx, void* workspace, size_t workspace_bytes, uspace_stream_t stream) {
+    if (!x || !y || !d2 || !idx || !workspace || !size_ok(nx) || !size_ok(ny) || F < 1 || k < 1 || k > kMaxK) return USPACE_ERR_ARG;
+    if (index_base < 0 || (long long)index_base + ny - 1 > INT_MAX || self_base < -1 || (long long)self_base + nx - 1 > INT_MAX)
+        return USPACE_ERR_ARG;
+    if (workspace_bytes < uspace_metric_workspace_bytes(nx, ny, 0, 0)) return USPACE_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    double* norm_x = (double*)workspace;
+    double* norm_y = norm_x + nx;
+    US_TRY(launch_norms(x, nx, F, norm_x, st));
+    US_TRY(launch_norms(y, ny, F, norm_y, st));
+    TopkConsumer c = {};
+    c.x = x;
+    c.y = y;
+    c.norm_x = norm_x;
+    c.norm_y = norm_y;
+    c.out_d2 = d2;
+    c.out_idx = idx;
+    c.nx = nx;
+    c.ny = ny;
+    c.F = F;
+    c.k = k;
+    c.index_base = index_base;
+    c.self_base = self_base;
+    c.vec = can_vec(x, F) && can_vec(y, F);
+    hipLaunchKernelGGL(gram_kernel<TopkConsumer>, dim3((unsigned)us_cdiv(nx, kBM)), dim3(256), 0, st, c);
+    US_CHECK_LAUNCH();
+    hipLaunchKernelGGL(topk_refine_kernel, dim3((unsigned)nx), dim3(64 * k), 0, st, x, y, F, k, index_base, d2, idx);
     US_CHECK_LAUNCH();
     return USPACE_OK;
 }
