@@ -864,6 +864,62 @@ USPACE_API int uspace_idnet_unit(const uspace_idnet_config* cfg, const void* blo
 USPACE_API int uspace_idnet_similarity_f64(const float* ea, const float* eb, int B, double* out, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Attribute-classifier tower and the effect of an attribute edit (uspace_amd/libs/resnet.py, tools/attr_metrics.py;
+ * csrc/resnet.hip): a torchvision-layout ResNet in eval mode, groups 1.  Stem: conv1 7 x 7 stride 2 padding 3 without bias, bn1,
+ * ReLU, max pool 3 x 3 stride 2 padding 1 (floor mode).  Body: layer1 .. layer4 of blocks[l] blocks; the first block of layers
+ * 2 - 4 has stride 2.  BasicBlock: conv3x3(stride) bn relu conv3x3 bn; Bottleneck: conv1x1 bn relu conv3x3(stride) bn relu conv1x1
+ * bn (the stride on the 3 x 3, "v1.5"; output channels 4 planes).  Shortcut: downsample.0 (1 x 1, the block's stride) and
+ * downsample.1 (batch norm) exactly when stride != 1 or in != out.  A block ends relu((branch + shift) + shortcut), in that order.
+ * Tail: the mean over the pixels, then fc with bias.  Batch norms use the running statistics, eps 1e-5, and are all folded into
+ * the convolution in front of them at pack time, in fp64, rounded once.  fp32 NHWC activations, every convolution the fp32-MFMA
+ * implicit GEMM (a k-ordered fp32 fma chain).  Every sum has one fixed order: an image's stage maps, pooled vector and logits are
+ * bit-identical whatever B it sits in and wherever it sits in the batch.  No atomics; nothing of a workspace is read before it
+ * is written.  Added without a change of USPACE_ABI_VERSION: symbols only.
+ * ------------------------------------------------------------------------------------- */
+/* (struct-then-typedef, as uspace_idnet_config; the binding is uspace_amd/_hip.py ResnetConfig) */
+struct uspace_resnet_config {
+    int stem;        /* conv1 output channels (64) */
+    int planes[4];   /* 64, 128, 256, 512 */
+    int blocks[4];   /* 2,2,2,2 | 3,4,6,3 | ...; each >= 1 */
+    int bottleneck;  /* 0: BasicBlock (expansion 1), 1: Bottleneck (expansion 4, stride on the 3 x 3: "v1.5") */
+    int num_outputs; /* fc rows, >= 1 */
+};
+typedef struct uspace_resnet_config uspace_resnet_config;
+
+/* parameter tensors in the module's state_dict order with the num_batches_tracked buffers dropped; a batch norm is weight, bias,
+ * running_mean, running_var: conv1.weight [stem, 3, 7, 7], bn1.*; per block layerL.i: conv1.weight, bn1.*, conv2.weight, bn2.*
+ * (Bottleneck: conv3.weight, bn3.* too), then downsample.0.weight [out, in, 1, 1] and downsample.1.* where the block has them;
+ * fc.weight [num_outputs, F], fc.bias, F = planes[3] (x 4 for Bottleneck).  Every channel count (stem, planes, 4 planes) must be
+ * a multiple of 4 and at most 2048; any H, W from 32 to 16384.  An invalid config gives USPACE_ERR_ARG (-1 from param_numel) / 0
+ * bytes; B outside 1 .. 32767, H or W outside their range, or a tensor of 2^31 elements or more likewise. */
+USPACE_API int uspace_resnet_num_params(const uspace_resnet_config* cfg);
+USPACE_API long uspace_resnet_param_numel(const uspace_resnet_config* cfg, int index);
+USPACE_API size_t uspace_resnet_weight_bytes(const uspace_resnet_config* cfg);
+USPACE_API size_t uspace_resnet_workspace_bytes(const uspace_resnet_config* cfg, int B, int H, int W);
+USPACE_API int uspace_resnet_pack_weights(const uspace_resnet_config* cfg, const float* const* params, int n_params, void* blob,
+                                          size_t blob_bytes, uspace_stream_t stream);
+/* x: fp32 NCHW [B, 3, H, W] in [0, 1] -> out: fp32 NHWC [B, H, W, 3], (x - mean_c) / std_c; mean and std are HOST arrays of 3
+ * floats (ImageNet's 0.485, 0.456, 0.406 and 0.229, 0.224, 0.225 for the usual classifiers), std positive and finite.  Not folded
+ * into conv1: the network zero-pads the normalised image. */
+USPACE_API int uspace_resnet_preprocess(const float* x, int B, int H, int W, const float* mean, const float* std, float* out,
+                                        uspace_stream_t stream);
+/* x_nhwc: fp32 [B, H, W, 3] (uspace_resnet_preprocess's output) -> logits fp32 [B, num_outputs]; pooled fp32 [B, F] or NULL */
+USPACE_API int uspace_resnet_forward(const uspace_resnet_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                     const float* x_nhwc, int B, int H, int W, float* pooled, float* logits, uspace_stream_t stream);
+/* Test aid: stage 0 = the stem after the max pool, 1 + u = block u's output (NHWC fp32 [B, h, w, c]), 1 + (number of blocks) =
+ * the pooled vector fp32 [B, F].  Nothing after the stage runs. */
+USPACE_API int uspace_resnet_tap(const uspace_resnet_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                 const float* x_nhwc, int B, int H, int W, int stage, float* dump, uspace_stream_t stream);
+/* The effect of an attribute edit from the classifier's logits za (original) and zb (edit), fp32 [B, A]; target int [B] (the
+ * edited attribute of each pair), sign fp32 [B] (the intended direction), sigma fp32 [A] (per-attribute logit standard deviation)
+ * or NULL for ones; all device pointers.  One thread per pair, fp64, in attribute order, d = zb - za:
+ * out [B, 4] = { sign d_t,  1 if sign zb_t > 0 else 0,  mean over j != t of |d_j| / sigma_j (0 if A == 1),
+ * |d_t| / sigma_t over (that + the sum over j != t of |d_j| / sigma_j), 0 where nothing moved }.  A target outside 0 .. A - 1
+ * gives that pair four NaNs. */
+USPACE_API int uspace_attr_effect_f64(const float* za, const float* zb, const int* target, const float* sign, const float* sigma,
+                                      int B, int A, double* out, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

@@ -64,6 +64,11 @@ class IdnetConfig(ctypes.Structure):
     _fields_ = [("input_size", ctypes.c_int), ("blocks", ctypes.c_int * 4), ("se", ctypes.c_int)]
 
 
+class ResnetConfig(ctypes.Structure):
+    _fields_ = [("stem", ctypes.c_int), ("planes", ctypes.c_int * 4), ("blocks", ctypes.c_int * 4), ("bottleneck", ctypes.c_int),
+                ("num_outputs", ctypes.c_int)]
+
+
 class GemmExt(ctypes.Structure):
     _fields_ = [("row_c", ctypes.c_void_p), ("out_cen", ctypes.c_void_p), ("ld_cen", ctypes.c_int),
                 ("part_out", ctypes.c_void_p), ("part_in", ctypes.c_void_p), ("np_in", ctypes.c_int),
@@ -218,6 +223,15 @@ SIGNATURES = {
     "uspace_idnet_unit_workspace_bytes": (_SZ, [ctypes.POINTER(IdnetConfig), _I, _I, _I, _I]),
     "uspace_idnet_unit": (_I, [ctypes.POINTER(IdnetConfig), _P, _P, _SZ, _I, _P, _I, _I, _I, _P, _P]),
     "uspace_idnet_similarity_f64": (_I, [_P, _P, _I, _P, _P]),
+    "uspace_resnet_num_params": (_I, [ctypes.POINTER(ResnetConfig)]),
+    "uspace_resnet_param_numel": (_L, [ctypes.POINTER(ResnetConfig), _I]),
+    "uspace_resnet_weight_bytes": (_SZ, [ctypes.POINTER(ResnetConfig)]),
+    "uspace_resnet_workspace_bytes": (_SZ, [ctypes.POINTER(ResnetConfig), _I, _I, _I]),
+    "uspace_resnet_pack_weights": (_I, [ctypes.POINTER(ResnetConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
+    "uspace_resnet_preprocess": (_I, [_P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _P, _P]),
+    "uspace_resnet_forward": (_I, [ctypes.POINTER(ResnetConfig), _P, _P, _SZ, _P, _I, _I, _I, _P, _P, _P]),
+    "uspace_resnet_tap": (_I, [ctypes.POINTER(ResnetConfig), _P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P]),
+    "uspace_attr_effect_f64": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),

@@ -1,8 +1,8 @@
 // One layout for every model's packed weights and workspaces (host side only): the aligned arena, the parameter table and
 // the loop that packs fp32 checkpoint tensors into a device blob.  Every model describes its parameters with a ParamTable and serves
 // num_params / param_numel / weight_bytes / pack_weights from it: uvit.hip, vae.hip (both halves), clip.hip, clip_vision.hip and dino.hip
-// (their layers through vit_encoder.h, the patch weight through vit_embed.h), and the fp32 convolution towers inception.hip, lpips.hip
-// and idnet.hip, whose convolutions and batch norms are P_OWNER entries that conv_f32.h's pack step writes.
+// (their layers through vit_encoder.h, the patch weight through vit_embed.h), and the fp32 convolution towers inception.hip, lpips.hip,
+// idnet.hip and resnet.hip, whose convolutions and batch norms are P_OWNER entries that conv_f32.h's pack step writes.
 #pragma once
 #include <vector>
 

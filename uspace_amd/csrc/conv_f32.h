@@ -1,5 +1,5 @@
 // The fp32 convolution and 3 x 3 pooling kernels over NHWC activations that the feature networks share (inception.hip,
-// lpips.hip, idnet.hip), with their launchers.  fp32 operands on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): that instruction is
+// lpips.hip, idnet.hip, resnet.hip), with their launchers.  fp32 operands on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): that instruction is
 // bit-for-bit a k-ordered fp32 fma chain, so every output element is fma(..fma(a_0 b_0, 0)..) over K in the fixed (tap, channel)
 // order, whatever the batch size: each image's activations are bit-identical across batch sizes.
 #pragma once
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void pool3_kernel(const float* __restrict__ x,
 // floats), the next K slice is prefetched into registers while the current one is multiplied.  VEC: Cin % 16 == 0,
 // so a K slice is 16 consecutive channels of one tap and each thread loads 8 of them as two 16-B loads; otherwise
 // (Conv2d_1a, Cin = 3) the slice is gathered element by element.  Padding and rows beyond M read as zeros.
-// EPI chooses the epilogue (below); only idnet.hip asks for another than the default.
+// EPI chooses the epilogue (below); only idnet.hip and resnet.hip ask for another than the default.
 struct ConvArgs {
     const float* x;
     const float* w;
@@ -65,10 +65,14 @@ struct ConvArgs {
     float* y;
     int H, W, cin, Ho, Wo, cout, kw, s, ph, pw, K, Kpad, ldo, coff, M;
     const float* slope = nullptr;       // CONV_EPI_PRELU: per output channel
+    const float* res = nullptr;         // CONV_EPI_ADD_RELU: the residual map, row m at res + m * ldr, channel n at + n
+    int ldr = 0;
 };
 
-// Epilogues: bias + ReLU (the feature networks) | bias + per-channel PReLU max(v, 0) + a_n min(v, 0) | bias alone.
-enum { CONV_EPI_RELU = 0, CONV_EPI_PRELU = 1, CONV_EPI_BIAS = 2 };
+// Epilogues: bias + ReLU (the feature networks) | bias + per-channel PReLU max(v, 0) + a_n min(v, 0) | bias alone |
+// the residual block's end, y = relu((acc + bias) + res[m, n]): the bias (the folded batch norm's shift) joins the accumulator
+// first and the residual second, the order of the network's own `bn(conv(x)) + identity`; the order is part of the bits.
+enum { CONV_EPI_RELU = 0, CONV_EPI_PRELU = 1, CONV_EPI_BIAS = 2, CONV_EPI_ADD_RELU = 3 };
 
 constexpr int BM = 128, BN = 64, BK = 16;
 
@@ -181,19 +185,26 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a) {
     for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
         const int mA = m0 + wm * 64 + row, mB = mA + 32;
-        if (mA < a.M) a.y[(size_t)mA * a.ldo + a.coff + n] = act(acc0[r] + bias);
-        if (mB < a.M) a.y[(size_t)mB * a.ldo + a.coff + n] = act(acc1[r] + bias);
+        if constexpr (EPI == CONV_EPI_ADD_RELU) {
+            if (mA < a.M) a.y[(size_t)mA * a.ldo + a.coff + n] = fmaxf((acc0[r] + bias) + a.res[(size_t)mA * a.ldr + n], 0.f);
+            if (mB < a.M) a.y[(size_t)mB * a.ldo + a.coff + n] = fmaxf((acc1[r] + bias) + a.res[(size_t)mB * a.ldr + n], 0.f);
+        } else {
+            if (mA < a.M) a.y[(size_t)mA * a.ldo + a.coff + n] = act(acc0[r] + bias);
+            if (mB < a.M) a.y[(size_t)mB * a.ldo + a.coff + n] = act(acc1[r] + bias);
+        }
     }
 }
 
 // ---- launcher.  w: packed W'[k = (ty * kw + tx) * Cin + c][n] with rows K .. Kpad - 1 zero, bias [Cout]; the output pixel
 // rows are ldo channels apart and the result lands at channel offset coff (Cout % 4 == 0: the weight rows are read 16 bytes
-// at a time).  EPI: the epilogue (CONV_EPI_*; slope [Cout] for PReLU); a template, so that only the translation unit that asks
-// for an epilogue carries its kernels.  Ho / Wo receive the output size.
+// at a time).  EPI: the epilogue (CONV_EPI_*; slope [Cout] for PReLU; res with rows ldr floats apart for ADD_RELU, which y must
+// not overlap); a template, so that only the translation unit that asks for an epilogue carries its kernels.  Ho / Wo receive
+// the output size.
 template <int EPI = CONV_EPI_RELU>
 int conv_f32_launch(const ConvSpec& c, const float* x, int B, int H, int W, const float* w, const float* bias, float* y, int ldo,
-                    int coff, hipStream_t st, int* Ho, int* Wo, const float* slope = nullptr) {
+                    int coff, hipStream_t st, int* Ho, int* Wo, const float* slope = nullptr, const float* res = nullptr, int ldr = 0) {
     if (EPI == CONV_EPI_PRELU && !slope) return USPACE_ERR_ARG;
+    if (EPI == CONV_EPI_ADD_RELU && (!res || ldr < c.cout)) return USPACE_ERR_ARG;
     ConvArgs a;
     a.x = x;
     a.w = w;
@@ -215,6 +226,8 @@ int conv_f32_launch(const ConvSpec& c, const float* x, int B, int H, int W, cons
     a.coff = coff;
     a.M = B * a.Ho * a.Wo;
     a.slope = slope;
+    a.res = res;
+    a.ldr = ldr;
     const dim3 grid(us_cdiv(a.M, BM), us_cdiv(c.cout, BN));
     if (c.cin % 16 == 0)
         hipLaunchKernelGGL((conv_kernel<true, EPI>), grid, dim3(256), 0, st, a);
@@ -227,7 +240,7 @@ int conv_f32_launch(const ConvSpec& c, const float* x, int B, int H, int W, cons
 }
 // every translation unit carries the default epilogue's two kernels, as it did while that launcher was not a template
 template int conv_f32_launch<CONV_EPI_RELU>(const ConvSpec&, const float*, int, int, int, const float*, const float*, float*, int, int,
-                                            hipStream_t, int*, int*, const float*);
+                                            hipStream_t, int*, int*, const float*, const float*, int);
 
 // ---- weight packing.  Where a packed convolution's scale and bias come from: the eval-mode batch norm that follows it
 // (gamma != NULL), folded in fp64 and rounded once to fp32 -- W' = w s_n, s_n = gamma_n / sqrt(var_n + eps), bias_n = beta_n - mean_n s_n;

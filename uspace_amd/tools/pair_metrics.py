@@ -63,7 +63,10 @@ class PairMetrics:
     weight file's path; with neither, ``LPIPS(net)`` needs its weights at first use and says so.  ``structure``: a
     ``DinoVisionTransformer`` (usually ``DINO_B8``) adds a ``structure`` column, ``dino_metrics.structure_distance`` of every
     pair on that tower's last-layer keys; ``identity``: an ArcFace ``Backbone`` (usually ``IR_SE50``) adds an ``identity`` column,
-    ``id_metrics.id_similarity`` of every pair (keyword only).  The defaults None leave the three columns as they are."""
+    ``id_metrics.id_similarity`` of every pair (keyword only).  The defaults None leave the three columns as they are.
+    ``attributes``: a property, None by default; set to an ``attr_metrics.AttributeEffect`` before the first ``update`` it adds that
+    edit's ``target_shift``, ``target_hit``, ``off_target`` and ``selectivity`` columns (``attr_metrics.attribute_effect`` of every
+    pair).  It is not a parameter of ``__init__``, whose parameter list is pinned as it is."""
 
     def __init__(self, device=None, lpips=None, net="alex", structure=None, *, identity=None):
         self.device = _inputs.rocm_device(device, "PairMetrics")
@@ -71,6 +74,18 @@ class PairMetrics:
         self._lpips = lpips
         self._structure = structure
         self._identity = identity
+        self._attributes = None
+        self.reset()
+
+    @property
+    def attributes(self):
+        return self._attributes
+
+    @attributes.setter
+    def attributes(self, effect):
+        if self.n:
+            raise ValueError("PairMetrics.attributes must be set before the first update (or after reset)")
+        self._attributes = effect
         self.reset()
 
     @property
@@ -85,6 +100,9 @@ class PairMetrics:
             self._parts["structure"] = []
         if self._identity is not None:
             self._parts["identity"] = []
+        if self._attributes is not None:
+            from uspace_amd.tools.attr_metrics import COLUMNS
+            self._parts.update({k: [] for k in COLUMNS})
 
     @property
     def n(self):
@@ -113,10 +131,15 @@ class PairMetrics:
         if self._identity is not None:
             from uspace_amd.tools.id_metrics import id_similarity
             self._parts["identity"].append(id_similarity(self._identity, x, y, quantize=False))     # x, y are quantised above
+        if self._attributes is not None:
+            from uspace_amd.tools.attr_metrics import COLUMNS
+            cols = self._attributes.columns(x, y, quantize=False)                                   # fp64 [B, 4]; likewise
+            for i, k in enumerate(COLUMNS):
+                self._parts[k].append(cols[:, i].contiguous())
 
     def compute(self):
-        """dict(lpips, ssim, psnr, n) -- with ``structure=`` also ``structure``, with ``identity=`` also ``identity`` --: the means
-        over the pairs seen (numpy fp64 means of ``values``)."""
+        """dict(lpips, ssim, psnr, n) -- with ``structure=`` also ``structure``, with ``identity=`` also ``identity``, with
+        ``attributes`` set also its four columns --: the means over the pairs seen (numpy fp64 means of ``values``)."""
         v = self.values
         n = len(v["psnr"])
         if n == 0:
