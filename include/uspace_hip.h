@@ -920,6 +920,101 @@ USPACE_API int uspace_attr_effect_f64(const float* za, const float* zb, const in
                                       int B, int A, double* out, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Segmentation operators and the pair reductions of the segmentation-consistency metric (uspace_amd/tools/seg_metrics.py;
+ * csrc/segformer.hip).  No workspace, no floating-point atomics; every output element has one thread, every pair one workgroup and
+ * one summation order, so a result is bit-identical whatever batch it sits in.  All pointers are device pointers.  Sides (h, w, H,
+ * W, Ho, Wo) are 1 .. 16384, label counts L 1 .. 256; anything else gives USPACE_ERR_ARG.  Added without a change of
+ * USPACE_ABI_VERSION: symbols only.
+ * ------------------------------------------------------------------------------------- */
+/* Attention with few resident keys and many queries (csrc/attention_kv.hip; SegFormer's spatially reduced attention): q bf16
+ * [B, Lq, ldq] (head h in columns 64 h .. 64 h + 63), kv bf16 [B, Lk, ldkv] (k of head h in columns 64 h .., v in columns
+ * 64 (H + h) ..), out bf16 [B, Lq, ldo].  Head dim 64, softmax of q.k / 8 over the Lk keys, 1 <= Lk <= 336, any Lq >= 1.  K and V
+ * of a (sample, head) are staged once per workgroup; the queries are cut into chunks of whole 16-row tiles, one workgroup each.
+ * A row's arithmetic is uspace_attention_bf16's (fp32 softmax, P rounded once to bf16, row sum by the all-ones MFMA) and its bits do
+ * not depend on the chunking or on its place in the batch.  ldq, ldkv multiples of 8, ldo of 4, q and kv 16-byte aligned.
+ * uspace_attention_kv_plan: what the launch uses, out[7] = {key tiles compiled for, waves per workgroup, query tiles per chunk,
+ * chunks per (sample, head), grid, block, LDS bytes}; the chunk rule is reasoned, not measured (see the file's head). */
+USPACE_API int uspace_attention_kv_plan(int B, int Lq, int Lk, int H, int* out);
+USPACE_API int uspace_attention_kv_bf16(const uint16_t* q, int ldq, const uint16_t* kv, int ldkv, uint16_t* out, int ldo, int B, int Lq,
+                                        int Lk, int H, uspace_stream_t stream);
+/* y = GELU(depthwise 3 x 3 convolution of x + bias), zero padding 1: x, y bf16 NHWC [B, H, W, C] (y != x), w fp32 [9][C] with tap
+ * ty * 3 + tx reading pixel (y + ty - 1, x + tx - 1), bias fp32 [C].  fp32: acc = bias, then one fma per tap in (ty, tx) order, taps
+ * outside the map left out; the erf-GELU of the GEMM epilogue; one rounding to bf16.  C a multiple of 8, pointers 16-byte aligned. */
+USPACE_API int uspace_dwconv3x3_gelu_bf16(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int B, int H, int W,
+                                          int C, uspace_stream_t stream);
+/* Bilinear resampling, align_corners = False (torch.nn.functional.interpolate): x fp32 NHWC [B, h, w, C] -> channels coff ..
+ * coff + C - 1 of y, fp32 [B, Ho, Wo, ldo]: a concatenation is written in place.  The source coordinate ((2 d + 1) in - out) /
+ * (2 out), clamped at 0, is split into tap and weight in integers; in == out copies. */
+USPACE_API int uspace_bilinear_nhwc_f32(const float* x, int B, int h, int w, int C, float* y, int Ho, int Wo, int ldo, int coff,
+                                        uspace_stream_t stream);
+/* labels uint8 [B, H, W] = argmax over the L channels of logits fp32 NHWC [B, h, w, L] resampled to H x W by the arithmetic of
+ * uspace_bilinear_nhwc_f32 (bit for bit), the lowest index on ties; a NaN never wins.  The resampled logits are not stored. */
+USPACE_API int uspace_seg_labels_u8(const float* logits, int B, int h, int w, int L, uint8_t* labels, int H, int W,
+                                    uspace_stream_t stream);
+/* counts int32 [B, 3, L] of two label maps la, lb uint8 [B, npx]: pixels of each label in a, in b, and in both at once.  Labels
+ * >= L are counted nowhere.  B <= 65535, npx < 2^31. */
+USPACE_API int uspace_seg_pair_counts(const uint8_t* la, const uint8_t* lb, int B, long npx, int L, int* counts,
+                                      uspace_stream_t stream);
+/* out fp64 [B, 2] = { sum of (img_a - img_b)^2 over the 3 channels, number of pixels } over the pixels whose label is in the set
+ * `member` (uint8 [L], nonzero = in the set) in NEITHER map; images fp32 NCHW [B, 3, H, W], la, lb uint8 [B, H, W].  Differences
+ * and sum in fp64 in one fixed order.  Labels >= L are in no set. */
+USPACE_API int uspace_seg_region_sse_f64(const float* img_a, const float* img_b, const uint8_t* la, const uint8_t* lb,
+                                         const uint8_t* member, int L, int B, int H, int W, double* out, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * SegFormer (uspace_amd/libs/segformer.py; csrc/segformer.hip): Hugging Face SegformerForSemanticSegmentation in eval mode, the
+ * MiT encoder of four stages with the all-MLP decode head.  Stage i: overlapping patch embedding (convolution 7 x 7 stride 4
+ * padding 3 for stage 0, 3 x 3 stride 2 padding 1 after, with bias) and LayerNorm; depths[i] blocks x += o_proj(attn(LN1 x)),
+ * x += fc2(GELU(dwconv3x3(fc1(LN2 x)))), where q = q_proj(LN1 x) and k, v are linear maps of LN1 x reduced by a convolution of
+ * kernel = stride = sr[i] without padding and LayerNormed (sr[i] == 1: of LN1 x itself), softmax of q.k / 8; a LayerNorm closes
+ * the stage.  Head: per-stage Linear hidden[i] -> decoder_dim, bilinear resize (align_corners = False) to the stage-0 map,
+ * concatenation in reversed stage order, 1 x 1 convolution without bias + BatchNorm (running statistics) + ReLU, 1 x 1 classifier.
+ * Convolutions and the head run in fp32 (fp32 MFMA), the five linears of a block on uspace_gemm_bf16 with the residual stream in
+ * fp32.  A sample's maps and logits are bit-identical whatever B it sits in and wherever it sits in the batch.  Added without a
+ * change of USPACE_ABI_VERSION: symbols only.
+ * ------------------------------------------------------------------------------------- */
+/* (struct-then-typedef, as uspace_resnet_config; the binding is uspace_amd/_hip.py SegformerConfig) */
+struct uspace_segformer_config {
+    int hidden[4];    /* C_i: multiples of 64, at most 2048 */
+    int depths[4];    /* blocks per stage, each >= 1 */
+    int heads[4];     /* heads[i] * 64 == hidden[i]: head dim 64 only (MiT-B0 has 32) */
+    int sr[4];        /* 8, 4, 2, 1 in every published model; 1 .. 16 */
+    int mlp[4];       /* Mix-FFN width over hidden[i], 1 .. 8 */
+    int decoder_dim;  /* D: a multiple of 4, at most 2048 */
+    int num_labels;   /* 1 .. 256 */
+    float eps_embed;  /* the patch embeddings' LayerNorm */
+    float eps_block;  /* layernorm_before / layernorm_after */
+    float eps_sr;     /* the sequence reduction's LayerNorm */
+    float eps_stage;  /* the LayerNorm that closes a stage */
+    float eps_bn;     /* the head's BatchNorm */
+};
+typedef struct uspace_segformer_config uspace_segformer_config;
+
+/* parameter tensors in the module's state_dict order with num_batches_tracked dropped.  Per stage: patch_embeddings.proj.{weight,
+ * bias}, patch_embeddings.layer_norm.*; per block layernorm_before.*, attention.{q_proj, k_proj, v_proj, o_proj}.{weight, bias},
+ * attention.sequence_reduction.sequence_reduction.{weight, bias} and .layer_norm.* (only where sr > 1), layernorm_after.*,
+ * mlp.fc1.*, mlp.dwconv.dwconv.{weight [4C, 1, 3, 3], bias}, mlp.fc2.*; the stage's layer_norm.*.  Then decode_head.
+ * linear_projections.i.proj.*, linear_fuse.weight, batch_norm.{weight, bias, running_mean, running_var}, classifier.*.
+ * An invalid config gives USPACE_ERR_ARG (-1 from param_numel) / 0 bytes.  H and W from 32 to 16384; every reduced key map at most
+ * 336 positions (images up to about 576^2 with the published sr); B 1 .. 32767; otherwise USPACE_ERR_ARG / 0 bytes. */
+USPACE_API int uspace_segformer_num_params(const uspace_segformer_config* cfg);
+USPACE_API long uspace_segformer_param_numel(const uspace_segformer_config* cfg, int index);
+USPACE_API size_t uspace_segformer_weight_bytes(const uspace_segformer_config* cfg);
+USPACE_API size_t uspace_segformer_workspace_bytes(const uspace_segformer_config* cfg, int B, int H, int W);
+USPACE_API int uspace_segformer_pack_weights(const uspace_segformer_config* cfg, const float* const* params, int n_params, void* blob,
+                                             size_t blob_bytes, uspace_stream_t stream);
+/* x_nhwc: fp32 [B, H, W, 3], normalised (uspace_resnet_preprocess's output) -> logits fp32 NHWC [B, h, w, num_labels] at the
+ * stage-0 map h = (H - 1) / 4 + 1, w = (W - 1) / 4 + 1 */
+USPACE_API int uspace_segformer_forward(const uspace_segformer_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                        const float* x_nhwc, int B, int H, int W, float* logits, uspace_stream_t stream);
+/* Test aid.  Stages in order, all fp32 NHWC: per encoder stage the patch embedding after its LayerNorm, every block's output,
+ * the stage's closing LayerNorm ([B, h_i, w_i, hidden[i]]); then the concatenation [B, h_0, w_0, 4 D], the fused map
+ * [B, h_0, w_0, D], the logits.  uspace_segformer_num_stages counts them.  Nothing after the stage runs. */
+USPACE_API int uspace_segformer_num_stages(const uspace_segformer_config* cfg);
+USPACE_API int uspace_segformer_tap(const uspace_segformer_config* cfg, const void* blob, void* workspace, size_t workspace_bytes,
+                                    const float* x_nhwc, int B, int H, int W, int stage, float* dump, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

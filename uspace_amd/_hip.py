@@ -69,6 +69,12 @@ class ResnetConfig(ctypes.Structure):
                 ("num_outputs", ctypes.c_int)]
 
 
+class SegformerConfig(ctypes.Structure):
+    _fields_ = [("hidden", ctypes.c_int * 4), ("depths", ctypes.c_int * 4), ("heads", ctypes.c_int * 4), ("sr", ctypes.c_int * 4),
+                ("mlp", ctypes.c_int * 4), ("decoder_dim", ctypes.c_int), ("num_labels", ctypes.c_int), ("eps_embed", ctypes.c_float),
+                ("eps_block", ctypes.c_float), ("eps_sr", ctypes.c_float), ("eps_stage", ctypes.c_float), ("eps_bn", ctypes.c_float)]
+
+
 class GemmExt(ctypes.Structure):
     _fields_ = [("row_c", ctypes.c_void_p), ("out_cen", ctypes.c_void_p), ("ld_cen", ctypes.c_int),
                 ("part_out", ctypes.c_void_p), ("part_in", ctypes.c_void_p), ("np_in", ctypes.c_int),
@@ -232,6 +238,21 @@ SIGNATURES = {
     "uspace_resnet_forward": (_I, [ctypes.POINTER(ResnetConfig), _P, _P, _SZ, _P, _I, _I, _I, _P, _P, _P]),
     "uspace_resnet_tap": (_I, [ctypes.POINTER(ResnetConfig), _P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P]),
     "uspace_attr_effect_f64": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "uspace_attention_kv_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "uspace_attention_kv_bf16": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "uspace_dwconv3x3_gelu_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "uspace_bilinear_nhwc_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "uspace_seg_labels_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "uspace_seg_pair_counts": (_I, [_P, _P, _I, _L, _I, _P, _P]),
+    "uspace_seg_region_sse_f64": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "uspace_segformer_num_params": (_I, [ctypes.POINTER(SegformerConfig)]),
+    "uspace_segformer_param_numel": (_L, [ctypes.POINTER(SegformerConfig), _I]),
+    "uspace_segformer_weight_bytes": (_SZ, [ctypes.POINTER(SegformerConfig)]),
+    "uspace_segformer_workspace_bytes": (_SZ, [ctypes.POINTER(SegformerConfig), _I, _I, _I]),
+    "uspace_segformer_pack_weights": (_I, [ctypes.POINTER(SegformerConfig), ctypes.POINTER(_P), _I, _P, _SZ, _P]),
+    "uspace_segformer_forward": (_I, [ctypes.POINTER(SegformerConfig), _P, _P, _SZ, _P, _I, _I, _I, _P, _P]),
+    "uspace_segformer_num_stages": (_I, [ctypes.POINTER(SegformerConfig)]),
+    "uspace_segformer_tap": (_I, [ctypes.POINTER(SegformerConfig), _P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),
@@ -640,6 +661,110 @@ def inception_score_splits(logits, splits, ws=None):
     check(lib().uspace_inception_score_f64(ptr(logits), N, C, int(splits), ptr(ws), ws.numel(), ptr(scores), stream_ptr()),
           "uspace_inception_score_f64")
     return scores
+
+
+def attention_kv_plan(B, Lq, Lk, H):
+    """dict(NT, NW, chunk, nchunks, grid, block, lds): what ``attention_kv`` launches for these sizes (no device needed)."""
+    out = (ctypes.c_int * 7)()
+    check(lib().uspace_attention_kv_plan(int(B), int(Lq), int(Lk), int(H), out), "uspace_attention_kv_plan")
+    return dict(zip(("NT", "NW", "chunk", "nchunks", "grid", "block", "lds"), out))
+
+
+def attention_kv(q, kv, H, out=None):
+    """Attention of many queries over few resident keys: q bf16 [B, Lq, ldq >= 64 H], kv bf16 [B, Lk, ldkv >= 128 H] (k | v),
+    Lk <= 336 -> bf16 [B, Lq, 64 H] (``out``: a bf16 [B, Lq, ldo] tensor to write the first 64 H columns of)."""
+    for t, name in ((q, "q"), (kv, "kv")) + (((out, "out"),) if out is not None else ()):
+        require_device(t, name)
+        if t.dtype != torch.bfloat16 or t.dim() != 3 or not t.is_contiguous() or t.shape[0] != q.shape[0]:
+            raise UspaceHipError(f"{name} must be a contiguous bf16 [B, rows, columns] tensor, got {t.dtype} {tuple(t.shape)}")
+    B, Lq, ldq = q.shape
+    if out is None:
+        out = torch.empty(B, Lq, int(H) * 64, dtype=torch.bfloat16, device=q.device)
+    if out.shape[1] != Lq:
+        raise UspaceHipError(f"out must have {Lq} rows per sample, got {tuple(out.shape)}")
+    check(lib().uspace_attention_kv_bf16(ptr(q), ldq, ptr(kv), kv.shape[2], ptr(out), out.shape[2], B, Lq, kv.shape[1], int(H),
+                                         stream_ptr()), "uspace_attention_kv_bf16")
+    return out
+
+
+def _seg_tensor(t, name, dtype, dims):
+    require_device(t, name)
+    if t.dtype != dtype or t.dim() != dims or not t.is_contiguous() or t.numel() < 1:
+        raise UspaceHipError(f"{name} must be a contiguous {dtype} tensor of {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
+
+
+def dwconv3x3_gelu(x, w, bias):
+    """bf16 NHWC [B, H, W, C] -> GELU(depthwise 3 x 3 convolution + bias), zero padding 1, bf16 NHWC; ``w`` fp32 [9, C] (tap
+    ty * 3 + tx), ``bias`` fp32 [C]; C a multiple of 8."""
+    _seg_tensor(x, "x", torch.bfloat16, 4)
+    _seg_tensor(w, "w", torch.float32, 2)
+    _seg_tensor(bias, "bias", torch.float32, 1)
+    B, H, W, C = x.shape
+    if tuple(w.shape) != (9, C) or tuple(bias.shape) != (C,):
+        raise UspaceHipError(f"expected w [9, {C}] and bias [{C}], got {tuple(w.shape)} and {tuple(bias.shape)}")
+    y = torch.empty_like(x)
+    check(lib().uspace_dwconv3x3_gelu_bf16(ptr(x), ptr(w), ptr(bias), ptr(y), B, H, W, C, stream_ptr()), "uspace_dwconv3x3_gelu_bf16")
+    return y
+
+
+def bilinear_nhwc(x, size, out=None, coff=0):
+    """fp32 NHWC [B, h, w, C] -> bilinear (align_corners=False) at ``size`` = (Ho, Wo), written to channels coff .. coff + C - 1 of
+    ``out`` fp32 [B, Ho, Wo, ldo] (allocated [B, Ho, Wo, C] where None): a concatenation is filled slice by slice, never copied."""
+    _seg_tensor(x, "x", torch.float32, 4)
+    B, h, w, C = x.shape
+    Ho, Wo = (int(v) for v in size)
+    if out is None:
+        out = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
+    _seg_tensor(out, "out", torch.float32, 4)
+    if tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise UspaceHipError(f"out must be [{B}, {Ho}, {Wo}, ldo], got {tuple(out.shape)}")
+    check(lib().uspace_bilinear_nhwc_f32(ptr(x), B, h, w, C, ptr(out), Ho, Wo, out.shape[3], int(coff), stream_ptr()),
+          "uspace_bilinear_nhwc_f32")
+    return out
+
+
+def seg_labels(logits, size):
+    """uint8 [B, H, W]: the argmax (lowest index on ties) over the channels of ``logits`` fp32 NHWC [B, h, w, L], L <= 256,
+    resampled to ``size`` = (H, W) as ``bilinear_nhwc`` does; the resampled logits are never stored."""
+    _seg_tensor(logits, "logits", torch.float32, 4)
+    B, h, w, L = logits.shape
+    H, W = (int(v) for v in size)
+    labels = torch.empty(B, max(H, 0), max(W, 0), dtype=torch.uint8, device=logits.device)
+    check(lib().uspace_seg_labels_u8(ptr(logits), B, h, w, L, ptr(labels), H, W, stream_ptr()), "uspace_seg_labels_u8")
+    return labels
+
+
+def _label_maps(la, lb):
+    for t, name in ((la, "la"), (lb, "lb")):
+        require_device(t, name)
+        if t.dtype != torch.uint8 or t.dim() < 2 or not t.is_contiguous() or t.shape != la.shape or t.numel() < 1:
+            raise UspaceHipError(f"{name} must be a contiguous uint8 [B, ...] label map, both of one shape, got {t.dtype} {tuple(t.shape)}")
+
+
+def seg_pair_counts(la, lb, num_labels):
+    """int32 [B, 3, L] on the device: per pair of label maps uint8 [B, ...] the pixels of each label in a, in b, and in both."""
+    _label_maps(la, lb)
+    B, L = la.shape[0], int(num_labels)
+    counts = torch.empty(B, 3, max(L, 0), dtype=torch.int32, device=la.device)
+    check(lib().uspace_seg_pair_counts(ptr(la), ptr(lb), B, la[0].numel(), L, ptr(counts), stream_ptr()), "uspace_seg_pair_counts")
+    return counts
+
+
+def seg_region_sse(img_a, img_b, la, lb, member):
+    """fp64 [B, 2] on the device: (sum of squared differences over the 3 channels, pixel count) of images fp32 [B, 3, H, W] over the
+    pixels whose label (uint8 [B, H, W]) is in the set ``member`` (uint8 [L], nonzero = in) in neither map."""
+    _label_maps(la, lb)
+    _seg_tensor(img_a, "img_a", torch.float32, 4)
+    _seg_tensor(img_b, "img_b", torch.float32, 4)
+    _seg_tensor(member, "member", torch.uint8, 1)
+    B, _, H, W = img_a.shape
+    if img_a.shape != img_b.shape or img_a.shape[1] != 3 or tuple(la.shape) != (B, H, W):
+        raise UspaceHipError(f"expected images [B, 3, H, W] and label maps [B, H, W], got {tuple(img_a.shape)}, {tuple(img_b.shape)} "
+                             f"and {tuple(la.shape)}")
+    out = torch.empty(B, 2, dtype=torch.float64, device=img_a.device)
+    check(lib().uspace_seg_region_sse_f64(ptr(img_a), ptr(img_b), ptr(la), ptr(lb), ptr(member), member.numel(), B, H, W, ptr(out),
+                                          stream_ptr()), "uspace_seg_region_sse_f64")
+    return out
 
 
 def prof_gemm_begin(epi_flags, N, K, max_launches=8192):

@@ -66,7 +66,9 @@ class PairMetrics:
     ``id_metrics.id_similarity`` of every pair (keyword only).  The defaults None leave the three columns as they are.
     ``attributes``: a property, None by default; set to an ``attr_metrics.AttributeEffect`` before the first ``update`` it adds that
     edit's ``target_shift``, ``target_hit``, ``off_target`` and ``selectivity`` columns (``attr_metrics.attribute_effect`` of every
-    pair).  It is not a parameter of ``__init__``, whose parameter list is pinned as it is."""
+    pair).  It is not a parameter of ``__init__``, whose parameter list is pinned as it is.  ``parsing``: a property set and read
+    the same way; a ``seg_metrics.SegmentationConsistency`` adds its ``column_names`` (``agreement``, ``miou`` and, with a region,
+    ``outside_mse``, ``outside_psnr``, ``outside_share``)."""
 
     def __init__(self, device=None, lpips=None, net="alex", structure=None, *, identity=None):
         self.device = _inputs.rocm_device(device, "PairMetrics")
@@ -75,6 +77,18 @@ class PairMetrics:
         self._structure = structure
         self._identity = identity
         self._attributes = None
+        self._parsing = None
+        self.reset()
+
+    @property
+    def parsing(self):
+        return self._parsing
+
+    @parsing.setter
+    def parsing(self, consistency):
+        if self.n:
+            raise ValueError("PairMetrics.parsing must be set before the first update (or after reset)")
+        self._parsing = consistency
         self.reset()
 
     @property
@@ -103,6 +117,8 @@ class PairMetrics:
         if self._attributes is not None:
             from uspace_amd.tools.attr_metrics import COLUMNS
             self._parts.update({k: [] for k in COLUMNS})
+        if self._parsing is not None:
+            self._parts.update({k: [] for k in self._parsing.column_names})
 
     @property
     def n(self):
@@ -136,10 +152,13 @@ class PairMetrics:
             cols = self._attributes.columns(x, y, quantize=False)                                   # fp64 [B, 4]; likewise
             for i, k in enumerate(COLUMNS):
                 self._parts[k].append(cols[:, i].contiguous())
+        if self._parsing is not None:
+            for k, v in self._parsing.columns(x, y, quantize=False).items():                       # fp64 numpy [B]; likewise
+                self._parts[k].append(torch.from_numpy(np.ascontiguousarray(v)))
 
     def compute(self):
         """dict(lpips, ssim, psnr, n) -- with ``structure=`` also ``structure``, with ``identity=`` also ``identity``, with
-        ``attributes`` set also its four columns --: the means over the pairs seen (numpy fp64 means of ``values``)."""
+        ``attributes`` set also its four columns, with ``parsing`` set also its columns --: the means over the pairs seen (numpy fp64 means of ``values``)."""
         v = self.values
         n = len(v["psnr"])
         if n == 0:
