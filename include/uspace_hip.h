@@ -1015,6 +1015,31 @@ USPACE_API int uspace_segformer_tap(const uspace_segformer_config* cfg, const vo
                                     const float* x_nhwc, int B, int H, int W, int stage, float* dump, uspace_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Local edits (uspace_amd/tools/local_edit.py, CNF.decode_local; csrc/local_edit.hip): the velocity blend of a paired solve and
+ * the masks it takes.  Enqueued on `stream`; no atomics, every sum in one fixed order, a sample's result bit-identical whatever
+ * batch it sits in.  All pointers are device pointers.  Added without a change of USPACE_ABI_VERSION: symbols only.
+ * ------------------------------------------------------------------------------------- */
+/* pair fp32 [2B, C, cells], source rows first; mask fp32 [B, cells], broadcast over C.  out rows [0, B) = the source rows as they
+ * are; row B + b per element, with s = pair[b], e = pair[B + b], m = mask[b, p]: m <= 0 or NaN -> s, m >= 1 -> e (both bit for
+ * bit), otherwise fmaf(m, e - s, s).  out == pair (in place) or disjoint from it.  16-byte accesses where cells % 4 == 0 and the
+ * three pointers are 16-byte aligned, a scalar form otherwise. */
+USPACE_API int uspace_pair_blend(const float* pair, const float* mask, int B, int C, long cells, float* out, uspace_stream_t stream);
+/* mask fp32 [B, S, S] from label maps uint8 [B, H, W] and the set `member` (uint8 [256], nonzero = in the region); H and W
+ * multiples of S, S 1 .. 64, sides up to 16384.  Per cell share = (float)count / (float)(H/S * W/S), count the member pixels of
+ * the cell (an integer); v = the maximum of share over the (2 dilate + 1)^2 window of cells clipped at the border, dilate 0 .. 4;
+ * soft != 0 stores v, otherwise v > thr ? 1 : 0. */
+USPACE_API int uspace_mask_from_labels(const uint8_t* labels, int B, int H, int W, const uint8_t* member, int S, int dilate, float thr,
+                                       int soft, float* mask, uspace_stream_t stream);
+/* mask fp32 [R, G * patch, G * patch] from maps fp32 [n_blocks, R, G * G, nk] (uspace_uvit_forward_maps' image x context window),
+ * block_w fp32 [n_blocks] and cols fp32 [R, nk].  Per row r: a[p] = sum_blk block_w[blk] * (sum_j cols[r, j] * maps[blk, r, p, j])
+ * in fp32, blocks ascending, columns ascending, one fused multiply-add per term from 0 (terms of a block or a column of weight 0
+ * are left out); the 3 x 3 maximum over the G x G grid clipped at the border; divided by the row's maximum; soft != 0 stores that,
+ * otherwise > thr ? 1 : 0; every token cell goes to its patch x patch cells.  A row whose maximum is not above 0 is all 0.
+ * G 1 .. 64, patch 1 .. 16. */
+USPACE_API int uspace_mask_from_maps(const float* maps, int n_blocks, int R, int G, int nk, const float* block_w, const float* cols,
+                                     int patch, float thr, int soft, float* mask, uspace_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py): record HIP events, on the launching stream, around every
  * uspace_gemm_bf16 launch whose (epi_flags, N, K) match, up to max_launches; _end() waits for
  * the recorded events and returns their summed duration.  Off unless _begin() was called.

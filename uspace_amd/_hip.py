@@ -253,6 +253,9 @@ SIGNATURES = {
     "uspace_segformer_forward": (_I, [ctypes.POINTER(SegformerConfig), _P, _P, _SZ, _P, _I, _I, _I, _P, _P]),
     "uspace_segformer_num_stages": (_I, [ctypes.POINTER(SegformerConfig)]),
     "uspace_segformer_tap": (_I, [ctypes.POINTER(SegformerConfig), _P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P]),
+    "uspace_pair_blend": (_I, [_P, _P, _I, _I, _L, _P, _P]),
+    "uspace_mask_from_labels": (_I, [_P, _I, _I, _I, _P, _I, _I, _F, _I, _P, _P]),
+    "uspace_mask_from_maps": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _F, _I, _P, _P]),
     "uspace_prof_gemm_begin": (_I, [_I, _I, _I, _I]),
     "uspace_prof_gemm_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
     "uspace_prof_all_begin": (_I, [_I]),
@@ -765,6 +768,59 @@ def seg_region_sse(img_a, img_b, la, lb, member):
     check(lib().uspace_seg_region_sse_f64(ptr(img_a), ptr(img_b), ptr(la), ptr(lb), ptr(member), member.numel(), B, H, W, ptr(out),
                                           stream_ptr()), "uspace_seg_region_sse_f64")
     return out
+
+
+def pair_blend(pair, mask, out=None):
+    """The velocity blend of a paired solve: ``pair`` fp32 [2B, C, ...] (source rows first), ``mask`` fp32 [B, cells] (or [B, ...] of
+    that many cells) -> ``out`` (``pair`` itself where None: in place) with the source rows unchanged and row B + b the edited row
+    where the mask is 1, the source row where it is 0, fmaf(m, e - s, s) between."""
+    require_device(pair, "pair")
+    if pair.dtype != torch.float32 or not pair.is_contiguous() or pair.dim() < 2 or pair.shape[0] < 2 or pair.shape[0] % 2:
+        raise ValueError(f"pair must be a contiguous fp32 [2B, C, ...] tensor, got {pair.dtype} {tuple(pair.shape)}")
+    B, C = pair.shape[0] // 2, pair.shape[1]
+    cells = pair.numel() // (2 * B * C)
+    if not (mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == B * cells):
+        raise ValueError(f"mask must be a contiguous fp32 device tensor of {B} x {cells} entries, got {mask.dtype} {tuple(mask.shape)}")
+    if out is None:
+        out = pair
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != pair.shape or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous fp32 device tensor like pair, got {out.dtype} {tuple(out.shape)}")
+    check(lib().uspace_pair_blend(ptr(pair), ptr(mask), B, C, cells, ptr(out), stream_ptr()), "uspace_pair_blend")
+    return out
+
+
+def mask_from_labels(labels, member, S, dilate=0, thr=0.0, soft=False):
+    """fp32 [B, S, S]: per latent cell the share of pixels of ``labels`` (uint8 [B, H, W]) whose label is in ``member`` (uint8 [256],
+    nonzero = in), dilated by a maximum over (2 dilate + 1)^2 cells; ``soft`` keeps the share, otherwise share > thr."""
+    _seg_tensor(labels, "labels", torch.uint8, 3)
+    _seg_tensor(member, "member", torch.uint8, 1)
+    if member.numel() != 256:
+        raise UspaceHipError(f"member must have 256 entries, got {member.numel()}")
+    B, H, W = labels.shape
+    mask = torch.empty(B, max(int(S), 0), max(int(S), 0), dtype=torch.float32, device=labels.device)
+    check(lib().uspace_mask_from_labels(ptr(labels), B, H, W, ptr(member), int(S), int(dilate), float(thr), 1 if soft else 0, ptr(mask),
+                                        stream_ptr()), "uspace_mask_from_labels")
+    return mask
+
+
+def mask_from_maps(maps, block_w, cols, G, patch, thr=0.3, soft=False):
+    """fp32 [R, G * patch, G * patch] from attention maps fp32 [n_blocks, R, G * G, nk], block weights fp32 [n_blocks] and token
+    columns fp32 [R, nk]: the weighted maps summed over the chosen columns, 3 x 3 max-pooled, divided by the row's maximum,
+    thresholded (``soft``: not), spread over patch x patch latent cells."""
+    for t, name in ((maps, "maps"), (block_w, "block_w"), (cols, "cols")):
+        require_device(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise UspaceHipError(f"{name} must be a contiguous fp32 tensor, got {t.dtype} {tuple(t.shape)}")
+    G, patch = int(G), int(patch)
+    if maps.dim() != 4 or maps.shape[2] != G * G or tuple(block_w.shape) != (maps.shape[0],) or tuple(cols.shape) != (maps.shape[1], maps.shape[3]):
+        raise UspaceHipError(f"expected maps [n_blocks, R, {G * G}, nk], block_w [n_blocks] and cols [R, nk], got {tuple(maps.shape)}, "
+                             f"{tuple(block_w.shape)} and {tuple(cols.shape)}")
+    n_blocks, R, _, nk = maps.shape
+    side = max(G * patch, 0)
+    mask = torch.empty(R, side, side, dtype=torch.float32, device=maps.device)
+    check(lib().uspace_mask_from_maps(ptr(maps), n_blocks, R, G, nk, ptr(block_w), ptr(cols), patch, float(thr), 1 if soft else 0,
+                                      ptr(mask), stream_ptr()), "uspace_mask_from_maps")
+    return mask
 
 
 def prof_gemm_begin(epi_flags, N, K, max_launches=8192):

@@ -111,9 +111,10 @@ class CNFBase(nn.Module):
         self.last_stats = stats
         return out
 
-    def _solve(self, cond, x, t0, t1, kwargs, force_fixed=False):
+    def _solve(self, cond, x, t0, t1, kwargs, force_fixed=False, func=None):
         self.last_stats = Stats()
-        func = lambda t, xx: self._velocity(t, xx, cond, kwargs)
+        if func is None:
+            func = lambda t, xx: self._velocity(t, xx, cond, kwargs)
         sk = kwargs["solver_kwargs"]            # KeyError if absent, as in the reference
         n_steps = sk.get("n_steps") if hasattr(sk, "get") else None
         if force_fixed:
@@ -131,6 +132,96 @@ class CNFBase(nn.Module):
         fixed_kw, adaptive_kw = self.get_ode_kwargs(**kwargs)
         mid = self._integrate(func, z, t0, t_mid, fixed_kw)
         return self._integrate(func, mid, t_mid, t1, adaptive_kw)
+
+    # ------------------------------------------------------------------ local edits: the paired solve
+    _WRITE_NAMES = ("write_attr", "write_pca")
+
+    def _local_kwargs(self, B, kwargs):
+        """The keywords of a paired solve over 2B rows (source rows first) from those of the edit: the refusals, ``write_scale`` as
+        ``cat(zeros(B), s)`` and ``target_context_ids`` as ``[empty] * B + ids`` -- the per-row mechanisms the network already has.
+        Host work only."""
+        import numpy as np
+        if kwargs.get("cfg_scale") is not None:
+            raise ValueError("decode_local under cfg_scale is not supported: a guided local edit would run 4B rows")
+        if kwargs.get("dissect_name") == "read":
+            raise ValueError("decode_local with a read hook is not supported: the hook would save the 2B rows of both branches")
+        if kwargs.get("vis_am_path") is not None:
+            raise ValueError("decode_local with vis_am_path is not supported: draw the maps in a plain decode")
+        kw = dict(kwargs)
+        if kw.get("dissect_name") in self._WRITE_NAMES:
+            s = kw.get("write_scale")
+            if torch.is_tensor(s):
+                s = s.detach().cpu().numpy()
+            s = np.asarray(0.0 if s is None else s, dtype=np.float32).reshape(-1)
+            if s.size not in (1, B):
+                raise ValueError(f"write_scale has {s.size} entries for a batch of {B}")
+            kw["write_scale"] = np.concatenate([np.zeros(B, np.float32), np.broadcast_to(s, (B,))])
+        if kw.get("target_context_ids") is not None:
+            ids = list(kw["target_context_ids"])
+            if len(ids) != B:
+                raise ValueError(f"target_context_ids holds {len(ids)} lists for a batch of {B}")
+            kw["target_context_ids"] = [np.array([], dtype=np.int64) for _ in range(B)] + ids
+        return kw
+
+    def _local_mask(self, mask, z):
+        """``mask`` of ``decode_local`` -> a contiguous fp32 device tensor [B, S * S], or the mask object itself where it is made at
+        every evaluation (``tools.local_edit.AttentionWordMask``)."""
+        import numpy as np
+        from .tools import local_edit
+        B, S = z.shape[0], z.shape[-1]
+        if isinstance(mask, local_edit.AttentionWordMask):
+            return mask
+        if isinstance(mask, local_edit.LabelRegionMask):
+            if mask.mask is None:
+                raise ValueError("the LabelRegionMask is not bound to images: pass region.of(images, S)")
+            mask = mask.mask
+        if mask is None:
+            raise ValueError("decode_local needs mask=")
+        m = mask.detach() if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask, dtype=np.float32)))
+        shape = tuple(m.shape)
+        if z.dim() != 4 or z.shape[2] != S or shape not in ((S, S), (B, S, S), (B, 1, S, S)):
+            raise ValueError(f"mask must be [{S},{S}], [{B},{S},{S}] or [{B},1,{S},{S}] for latents {tuple(z.shape)}, got {shape}")
+        m = m.to(torch.float32)
+        if not bool(((m >= 0) & (m <= 1)).all()):            # NaN compares false
+            raise ValueError("mask values must lie in [0, 1] (and none may be NaN)")
+        if m.dim() == 2:
+            m = m.expand(B, S, S)
+        return m.to(z.device).reshape(B, S * S).contiguous()
+
+    def _decode_local(self, z, cond2, mask, kwargs, maps_velocity=None):
+        """The paired solve: state of 2B rows (source rows first, both branches from ``z``), one network call over the 2B rows per
+        evaluation (always eager), then one ``uspace_pair_blend`` that puts the source's velocity in the edited rows wherever the
+        mask is 0.  Goes through ``_solve`` like every decode; ``last_stats`` counts evaluations of 2B rows, and an error-controlled
+        solve takes its norm over the 2B rows.  -> (edited, source)."""
+        from . import _hip
+        B = z.shape[0]
+        kw = self._local_kwargs(B, kwargs)
+        m = self._local_mask(mask, z)
+        z2 = torch.cat([z, z])
+
+        def blended(v, mm):
+            if v.dtype == torch.float32 and v.is_contiguous():
+                return _hip.pair_blend(v, mm)
+            return _hip.pair_blend(v.to(torch.float32).contiguous(), mm).to(v.dtype)
+
+        if torch.is_tensor(m):
+            func = lambda t, xx: blended(self._velocity(t, xx, cond2, kw), m)
+        else:
+            if maps_velocity is None:
+                raise ValueError("an AttentionWordMask needs the text-to-image driver: this network has no word columns")
+            m.check(self.net, B)
+
+            def func(t, xx):
+                _ts, th = self._timesteps(t, xx)
+                if th is None:
+                    raise ValueError("an AttentionWordMask needs one time for the whole batch")
+                if m.all_ones_at(th):
+                    return self._velocity(t, xx, cond2, kw)             # mask == 1: the edited rows keep their own velocity
+                v, maps = maps_velocity(t, xx, cond2, kw, m.window(self.net))
+                return blended(v, m.from_maps(self.net, maps, th))
+
+        out = self._solve(cond2, z2, 0.0, 1.0, kw, func=func)
+        return out[B:], out[:B]
 
 
 class CNF(CNFBase):
@@ -160,6 +251,21 @@ class CNF(CNFBase):
         return self._fixadp(func, z, 0.0, t_mid, 1.0, kwargs)
 
     sample_ode = decode
+
+    def decode_local(self, z, y=None, *, mask=None, source=None, **kwargs):
+        """A local edit: ``decode(z, y, **kwargs)`` (a ``write_attr`` / ``write_pca`` edit) and the same decode without the edit in
+        one paired solve, the edited branch following the source's velocity wherever ``mask`` is 0 -> (edited, source).  Outside the
+        mask the edited latents are bit-equal to the source's under every solver.  ``mask``: [S, S], [B, S, S] or [B, 1, S, S] in
+        [0, 1], or a ``tools.local_edit.LabelRegionMask`` bound to images.  ``source``: ``dict(y=...)``, the source branch's labels
+        where they differ."""
+        ys = (source or {}).get("y", y)
+        if (y is None) != (ys is None):
+            raise ValueError("y and source['y'] must both be given or both be None")
+        y2 = None
+        if y is not None:
+            y = torch.as_tensor(y).reshape(-1)
+            y2 = torch.cat([torch.as_tensor(ys).reshape(-1).to(y.device), y])
+        return self._decode_local(z, y2, mask, kwargs)
 
     def decode_write_scales(self, z, y, write_scales, **kwargs):
         """The reference's sweep ``for write_scale in write_scales: decode(z, write_scale=...)``

@@ -86,7 +86,15 @@ class UViT(UViTBase):
 
     def forward(self, x, timesteps, context, **kwargs):
         """kwargs: the reference's, and ``cfg_scale`` (None: no guidance; a number; or B per-sample values -- a guidance sweep in one
-        solve) with ``empty_context`` ([77, clip_dim] or [B, 77, clip_dim])."""
+        solve) with ``empty_context`` ([77, clip_dim] or [B, 77, clip_dim]); ``maps_window=(q0, nq, k0, nk)`` (opt-in, what a paired
+        local edit with an ``AttentionWordMask`` passes): return ``(pred, maps)`` with the head-mean attention maps
+        [depth + 1, B, nq, nk] of this very evaluation, as ``attention_maps`` gives them."""
+        window = kwargs.get("maps_window")
+        if window is not None:
+            if kwargs.get("cfg_scale") is not None or kwargs.get("vis_am_path") is not None:
+                raise ValueError("maps_window is not available under cfg_scale or together with vis_am_path")
+            ctx, key_scale, _ = self._prepare(x, timesteps, context, kwargs)
+            return self._run(x, timesteps, context=ctx, key_scale=key_scale, attn_maps=tuple(int(v) for v in window))
         guide = None
         if kwargs.get("cfg_scale") is not None:
             guide = self._guidance(x.shape[0], kwargs["cfg_scale"], kwargs.get("empty_context"))
