@@ -80,6 +80,8 @@ __device__ __forceinline__ uint4 widen_pair(uint2 a, uint2 b) {
     return make_uint4(rx[0], ry[0], rx[1], ry[1]);
 }
 
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
 // byte offset inside a [rows][64] bf16 LDS tile of 16-B chunk `c` of row `r` (swizzled)
 __device__ __forceinline__ int lds_off(int r, int c) { return r * ROW_BYTES + ((c ^ ((r >> 1) & 7)) << 4); }
 
@@ -880,8 +882,16 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, char* const smem, c
         }
     };
     const bool interior = (m0 + BM <= m_lim) && (n0 + BN <= g.N);   // workgroup-uniform
+    // The LayerNorm consumers (qkv, fc1) run 3-4 rounds of tiles: their 16-byte bf16 stores are write-through (sc1), so that the dirty output
+    // lines of a round do not push the operand panels out of the XCD's L2 (profiles/epilogue_forms.md: forward -1.1 %, bit-equal).  The
+    // two-stage 256 x 256 bodies only; measured for them alone.
+    constexpr bool WT_BF16 = BM == 256 && BN == 256 && NST == 2 && !SK && LN_IN && (FLAGS & USPACE_EPI_OUT_BF16) != 0;
     if (interior && g.wide) {
         const int nw = n0 + wn * (BN / WN) + (fq & 1) * 16 + (fq >> 1) * 8;   // this lane's column in a widened pair (+ 32 per pair)
+        // write-through stores go through a buffer descriptor on this wave's rows (the aux bits carry sc1): 32-bit byte offsets from there
+        __amdgpu_buffer_rsrc_t wt_rs;
+        if constexpr (WT_BF16)
+            wt_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(g.out_bf16 + (size_t)(m0 + wm * (BM / WM)) * g.ld_bf16 + n0 + wn * (BN / WN)), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             if (SK && (i < own_lo || i >= own_hi)) continue;     // (SK: another K part finishes these rows)
@@ -915,7 +925,13 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, char* const smem, c
             }
 #pragma unroll
             for (int j = 0; j < TN; j += 2) {
-                if constexpr (FLAGS & USPACE_EPI_OUT_BF16) *(uint4*)(g.out_bf16 + (size_t)m * g.ld_bf16 + nw + j * 16) = widen_pair(pk[j], pk[j + 1]);
+                if constexpr (WT_BF16) {
+                    const uint4 w4 = widen_pair(pk[j], pk[j + 1]);
+                    const uint32_t off = (uint32_t)((i * 16 + fr) * g.ld_bf16 + (fq & 1) * 16 + (fq >> 1) * 8 + j * 16) * 2u;
+                    __builtin_amdgcn_raw_buffer_store_b128((u32x4){w4.x, w4.y, w4.z, w4.w}, wt_rs, off, 0, 16 /* sc1 */);
+                } else if constexpr (FLAGS & USPACE_EPI_OUT_BF16) {
+                    *(uint4*)(g.out_bf16 + (size_t)m * g.ld_bf16 + nw + j * 16) = widen_pair(pk[j], pk[j + 1]);
+                }
                 if constexpr (CEN) *(uint4*)(g.out_cen + (size_t)m * g.ld_cen + nw + j * 16) = widen_pair(pc[j], pc[j + 1]);
             }
             row_end(m, true, wm * (BM / WM) + i * 16 + fr, wn);   // main rows: wave (wm, wn) fills slot wn of its rows
@@ -1570,8 +1586,10 @@ int plain_args(GemmArgs& g, const uint16_t* A, int lda, const uint16_t* W, int l
     return USPACE_OK;
 }
 
-// 16-byte stores of the bf16 outputs need 16-byte aligned rows
+// 16-byte stores of the bf16 outputs need 16-byte aligned rows -- and, for the write-through form, which addresses a wave's 128 rows with
+// 32-bit byte offsets from a buffer descriptor of 2^31 - 1 bytes (stores beyond it would be dropped), 128 rows within that range
 int wide_ok(const GemmArgs& g, int epi_flags) {
+    if ((epi_flags & USPACE_EPI_OUT_BF16) && (long)g.ld_bf16 * 2 * 128 >= (1L << 31)) return 0;
     if ((epi_flags & USPACE_EPI_OUT_BF16) && ((g.ld_bf16 & 7) || ((uintptr_t)g.out_bf16 & 15))) return 0;
     if ((epi_flags & USPACE_EPI_CEN_OUT) && ((g.ld_cen & 7) || ((uintptr_t)g.out_cen & 15))) return 0;
     return 1;
